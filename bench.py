@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """bench.py -- RPN inference throughput of the MI355X point-ops hot path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1: re-executes itself under torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W          (N > 1: relaunches itself under torch.distributed.run, one rank per GPU)
+    python bench.py ... --full                             (+ every side measurement below)
+    python bench.py ... --dump-outputs DIR                 (+ what the last timed step returned, as DIR/<name>.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -11,7 +13,8 @@ levels, + cls/reg heads; lib/net/rpn.py:68-82 via pointrcnn_amd/rpn.py) -- over 
 `--batch` frames per GPU); inference needs no collective, so the only distributed traffic is the barrier
 and the max-over-ranks of the elapsed time.  Rank 0 prints ONE JSON line.
 
-Besides the contract fields the line carries
+A plain run sets up, warms up, times the steps and prints the contract fields (metric, value, unit, higher_is_better, dtype,
+ms_per_step, config).  With --full the line also carries
   roofline     -- for the dominant kernel family (the fused per-point MLP, fp32 MFMA): the FLOPs its launches execute
                   (rows actually processed -- device-side counts read back -- x layer widths) / their GPU time, measured
                   with HIP events on the launch stream in an instrumented pass of the same steps; peak = 157.3 TFLOP/s
@@ -59,6 +62,57 @@ def trace(msg):
 
 
 FP32_MFMA_PEAK_TFLOPS = 157.3      # MI355X dense fp32-input MFMA peak (/opt/skills/guides/MI355X_MICROARCH.md)
+DUMP_BUDGET_BYTES = 60 << 20       # --dump-outputs: all files together (headers aside)
+
+
+def _dump_allowance(sizes, budget):
+    """bytes each output may take: the smallest are written whole, what is left is shared equally by the larger ones"""
+    allow, left = [0] * len(sizes), budget
+    order = sorted(range(len(sizes)), key=lambda i: sizes[i])
+    for j, i in enumerate(order):
+        allow[i] = min(sizes[i], left // (len(sizes) - j))
+        left -= allow[i]
+    return allow
+
+
+def report_dump(out_dir, outputs):
+    for name, (shape, n) in dump_outputs(out_dir, outputs).items():
+        print("[bench] dumped %s %s: %s" % (name, list(shape), "whole" if n == int(torch.Size(shape).numel()) else "%d sampled elements" % n),
+              file=sys.stderr)
+
+
+def dump_outputs(out_dir, outputs, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: every tensor of `outputs` (a dict, or tensors nested in lists / tuples under it) as out_dir/<name>.npy.  Floating
+    outputs are written as float32 (float64 stays float64), integer and boolean ones as float64 (exact).  An output larger than its share
+    of `budget` is written as a sample: the flat elements at sorted, de-duplicated indices drawn from a generator seeded by the output's
+    name, so that two runs with the same arguments write the same elements.  -> {name: (shape, elements written)}"""
+    import zlib
+    import numpy as np
+    flat = []
+
+    def walk(name, v):
+        if isinstance(v, torch.Tensor):
+            flat.append((name, v.detach()))
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                walk("%s_%d" % (name, i), x)
+    for k in sorted(outputs):
+        walk(str(k), outputs[k])
+    os.makedirs(out_dir, exist_ok=True)
+    dtypes = [torch.float64 if (t.dtype == torch.float64 or not t.is_floating_point()) else torch.float32 for _, t in flat]
+    sizes = [t.numel() * (8 if d == torch.float64 else 4) for (_, t), d in zip(flat, dtypes)]
+    report = {}
+    for (name, t), d, allow in zip(flat, dtypes, _dump_allowance(sizes, budget)):
+        n, item = t.numel(), (8 if d == torch.float64 else 4)
+        v = t.reshape(-1)
+        if n * item > allow:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            idx = np.unique(rng.integers(0, n, allow // item, dtype=np.int64))
+            v = v[torch.from_numpy(idx).to(v.device)]
+        a = v.to(d).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a if v.numel() < n else a.reshape(tuple(t.shape)))
+        report[name] = (tuple(t.shape), int(a.size))
+    return report
 
 
 def parse(argv=None):
@@ -103,7 +157,20 @@ def parse(argv=None):
     ap.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 --pmc subprocess passes behind roofline.traffic")
     ap.add_argument("--dump-launches", action="store_true", help="print every library launch of one instrumented step to stderr "
                     "(name, live rows, executed GFLOP, us, TFLOP/s)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement after the timed steps: the variant loops (H2D-inclusive, latency mode, batches "
+                         "in flight, dedup off, saturated / lidar clouds, other arithmetics), the reference route, the instrumented "
+                         "roofline / per-kernel pass, the rocprofv3 traffic passes and the CPU baseline.  Without it a run only sets up, "
+                         "warms up, times the steps and prints the line; the --no-* switches still apply under --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, or float64 for "
+                         "integer outputs); at most %d MB in all: a larger output is written as a fixed, seeded sample of its elements"
+                         % (DUMP_BUDGET_BYTES >> 20))
     args = ap.parse_args(argv)
+    if not args.full:
+        args.no_variants = args.no_roofline = args.no_traffic = args.no_cpu_baseline = True
+    if args.dump_outputs and args.workload == "reference":
+        ap.error("--dump-outputs: the reference workload's outputs stay inside bench_reference.py")
     train = args.workload in ("train", "train-rcnn")
     if args.steps is None:
         args.steps = 20 if (train or args.workload == "reference") else 320
@@ -425,7 +492,7 @@ class InferenceBench:
         self.nstreams = max(1, args.streams)
         make_clouds = make_cloud_fn(clouds_kind)
         self.clouds_cpu = make_clouds(args.batch, args.npoints, seed0=shard_seed0(rank, world, 0, args.batch))
-        self.pipe, self.out, self.host, self.graphs = None, None, None, None
+        self.pipe, self.out, self.host, self.graphs, self.last_slot = None, None, None, None, None
         self._slot_clouds = lambda s_: (self.clouds_cpu if s_ == 0 else                                              # noqa: E731
                                         make_clouds(args.batch, args.npoints, seed0=shard_seed0(rank, world, s_, args.batch)))
         self._eager_inputs = None
@@ -541,8 +608,13 @@ class InferenceBench:
         if dist is not None:
             dist.barrier()
         elapsed = reduce_elapsed(time.perf_counter() - t0, dist, self.dev)
+        self.last_slot = (self.pipe._next_ticket - 1) % self.pipe.slots
         self.pipe.drain()
         return elapsed
+
+    def last_step_outputs(self):
+        """what the last step of the latest timed() returned: its slot's outputs (nothing has been submitted since)"""
+        return self.pipe.outputs[self.last_slot]
 
     def timed_single(self, steps, dist=None):
         """latency mode: ONE batch in flight -- submit, wait for its result, submit the next (what a tools/eval_rcnn.py-style loop
@@ -817,6 +889,8 @@ def run_train(args, dev, rank, world, local_rank, dist):
     # settle over the first handful of steps (three were not enough: 43 ms per step measured against 28.5 ms in steady state)
     timed_loop(max(1, args.warmup), prefetch)
     elapsed, loss = timed_loop(args.steps, prefetch)
+    if args.dump_outputs and rank == 0:
+        report_dump(args.dump_outputs, {"loss": loss})
     elapsed_other, _ = timed_loop(min(args.steps, 10), not prefetch)
     nparam = sum(p.numel() for p in model.parameters() if p.requires_grad)
     allreduce_ms = None
@@ -942,6 +1016,8 @@ def run_train_rcnn(args, dev, rank, world, local_rank, dist):
         return reduce_elapsed(time.perf_counter() - t0, dist, dev), loss_
     timed_loop(max(1, args.warmup))
     elapsed, loss = timed_loop(args.steps)
+    if args.dump_outputs and rank == 0:
+        report_dump(args.dump_outputs, {"loss": loss})
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
     trainer.model.train()
     trainer.optimizer.zero_grad(set_to_none=True)
@@ -1047,8 +1123,10 @@ def main():
     world, rank, local_rank, relaunch = resolve_world(args, os.environ, torch.cuda.device_count())
     if relaunch:
         cmd = self_launch_command(args.gpus, sys.argv[1:])
-        print("[bench] --gpus %d without a launcher environment: re-executing as %s" % (args.gpus, " ".join(cmd[:8]) + " ..."), file=sys.stderr)
-        os.execv(cmd[0], cmd)
+        print("[bench] --gpus %d without a launcher environment: re-executing in a child process as %s" % (args.gpus, " ".join(cmd[:8]) + " ..."),
+              file=sys.stderr, flush=True)
+        import subprocess
+        raise SystemExit(subprocess.call(cmd))
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
     dist = None
@@ -1142,6 +1220,8 @@ def main():
                   % (nstreams, free_b / 2 ** 30, total_b / 2 ** 30), file=sys.stderr, flush=True)
     elapsed = bench.timed(args.steps, args.warmup, dist, h2d=args.h2d)
     trace("timed loop done: %.3f ms/step" % (1e3 * elapsed / args.steps))
+    if args.dump_outputs and rank == 0:
+        report_dump(args.dump_outputs, bench.last_step_outputs())
     out, clouds_cpu, graph = bench.out, bench.clouds_cpu, bench.graphs
 
     line = {

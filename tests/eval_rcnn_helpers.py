@@ -9,9 +9,15 @@ the repo root -- the environment INTEGRATION.md section 1 describes.
                                                                  (the reference's own KittiRCNNDataset, same numpy seeds and loader
                                                                  settings as tools/eval_rcnn.py:459-470,856-871), one result file
                                                                  per frame
+    python eval_rcnn_helpers.py script <script.py> [args...]     run a reference script unchanged as __main__, as
+                                                                 `python <script.py> [args...]` would
     python eval_rcnn_helpers.py cpu-run <script.py> [args...]    build-container only (no GPU): run a reference script unchanged with
                                                                  `.cuda()` a no-op and the operators routed to the CPU oracle
+
+Every command first applies the environment adapters of tests/compat/usercustomize.py itself: `site` imports that module only
+while the user site directory is enabled, and the test suite runs with it disabled.
 """
+import importlib.util
 import logging
 import os
 import runpy
@@ -21,6 +27,12 @@ import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def _apply_compat_adapters():
+    """tests/compat/usercustomize.py by path (idempotent): the yaml.load / collections.Iterable adapters"""
+    spec = importlib.util.spec_from_file_location("prcnn_compat_adapters", os.path.join(HERE, "compat", "usercustomize.py"))
+    spec.loader.exec_module(importlib.util.module_from_spec(spec))
 
 
 def _reference_paths():
@@ -84,6 +96,12 @@ def mirror_eval(ckpt, out_dir, batch_size):
     print("mirror: %d frames, %d detections -> %s" % (len(ds), total, out_dir))
 
 
+def run_script(script, argv):
+    sys.argv = [script] + list(argv)
+    sys.path.insert(0, os.path.dirname(os.path.abspath(script)))
+    runpy.run_path(os.path.abspath(script), run_name="__main__")
+
+
 def cpu_run(script, argv):
     import cpu_ops
     assert not torch.cuda.is_available(), "cpu-run is the build container's route; on the GPU box run the script itself"
@@ -94,11 +112,14 @@ def cpu_run(script, argv):
 
 
 if __name__ == "__main__":
+    _apply_compat_adapters()
     cmd = sys.argv[1]
     if cmd == "ckpt":
         make_ckpt(sys.argv[2], sys.argv[3])
     elif cmd == "mirror":
         mirror_eval(sys.argv[2], sys.argv[3], sys.argv[4])
+    elif cmd == "script":
+        run_script(sys.argv[2], sys.argv[3:])
     elif cmd == "cpu-run":
         cpu_run(sys.argv[2], sys.argv[3:])
     else:

@@ -198,12 +198,14 @@ def make_net_golden():
     sd = model.state_dict()
     g = {"keys": np.array(sorted(sd)), "shapes": np.array([str(tuple(sd[k].shape)) for k in sorted(sd)]), "crc_in": crc(pts.numpy())}
     g["rpn_cls"] = out["rpn_cls"].numpy()[:, :, 0]
-    g["rpn_reg_s8"] = out["rpn_reg"].numpy()[:, ::8]
+    reg_s8 = out["rpn_reg"].numpy()[:, ::8]          # stored frame by frame in a file of its own (tests/util.py load_net_ref)
     g["rpn_reg_abs_sum"] = np.abs(out["rpn_reg"].numpy().astype(np.float64)).sum((1, 2))
     g["feat_s16"] = out["backbone_features"].numpy()[:, :, ::16]
     for k in ("rois", "roi_scores_raw", "seg_result", "rcnn_cls", "rcnn_reg"):
         g[k] = out[k].numpy()
     np.savez_compressed(os.path.join(HERE, "net_ref.npz"), **g)
+    for b in range(reg_s8.shape[0]):
+        np.savez_compressed(os.path.join(HERE, "net_ref_rpn_reg%d.npz" % b), rpn_reg_s8=reg_s8[b])
     print("net_ref: rois filled", (np.abs(g["rois"]).sum(-1) > 0).sum(1).tolist())
 
 

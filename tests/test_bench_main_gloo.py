@@ -39,7 +39,7 @@ def test_main_under_torch_distributed_run(workload):
     steps = 4
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), HARNESS, "--gpus", "2", "--steps", str(steps), "--warmup", "1", "--workload", workload,
-           "--no-roofline", "--no-cpu-baseline"]
+           "--no-roofline", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=_env())
     assert r.returncode == 0, r.stderr[-2000:]
     lines = _json_lines(r.stdout)
@@ -78,7 +78,7 @@ def test_inference_pipeline_bookkeeping_under_torch_distributed_run():
     steps = 7
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), HARNESS, "--gpus", "2", "--steps", str(steps), "--warmup", "2", "--batch", "4", "--npoints", "256",
-           "--streams", "3", "--proposals", "off", "--graph", "off", "--no-roofline", "--no-cpu-baseline"]
+           "--streams", "3", "--proposals", "off", "--graph", "off", "--no-roofline", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=dict(_env(), PRCNN_HARNESS_REAL_PIPELINE="1", PRCNN_BENCH_NO_SPLIT="1"))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _json_lines(r.stdout)
@@ -88,3 +88,49 @@ def test_inference_pipeline_bookkeeping_under_torch_distributed_run():
     assert line["ms_per_step"] >= 5.5                                  # rank 1: 6 ms per step
     assert abs(line["value"] - 4 * 2 * 1e3 / line["ms_per_step"]) <= 0.01 * line["value"]
     assert line["value_h2d_inclusive"] > 0 and line["value_latency_mode"] > 0
+
+
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """without --full the line holds the timed loop only (no variant loops); --dump-outputs writes what the last timed step returned
+    (the REAL InferenceBench + InferencePipeline on device "cpu" around the harness's toy model), identically from run to run"""
+    import numpy as np
+    steps, lines = 5, []
+    for d in ("a", "b"):
+        cmd = [sys.executable, HARNESS, "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--batch", "2", "--npoints", "64",
+               "--streams", "2", "--proposals", "off", "--graph", "off", "--dump-outputs", str(tmp_path / d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=dict(_env(), PRCNN_HARNESS_REAL_PIPELINE="1"))
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines += _json_lines(r.stdout)
+    assert len(lines) == 2
+    for line in lines:
+        assert line["steps"] == steps and line["ms_per_step"] > 0 and line["unit"] == "frames/s" and line["higher_is_better"] is True
+        assert not any(k in line for k in ("value_h2d_inclusive", "value_latency_mode", "roofline", "cpu_baseline", "arithmetics"))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["backbone_features.npy", "backbone_xyz.npy", "rpn_cls.npy", "rpn_reg.npy"]
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and a.size > 0 and np.array_equal(a, b)
+    # the toy model's rpn_cls is 0.5 x the sum of each point's coordinates: the dump holds the batch of the LAST step's slot
+    import bench
+    from pointrcnn_amd import rpn
+    slot = (1 + steps - 1) % 2          # tickets run on from the warm-up: timed step k runs on slot (warmup + k) % streams
+    clouds = rpn.synthetic_clouds(2, 64, seed0=bench.shard_seed0(0, 1, slot, 2))
+    assert np.allclose(np.load(tmp_path / "a" / "rpn_cls.npy"), clouds.sum(2, keepdim=True).numpy() * 0.5)
+
+
+def test_dump_outputs_samples_what_exceeds_the_budget(tmp_path):
+    """bench.dump_outputs: small outputs whole, larger ones a seeded sample within the byte budget; integers as float64"""
+    import numpy as np
+    import torch
+    import bench
+    outs = {"big": torch.arange(100000, dtype=torch.float32).reshape(100, 1000), "small": torch.ones(3, 2, dtype=torch.float16),
+            "keep": torch.tensor([3, -1, 7], dtype=torch.int32), "pair": (torch.zeros(2), torch.ones(1, dtype=torch.float64))}
+    rep = bench.dump_outputs(str(tmp_path / "a"), outs, budget=40000)
+    bench.dump_outputs(str(tmp_path / "b"), outs, budget=40000)
+    assert sorted(os.listdir(tmp_path / "a")) == ["big.npy", "keep.npy", "pair_0.npy", "pair_1.npy", "small.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) - 128 for f in os.listdir(tmp_path / "a")) <= 40000
+    small, keep = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "keep.npy")
+    assert small.dtype == np.float32 and small.shape == (3, 2) and keep.dtype == np.float64 and keep.tolist() == [3, -1, 7]
+    big = np.load(tmp_path / "a" / "big.npy")
+    assert big.ndim == 1 and 0 < big.size < 100000 and rep["big"] == ((100, 1000), big.size)
+    assert np.all(np.diff(big) > 0) and np.array_equal(big, np.load(tmp_path / "b" / "big.npy"))     # sorted distinct elements, same sample

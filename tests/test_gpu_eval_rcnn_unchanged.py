@@ -95,9 +95,10 @@ def test_reference_eval_rcnn_script_runs_unchanged_end_to_end(dev, mlp_mode, tmp
     assert _ground_truth_from(mirror_dir, training, P2) >= 2 * len(FRAMES)
 
     # pass 2: the reference's script, unchanged (README.md:84-87 with the synthetic tree's checkpoint; --workers 0 keeps the numpy
-    # draw of the 16384 points in the main process, where the script's own np.random.seed(666) fixes it)
+    # draw of the 16384 points in the main process, where the script's own np.random.seed(666) fixes it), run as __main__ by the
+    # helper, which applies the compat adapters first (`site` skips usercustomize while the user site directory is disabled)
     out_dir = os.path.join(where, "output", "e2e")
-    _run([sys.executable, "eval_rcnn.py", "--cfg_file", "cfgs/default.yaml", "--ckpt", ckpt, "--batch_size", "4", "--eval_mode", "rcnn",
+    _run([sys.executable, helpers, "script", "eval_rcnn.py", "--cfg_file", "cfgs/default.yaml", "--ckpt", ckpt, "--batch_size", "4", "--eval_mode", "rcnn",
           "--workers", "0", "--output_dir", out_dir], tools, env, str(tmp_path / "eval_rcnn.log"))
     with open(os.path.join(tools, "eval_rcnn.py"), "rb") as fh:
         assert fh.read() == script_bytes

@@ -22,7 +22,7 @@ import numpy as np
 import pytest
 import torch
 
-from util import GOLDEN
+from util import GOLDEN, load_net_ref
 
 sys.path.insert(0, GOLDEN)
 
@@ -72,7 +72,7 @@ def test_unchanged_reference_point_rcnn_on_hip_kernels(dev, refnet):
     from pointrcnn_amd import rpn
     from pointrcnn_amd.point_rcnn import PointRCNN as Mirror
     import cpu_ops
-    g = np.load(os.path.join(GOLDEN, "net_ref.npz"))
+    g = load_net_ref()
     c = NET_CASE
     model = refnet.build_reference_model("TEST", seed=c["wseed"])       # the reference's class, parameters by state-dict name
     sd = model.state_dict()

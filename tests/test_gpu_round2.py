@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 import torch
 
-from util import GOLDEN, enlarge, kitti_cloud, mlp_tol, rand_boxes3d
+from util import GOLDEN, enlarge, kitti_cloud, load_net_ref, mlp_tol, rand_boxes3d
 
 sys.path.insert(0, GOLDEN)
 
@@ -101,7 +101,7 @@ def test_two_stage_mirror_matches_reference_lib_net_golden(dev):
     from make_golden import NET_CASE, crc
     from pointrcnn_amd import rpn
     from pointrcnn_amd.point_rcnn import PointRCNN
-    g = np.load(os.path.join(GOLDEN, "net_ref.npz"))
+    g = load_net_ref()
     c = NET_CASE
     model = PointRCNN(mode="TEST")
     sd = model.state_dict()

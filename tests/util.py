@@ -4,6 +4,15 @@ import numpy as np
 GOLDEN = __import__("os").path.join(__import__("os").path.dirname(__import__("os").path.abspath(__file__)), "golden")
 
 
+def load_net_ref():
+    """tests/golden/net_ref.npz as one dict: its rpn_reg_s8 is stored frame by frame in net_ref_rpn_reg<frame>.npz (every fixture
+    file stays under 1 MiB)"""
+    import os
+    g = dict(np.load(os.path.join(GOLDEN, "net_ref.npz")))
+    g["rpn_reg_s8"] = np.stack([np.load(os.path.join(GOLDEN, "net_ref_rpn_reg%d.npz" % b))["rpn_reg_s8"] for b in range(g["rpn_cls"].shape[0])])
+    return g
+
+
 def unit_cloud(B, N, seed=0):
     return np.random.default_rng(seed).random((B, N, 3), dtype=np.float32)
 

@@ -14,19 +14,19 @@ rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_INSTS_VALU_MFMA_MO
 python profiles/derive_hbm_traffic.py $O/pmc_ $O/hbm_traffic.json > $O/hbm_traffic.txt 2>&1
 cp $O/hbm_traffic.json profiles/r06_hbm_traffic.json
 python profiles/derive_mfma_util.py $O/pmc_mfma > $O/mfma_util.txt 2>&1
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-python bench.py --steps 20 --warmup 5 > $O/bench_driver_flags.json 2>> $O/bench_default.err
-python bench.py --streams 1 --no-cpu-baseline --no-variants > $O/bench_streams1.json 2>> $O/bench_default.err
-python bench.py --input raw --no-variants > $O/bench_raw_input.json 2>> $O/bench_default.err
-python bench.py --workload rcnn > $O/bench_rcnn.json 2>> $O/bench_default.err
-PRCNN_MLP_SPLIT=0 python bench.py --workload rcnn --no-cpu-baseline > $O/bench_rcnn_f32_mfma.json 2>> $O/bench_default.err
-python bench.py --workload train > $O/bench_train.json 2>> $O/bench_default.err
-python bench.py --workload train-rcnn > $O/bench_train_rcnn.json 2>> $O/bench_default.err
-python bench.py --npoints 65536 --batch 8 --steps 64 --no-variants > $O/bench_config5_rpn.json 2>> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_flags.json 2>> $O/bench_default.err
+python bench.py --full --streams 1 --no-cpu-baseline --no-variants > $O/bench_streams1.json 2>> $O/bench_default.err
+python bench.py --full --input raw --no-variants > $O/bench_raw_input.json 2>> $O/bench_default.err
+python bench.py --full --workload rcnn > $O/bench_rcnn.json 2>> $O/bench_default.err
+PRCNN_MLP_SPLIT=0 python bench.py --full --workload rcnn --no-cpu-baseline > $O/bench_rcnn_f32_mfma.json 2>> $O/bench_default.err
+python bench.py --full --workload train > $O/bench_train.json 2>> $O/bench_default.err
+python bench.py --full --workload train-rcnn > $O/bench_train_rcnn.json 2>> $O/bench_default.err
+python bench.py --full --npoints 65536 --batch 8 --steps 64 --no-variants > $O/bench_config5_rpn.json 2>> $O/bench_default.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt3 -- python bench.py --no-cpu-baseline --no-roofline --no-variants > /dev/null 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt1 -- python bench.py --no-cpu-baseline --no-roofline --no-variants --streams 1 > /dev/null 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/ktt -- python bench.py --workload train --steps 16 > /dev/null 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/ktr -- python bench.py --workload train-rcnn --steps 16 > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/ktt -- python bench.py --full --workload train --steps 16 > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/ktr -- python bench.py --full --workload train-rcnn --steps 16 > /dev/null 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ktc -- python bench.py --workload rcnn --steps 160 --no-cpu-baseline --no-roofline > /dev/null 2>&1
 python profiles/summarize_rocprof.py $O/ktc "python bench.py --workload rcnn --steps 160 (config 3: two-stage detector, 10 batches in flight, hipGraph replay)" > $O/kernel_stats_rcnn.txt
 PRCNN_MLP_SPLIT=0 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kts -- python bench.py --no-cpu-baseline --no-roofline --no-variants > /dev/null 2>&1
