@@ -56,7 +56,8 @@ typedef void* prcnn_stream_t; /* hipStream_t */
 #define PRCNN_EHIP (-2)         /* HIP runtime / launch failure */
 #define PRCNN_EUNSUPPORTED (-3) /* valid request this build has no kernel for */
 
-int prcnn_abi_version(void);   /* 9: + prcnn_fps_mode, prcnn_ball_query_arith, prcnn_three_nn_arith (comparison mode: the squared distance as nvcc contracts the
+int prcnn_abi_version(void);   /* 10: + prcnn_corner_iou3d, prcnn_gt_aug_sample (GT-augmentation sampling loop on the device);
+                                 * 9: + prcnn_fps_mode, prcnn_ball_query_arith, prcnn_three_nn_arith (comparison mode: the squared distance as nvcc contracts the
                                  * upstream expression); prcnn_nms_workspace_bytes grew by one flag byte per 64 x 64 tile; 8: + prcnn_mlp_group_split;
                                  * 7: split-bf16 chain entry points take the fp32 pack images too (fp32 recomputation of rows with non-finite values); 6: + prcnn_fps_status, training-mode SharedMLP (prcnn_train_*), prcnn_boxes_iou3d, prcnn_proposal_target_sample, prcnn_ref_trig (box trigonometry = the reference's host libm, bit for bit); 5: + prcnn_gt_aug_edit;
                                  * 4: + prcnn_host_* (host twins of the reference's *_cpu entry points), prcnn_build_id,
@@ -345,11 +346,42 @@ int prcnn_rpn_labels(const float* pts, const float* gt_boxes3d, const int32_t* n
  * num_new: (B) i32 live counts or NULL (all rows live).  Output: out_pts (B,N+P,3), out_intensity (B,N+P) or NULL: the scene
  * points outside every box IN THEIR ORIGINAL ORDER, then the new points; rows >= out_count[b] are zero.  out_count (B) i32;
  * removed (B,N) i32 or NULL: 1 where a scene point was dropped (the complement of the reference's src_pts_flag).
- * In-box test == prcnn_pts_in_boxes3d.  The sampling loop (database lookup, road plane, collision test) stays with the caller. */
+ * In-box test == prcnn_pts_in_boxes3d.  The sampling loop that decides which objects are pasted and where is prcnn_gt_aug_sample. */
 int prcnn_gt_aug_edit(const float* pts, const float* intensity, const int32_t* num_pts, const float* boxes3d,
                       const int32_t* num_boxes, float extra_h, const float* new_pts, const float* new_intensity,
                       const int32_t* num_new, int B, int N, int K, int P, float* out_pts, float* out_intensity,
                       int32_t* out_count, int32_t* removed, prcnn_stream_t stream);
+
+/* kitti_utils.get_iou3d (lib/utils/kitti_utils.py:195-235) on corner sets: corners_a (N,8,3), corners_b (M,8,3) in rect coords
+ * (kitti_utils.boxes3d_to_corners3d order) -> iou3d (N,M), iou_bev (N,M) or NULL (the need_bev=True branch).  Heights in fp32 from
+ * the corners as numpy forms them (min_h = -(sum of y over corners 0:4, left to right) / 4, max_h over 4:8); a pair with no height
+ * overlap is 0.  The bottom quads (corners 0:4 in (x, z)) are clipped against each other in DOUBLE (exact convex clip, in place of
+ * shapely's intersection) and the ratios are formed in double and stored as fp32.  A quad that is not strictly convex (degenerate,
+ * self-intersecting) gives 0, as the reference's is_valid branch does.  Can differ from shapely only when an IoU is within
+ * rounding of a decision threshold, i.e. for boxes that touch.  csrc/quad_clip.h. */
+int prcnn_corner_iou3d(const float* corners_a, int N, const float* corners_b, int M, float* iou3d, float* iou_bev, prcnn_stream_t stream);
+
+/* The sampling loop of KittiRCNNDataset.apply_gt_aug_to_one_scene (lib/datasets/kitti_rcnn_dataset.py:414-497) and the
+ * apply-probability draw before it (:279), for a whole batch in one launch, one workgroup per frame, no host round trip.
+ *   gt_boxes3d (B,G,7) the frame's non-DontCare labels [x,y(bottom),z,h,w,l,ry] (filtrate_dc_objects), num_gt (B) i32 or NULL;
+ *   planes (B,4) f64 device: road plane a b c d, normal facing up and unit length (kitti_dataset.get_road_plane);
+ *   db_boxes (D,7), db_alpha (D), db_npts (D) i32: the packed GT database; easy_idx (E) / hard_idx (H) i32: database ids of the
+ *   easy (> 100 points) and hard lists, used when GT_AUG_HARD_RATIO > 0 (otherwise the draw is over all D entries);
+ *   cfg4: four DOUBLES in HOST memory: GT_EXTRA_NUM, GT_AUG_RAND_NUM (0/1), GT_AUG_APPLY_PROB, GT_AUG_HARD_RATIO;
+ *   scope: six doubles in HOST memory = PC_AREA_SCOPE (check_pc_range on the database centre) or NULL (PC_REDUCE_BY_RANGE false);
+ *   try_times = 100 in the reference; K = bound on accepted objects per frame (1..64, G + K <= 256).
+ * Per try: easy/hard draw, index draw, range check (skipped, not counted), < 5 points (skipped, not counted), the move onto the
+ * road plane in double (new y rounded to fp32), w and l + 0.5, cnt += 1, collision test of the enlarged box against the list
+ * (accepted iff every iou3d < 1e-8, prcnn_corner_iou3d arithmetic).  The list starts as the scene boxes with w, l + 0.5; every
+ * accepted enlarged box is appended.  The loop ends when cnt > extra_gt_num or the tries run out: cnt counts tries that reached
+ * the collision test, not accepted objects.
+ * Output: count (B) i32; db_id (B,K) i32 (-1 past count), boxes3d (B,K,7) the placed UNENLARGED boxes, alpha (B,K), y_shift (B,K)
+ * f64 = move_height (a pasted point's y becomes fp32(double(y) - y_shift)); stats (B,4) i32 = applied, extra_gt_num, cnt, tries
+ * started; status (B): 0 ok, 1 = the reference raises for this frame (randint on an empty list or with GT_EXTRA_NUM <= 10, max of
+ * an empty IoU array), 2 = more than K objects would be accepted (the first K are returned), 3 = an easy / hard list entry is
+ * not a database id in [0, D) (the loop stops there).
+ * Random calls: the counter-based table of csrc/train_input.hip (streams 30-33). */
+int prcnn_gt_aug_sample(const float* gt_boxes3d, const int32_t* num_gt, const double* planes, int B, int G, const float* db_boxes, const float* db_alpha, const int32_t* db_npts, int D, const int32_t* easy_idx, int E, const int32_t* hard_idx, int H, const double* cfg4, const double* scope, int try_times, int K, uint32_t seed, int32_t* count, int32_t* db_id, float* boxes3d, float* alpha, double* y_shift, int32_t* stats, int32_t* status, prcnn_stream_t stream);
 
 /* HOST twins of the reference's two CPU entry points (roipool3d.cpp:97-125 pts_in_boxes3d_cpu, :127-195 roipool3d_cpu),
  * which its dataloader calls inside forked worker processes (kitti_rcnn_dataset.py:487,582,625,843,970).  Host pointers,

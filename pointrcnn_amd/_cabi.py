@@ -36,7 +36,7 @@ class TrainLayer(ctypes.Structure):
                 ("dW", _P), ("dgamma", _P), ("dbeta", _P)]
 
 
-REQUIRED_ABI = 9                 # prcnn_abi_version() the signatures below describe
+REQUIRED_ABI = 10                # prcnn_abi_version() the signatures below describe
 
 # name -> (restype, argtypes); mirrors include/prcnn_pointops.h one for one
 SIGNATURES = {
@@ -51,6 +51,9 @@ SIGNATURES = {
     "prcnn_three_nn_arith": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "prcnn_rpn_labels": (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _P, _P]),
     "prcnn_gt_aug_edit": (_I, [_P, _P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "prcnn_corner_iou3d": (_I, [_P, _I, _P, _I, _P, _P, _P]),
+    "prcnn_gt_aug_sample": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _P, _I, _I, ctypes.c_uint32,
+                                 _P, _P, _P, _P, _P, _P, _P, _P]),
     "prcnn_host_pts_in_boxes3d": (_I, [_P, _P, _L, _L, _P]),
     "prcnn_host_roipool3d": (_I, [_P, _P, _P, _L, _L, _L, _L, _P, _P, _P]),
     "prcnn_gather": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),

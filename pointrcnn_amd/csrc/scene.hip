@@ -20,6 +20,14 @@
 //   r(stream, frame, i) = mix(i ^ mix(frame * 0x9E3779B9 + mix(seed + stream * 0x85EBCA6B))),  mix = the 32-bit finaliser below;
 //   "draw k of a candidate set without replacement" = the k candidates with the smallest (r(0,.) >> 2, raw index);
 //   "shuffle" = ascending order of (r(1,.), raw index) (top-up copies use r(2,.)).
+// Stream ids in use (each reference random call has a fixed (stream, frame, position); counter_rand.h is the generator):
+//   0-2    this file (draw, shuffle, top-up shuffle; position = raw index)
+//   10-13, 20   proposal_target.hip (RoI sampling and noise)
+//   30     train_input.hip: get_rpn_sample's np.random.rand() < GT_AUG_APPLY_PROB (kitti_rcnn_dataset.py:279), position 0 -- u01(r)
+//   31     train_input.hip: randint(10, GT_EXTRA_NUM) (:419), position 0 -- 10 + below(r, GT_EXTRA_NUM - 10)
+//   32     train_input.hip: per try t, the easy / hard rand() (:437), position t -- u01(r)
+//   33     train_input.hip: per try t, randint(0, len(list)) (:441-448), position t -- below(r, len)
+//   with u01(r) = fp32(r >> 8) * 2^-24 widened to double, below(r, n) = (r * n) >> 32.
 // Both are exact uniform draws / permutations when r is uniform; the selected SET and the output ORDER depend only on
 // (seed, frame, raw index), never on the order in which the kernels' atomics append.
 //
@@ -29,6 +37,7 @@
 //                         (LDS histograms), ties by raw index, selected entries appended to LDS, sorted by their shuffle
 //                         key with the shared bitonic sort (lds_sort.h), rows recomputed and written in that order.
 #include "lds_sort.h"
+#include "counter_rand.h"
 
 constexpr int SCENE_THREADS = 1024;
 constexpr int SCENE_MAX_TIES = 1024;
@@ -52,13 +61,6 @@ struct SceneParams {
     int32_t* status;            // (B) 0 ok, 1 outside the reference's domain (it raises), 2 no valid point
 };
 
-__host__ __device__ __forceinline__ unsigned scene_mix(unsigned x) {
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-    return x;
-}
-__host__ __device__ __forceinline__ unsigned scene_rand(unsigned seed, unsigned stream, unsigned frame, unsigned i) {
-    return scene_mix(i ^ scene_mix(frame * 0x9E3779B9U + scene_mix(seed + stream * 0x85EBCA6BU)));
-}
 
 struct RectPoint { float x, y, z; bool valid; };
 

@@ -132,3 +132,70 @@ def gt_aug_edit_scene(pts_rect, pts_intensity, accepted_boxes3d, new_pts_list, n
                                               torch.as_tensor(new_int, device=device)[None])
     n = int(count[0])
     return out_pts[0, :n].cpu().numpy(), out_int[0, :n].cpu().numpy()
+
+
+class GTDatabase:
+    """The GT database of the reference's GT augmentation (generate_gt_database.py:78-84, kitti_rcnn_dataset.py:62-76), packed once
+    into device tensors: boxes (D,7), alpha (D,), npts (D,) i32, point offsets (D+1,) i64, points (P,3), intensity (P,); and the
+    easy (> 100 points) / hard id lists of GT_AUG_HARD_RATIO > 0 (in database order, as the reference builds its two lists)."""
+
+    def __init__(self, boxes, alpha, points, intensity, hard_ratio=0.6, device="cuda"):
+        boxes = np.ascontiguousarray(boxes, np.float32).reshape(-1, 7)
+        D = boxes.shape[0]
+        if len(points) != D or len(intensity) != D or np.asarray(alpha).reshape(-1).shape[0] != D:
+            raise ValueError("GTDatabase: boxes, alpha, points and intensity must describe the same %d objects" % D)
+        npts = np.array([np.asarray(p).reshape(-1, 3).shape[0] for p in points], np.int32)
+        off = np.zeros(D + 1, np.int64)
+        np.cumsum(npts, out=off[1:])
+        pts = np.concatenate([np.asarray(p, np.float32).reshape(-1, 3) for p in points]) if D else np.zeros((0, 3), np.float32)
+        inten = np.concatenate([np.asarray(v, np.float32).reshape(-1) for v in intensity]) if D else np.zeros((0,), np.float32)
+        if inten.shape[0] != pts.shape[0]:
+            raise ValueError("GTDatabase: every object needs one intensity per point")
+        self.hard_ratio = float(hard_ratio)
+        easy = np.nonzero(npts > 100)[0].astype(np.int32)
+        hard = np.nonzero(npts <= 100)[0].astype(np.int32)
+        # the reference raises (np.random.randint on an empty range) when it draws from an empty list
+        if self.hard_ratio > 0:
+            if len(hard) == 0:
+                raise ValueError("GTDatabase: the hard list (<= 100 points) is empty but GT_AUG_HARD_RATIO > 0 draws from it")
+            if len(easy) == 0 and self.hard_ratio < 1.0:
+                raise ValueError("GTDatabase: the easy list (> 100 points) is empty but GT_AUG_HARD_RATIO < 1 draws from it")
+        elif D == 0:
+            raise ValueError("GTDatabase: empty database")
+        dev = torch.device(device)
+        T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
+        self.size = D
+        self.max_points = int(npts.max()) if D else 0
+        self.boxes, self.alpha, self.npts = T(boxes), T(np.asarray(alpha, np.float32).reshape(-1)), T(npts)
+        self.offsets, self.points, self.intensity = T(off), T(pts), T(inten)
+        self.easy_idx, self.hard_idx = T(easy), T(hard)
+
+    @classmethod
+    def from_arrays(cls, boxes, alpha, points, intensity, hard_ratio=0.6, device="cuda"):
+        return cls(boxes, alpha, points, intensity, hard_ratio, device)
+
+    @classmethod
+    def from_pickle(cls, path, hard_ratio=0.6, device="cuda"):
+        """the reference's *_gt_database_3level_*.pkl: a list of dicts with gt_box3d, points, intensity, obj (its Object3d class
+        must be importable by the caller's environment for the unpickling)"""
+        import pickle
+        with open(path, "rb") as f:
+            db = pickle.load(f)
+        return cls([d["gt_box3d"] for d in db], [d["obj"].alpha for d in db], [d["points"] for d in db],
+                   [d["intensity"] for d in db], hard_ratio, device)
+
+    def sample(self, gt_boxes3d, num_gt, planes, extra_num=15, rand_num=True, apply_prob=1.0, area_scope=PC_AREA_SCOPE,
+               try_times=100, max_accept=16, seed=0):
+        """prcnn_gt_aug_sample against this database: gt_boxes3d (B,G,7) + num_gt (B) i32 (non-DontCare labels), planes (B,4) f64,
+        all on the device.  area_scope = cfg.PC_AREA_SCOPE or None (PC_REDUCE_BY_RANGE false).  -> ops.gt_aug_sample's dict."""
+        scope = None if area_scope is None else [float(v) for ax in area_scope for v in ax]
+        return ops.gt_aug_sample(gt_boxes3d, num_gt, planes, self.boxes, self.alpha, self.npts, self.easy_idx, self.hard_idx,
+                                 extra_num, rand_num, apply_prob, self.hard_ratio, scope, try_times, max_accept, seed)
+
+
+def road_plane_from_lines(lines):
+    """kitti_dataset.get_road_plane (lib/datasets/kitti_dataset.py:55-68) on the plane file's lines: normal facing up, unit length"""
+    plane = np.asarray([float(v) for v in lines[3].split()])
+    if plane[1] > 0:
+        plane = -plane
+    return plane / np.linalg.norm(plane[0:3])

@@ -140,6 +140,26 @@ def main():
     emit("gt_aug_edit", "B%d N%d K15 P4000" % (B, N), timeit(lambda: ops.gt_aug_edit(xyz, inten, ab, npts, nint)),
          bytes=B * (2 * N * 16 + 2 * 4000 * 16))
 
+    # ---- GT-augmentation sampling (kitti_rcnn_dataset.py:414-497): corner IoU pairs, and the whole sampling loop at B = 16
+    from . import kitti_input
+    gq = torch.Generator().manual_seed(11)
+    cb = torch.rand(256, 7, generator=gq) * torch.tensor([60., 1., 60., 1., 1., 3., 6.28]) + torch.tensor([-30., 1., 5., 1., 1., 2., -3.14])
+    hw, hl, c, s_ = cb[:, 4:5] / 2, cb[:, 5:6] / 2, torch.cos(cb[:, 6:7]), torch.sin(cb[:, 6:7])
+    lx = torch.cat([hl, hl, -hl, -hl] * 2, 1); lz = torch.cat([hw, -hw, -hw, hw] * 2, 1)
+    ly = torch.cat([torch.zeros(256, 4), -cb[:, 3:4].expand(-1, 4)], 1)
+    corners = torch.stack([cb[:, 0:1] + lx * c + lz * s_, cb[:, 1:2] + ly, cb[:, 2:3] - lx * s_ + lz * c], 2).to(dev).contiguous()
+    emit("corner_iou3d", "256 x 256 pairs", timeit(lambda: ops.corner_iou3d(corners, corners)), pairs=256 * 256)
+    Bs, D = 16, 2000
+    dbb = (torch.rand(D, 7, generator=gq) * torch.tensor([60., .8, 60., .3, .3, 1., 6.28]) + torch.tensor([-30., 1.2, 5., 1.4, 1.5, 3.4, -3.14]))
+    npd = torch.randint(5, 400, (D,), generator=gq)
+    gdb = kitti_input.GTDatabase.from_arrays(dbb.numpy(), torch.zeros(D).numpy(), [torch.zeros(int(n), 3).numpy() for n in npd],
+                                             [torch.zeros(int(n)).numpy() for n in npd], device=dev)
+    sg = (torch.rand(Bs, 12, 7, generator=gq) * torch.tensor([60., .8, 60., .3, .3, 1., 6.28]) + torch.tensor([-30., 1.2, 5., 1.4, 1.5, 3.4, -3.14])).to(dev)
+    ngt = torch.full((Bs,), 12, dtype=torch.int32, device=dev)
+    planes = torch.tensor([[0.0, -1.0, 0.0, 1.65]] * Bs, dtype=torch.float64, device=dev)
+    emit("gt_aug_sample", "B%d G12 D%d (default.yaml: 10-14 extra, 100 tries)" % (Bs, D),
+         timeit(lambda: gdb.sample(sg, ngt, planes, seed=5)))
+
     # ---- NMS (default RPN path: normal, 6300 boxes, thr 0.8) and rotated
     c = torch.rand(6300, 2, generator=g) * torch.tensor([80.0, 70.0])
     s = torch.rand(6300, 2, generator=g) * torch.tensor([0.5, 1.5]) + torch.tensor([0.8, 1.7])

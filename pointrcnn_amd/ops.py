@@ -650,6 +650,68 @@ def gt_aug_edit(pts, intensity, boxes3d, new_pts, new_intensity, num_pts=None, n
     return (out_pts, out_int, count, removed) if want_removed else (out_pts, out_int, count)
 
 
+def corner_iou3d(corners_a, corners_b, need_bev=False):
+    """kitti_utils.get_iou3d (lib/utils/kitti_utils.py:195-235): corners_a (N,8,3), corners_b (M,8,3) -> iou3d (N,M)
+    [, iou_bev (N,M) when need_bev].  Exact double clip of the bottom quads in place of shapely (csrc/quad_clip.h)."""
+    _chk(corners_a, "corners_a", ndim=3); _chk(corners_b, "corners_b", ndim=3)
+    if tuple(corners_a.shape[1:]) != (8, 3) or tuple(corners_b.shape[1:]) != (8, 3):
+        raise ValueError("corner_iou3d: corners must be (N, 8, 3) and (M, 8, 3)")
+    N, M = corners_a.shape[0], corners_b.shape[0]
+    iou3d = torch.empty((N, M), dtype=_F32, device=corners_a.device)
+    bev = torch.empty((N, M), dtype=_F32, device=corners_a.device) if need_bev else None
+    _cabi.check(_cabi.lib().prcnn_corner_iou3d(_p(corners_a), N, _p(corners_b), M, _p(iou3d), _p(bev), _stream()), "prcnn_corner_iou3d")
+    return (iou3d, bev) if need_bev else iou3d
+
+
+def gt_aug_sample(gt_boxes3d, num_gt, planes, db_boxes, db_alpha, db_npts, easy_idx, hard_idx, extra_num=15, rand_num=True,
+                  apply_prob=1.0, hard_ratio=0.6, area_scope=None, try_times=100, max_accept=16, seed=0):
+    """The sampling loop of KittiRCNNDataset.apply_gt_aug_to_one_scene (kitti_rcnn_dataset.py:414-497) for a batch, one launch.
+    gt_boxes3d (B,G,7) non-DontCare labels, num_gt (B) i32 or None, planes (B,4) f64 road planes; db_boxes (D,7), db_alpha (D),
+    db_npts (D) i32, easy_idx (E) / hard_idx (H) i32 database ids (used when hard_ratio > 0); area_scope = 6 floats or None.
+    -> dict: count (B) i32, db_id (B,K) i32, boxes3d (B,K,7) placed boxes, alpha (B,K), y_shift (B,K) f64, stats (B,4) i32
+    (applied, extra_gt_num, counted tries, tries started), status (B) i32: 0 ok, 1 the reference raises, 2 more than max_accept
+    accepted, 3 an easy / hard entry outside [0, D) (include/prcnn_pointops.h)"""
+    _chk(gt_boxes3d, "gt_boxes3d", ndim=3); _chk(planes, "planes", torch.float64, 2)
+    _chk(db_boxes, "db_boxes", ndim=2); _chk(db_alpha, "db_alpha", ndim=1); _chk(db_npts, "db_npts", _INT, 1)
+    B, G, C = gt_boxes3d.shape
+    D = db_boxes.shape[0]
+    if C != 7 or tuple(planes.shape) != (B, 4):
+        raise ValueError("gt_aug_sample: gt_boxes3d must be (B, G, 7), planes (B, 4)")
+    if db_boxes.shape[1] != 7 or db_alpha.shape[0] != D or db_npts.shape[0] != D:
+        raise ValueError("gt_aug_sample: db_boxes (D, 7), db_alpha (D,), db_npts (D,) disagree")
+    if num_gt is not None:
+        _chk(num_gt, "num_gt", _INT, 1)
+        if num_gt.shape[0] != B:
+            raise ValueError("gt_aug_sample: num_gt must be (%d,)" % B)
+    for name, t in (("easy_idx", easy_idx), ("hard_idx", hard_idx)):
+        if t is not None:
+            _chk(t, name, _INT, 1)
+    if hard_ratio > 0 and (easy_idx is None or hard_idx is None):
+        raise ValueError("gt_aug_sample: hard_ratio > 0 needs the easy and hard lists")
+    dev = gt_boxes3d.device
+    for name, t in (("num_gt", num_gt), ("planes", planes), ("db_boxes", db_boxes), ("db_alpha", db_alpha), ("db_npts", db_npts),
+                    ("easy_idx", easy_idx), ("hard_idx", hard_idx)):
+        if t is not None and t.device != dev:
+            raise RuntimeError("gt_aug_sample: %s is on %s, gt_boxes3d on %s" % (name, t.device, dev))
+    # ids outside [0, D) in the easy / hard lists are caught by the kernel (status 3) without a host read of the lists
+    if not 1 <= max_accept <= 64 or G + max_accept > 256:
+        raise ValueError("gt_aug_sample: max_accept must be 1..64 with G + max_accept <= 256 (G=%d)" % G)
+    K = int(max_accept)
+    out = {"count": torch.empty((B,), dtype=_INT, device=dev), "db_id": torch.empty((B, K), dtype=_INT, device=dev),
+           "boxes3d": torch.empty((B, K, 7), dtype=_F32, device=dev), "alpha": torch.empty((B, K), dtype=_F32, device=dev),
+           "y_shift": torch.empty((B, K), dtype=torch.float64, device=dev), "stats": torch.empty((B, 4), dtype=_INT, device=dev),
+           "status": torch.empty((B,), dtype=_INT, device=dev)}
+    cfg4 = (ctypes.c_double * 4)(float(extra_num), 1.0 if rand_num else 0.0, float(apply_prob), float(hard_ratio))
+    scope = None if area_scope is None else (ctypes.c_double * 6)(*[float(v) for v in area_scope])
+    E = 0 if easy_idx is None else easy_idx.shape[0]
+    H = 0 if hard_idx is None else hard_idx.shape[0]
+    _cabi.check(_cabi.lib().prcnn_gt_aug_sample(
+        _p(gt_boxes3d), _p(num_gt), _p(planes), B, G, _p(db_boxes), _p(db_alpha), _p(db_npts), D, _p(easy_idx), E, _p(hard_idx), H,
+        ctypes.cast(cfg4, ctypes.c_void_p), None if scope is None else ctypes.cast(scope, ctypes.c_void_p), int(try_times), K, int(seed) & 0xFFFFFFFF, _p(out["count"]), _p(out["db_id"]), _p(out["boxes3d"]),
+        _p(out["alpha"]), _p(out["y_shift"]), _p(out["stats"]), _p(out["status"]), _stream()), "prcnn_gt_aug_sample")
+    return out
+
+
 def pts_in_boxes3d(pts, boxes3d):
     """pts (N,3), boxes3d (M,7) -> flags (M,N) i32"""
     _chk(pts, "pts", ndim=2); _chk(boxes3d, "boxes3d", ndim=2)
