@@ -4,7 +4,9 @@ synthetic KITTI tree and GT database, with its random calls answered from the co
 Only used to GENERATE tests/golden/train_input_ref.npz (python tests/golden/ref_train_input.py) in the build container: it needs
 the reference tree.  What is replaced:
   - kitti_utils.get_iou3d -> tests/train_input_twin.py corner_iou3d, the float64 restatement of shapely's clip (shapely is not
-    installed here).  This is the only replaced piece of the reference's arithmetic;
+    installed here).  This is the only replaced piece of the reference's arithmetic.  So every IoU behind the fixture is the
+    TWIN's: the fixture pins the sampling loop and the random stream, not get_iou3d.  The twin and the kernel are pinned to an
+    exact rational clip instead (tests/exact_quad.py, tests/test_quad_exact_cpu.py, tests/test_gpu_train_input.py);
   - roipool3d_cuda.pts_in_boxes3d_cpu (a compiled extension) -> this library's host twin of the same C++ code;
   - np.random.rand / np.random.randint while the method runs -> the table (stream 31 extra_gt_num, 32 easy/hard, 33 index).
 The apply-probability draw of get_rpn_sample (:279, stream 30) is the one line restated outside the method.  The tree holds

@@ -142,9 +142,12 @@ def corner_iou3d(corners_a, corners_b, need_bev=False):
     return (iou3d, bev) if need_bev else iou3d
 
 
-def gt_aug_sample(gt_boxes3d, plane, db_boxes, db_alpha, db_npts, cfg, seed, frame, max_accept=16):
+def gt_aug_sample(gt_boxes3d, plane, db_boxes, db_alpha, db_npts, cfg, seed, frame, max_accept=16, iou=None):
     """One frame of prcnn_gt_aug_sample.  cfg: dict GT_EXTRA_NUM, GT_AUG_RAND_NUM, GT_AUG_APPLY_PROB, GT_AUG_HARD_RATIO,
-    PC_AREA_SCOPE (6 floats or None), TRY_TIMES.  -> dict(ids, boxes, alpha, y_shift, stats=(applied, extra, cnt, started), status)"""
+    PC_AREA_SCOPE (6 floats or None), TRY_TIMES.  -> dict(ids, boxes, alpha, y_shift, stats=(applied, extra, cnt, started), status)
+    iou(corners_new, corners_entry) -> fp32 iou3d replaces pair_iou in the collision test (tests/exact_quad.py plugs in here)"""
+    if iou is None:
+        iou = lambda p, q: pair_iou(p, q)[0]            # noqa: E731
     db_boxes = np.asarray(db_boxes, np.float32)
     db_npts = np.asarray(db_npts)
     ratio = float(cfg["GT_AUG_HARD_RATIO"])
@@ -199,7 +202,7 @@ def gt_aug_sample(gt_boxes3d, plane, db_boxes, db_alpha, db_npts, cfg, seed, fra
                 out["status"] = 1
                 break
             nc = corners3d(enl)[0]
-            if not all(pair_iou(nc, e)[0] < np.float32(1e-8) for e in lst):
+            if not all(iou(nc, e) < np.float32(1e-8) for e in lst):
                 continue
             if len(out["ids"]) >= max_accept:
                 out["status"] = 2
