@@ -56,7 +56,8 @@ typedef void* prcnn_stream_t; /* hipStream_t */
 #define PRCNN_EHIP (-2)         /* HIP runtime / launch failure */
 #define PRCNN_EUNSUPPORTED (-3) /* valid request this build has no kernel for */
 
-int prcnn_abi_version(void);   /* 10: + prcnn_corner_iou3d, prcnn_gt_aug_sample (GT-augmentation sampling loop on the device);
+int prcnn_abi_version(void);   /* 11: + prcnn_train_scene_workspace_bytes, prcnn_train_scene_prepare (the RPN training batch on the device);
+                                 * 10: + prcnn_corner_iou3d, prcnn_gt_aug_sample (GT-augmentation sampling loop on the device);
                                  * 9: + prcnn_fps_mode, prcnn_ball_query_arith, prcnn_three_nn_arith (comparison mode: the squared distance as nvcc contracts the
                                  * upstream expression); prcnn_nms_workspace_bytes grew by one flag byte per 64 x 64 tile; 8: + prcnn_mlp_group_split;
                                  * 7: split-bf16 chain entry points take the fp32 pack images too (fp32 recomputation of rows with non-finite values); 6: + prcnn_fps_status, training-mode SharedMLP (prcnn_train_*), prcnn_boxes_iou3d, prcnn_proposal_target_sample, prcnn_ref_trig (box trigonometry = the reference's host libm, bit for bit); 5: + prcnn_gt_aug_edit;
@@ -578,6 +579,39 @@ int prcnn_scene_prepare(const float* raw, const int64_t* offsets, int B, int64_t
                         const float* calib, const int32_t* img_hw, const double* scope, int npoints, uint32_t seed,
                         float* out_xyz, float* out_intensity, int32_t* out_src, int32_t* nvalid, int32_t* status,
                         void* workspace, size_t workspace_bytes, prcnn_stream_t stream);
+
+/* ======================================================================================================
+ * RPN training batch (train_scene.hip).  KittiRCNNDataset.get_rpn_sample in TRAIN mode (kitti_rcnn_dataset.py:246-362, RPN.FIXED
+ * false) between the GT-augmentation sampling loop (prcnn_gt_aug_sample, run before) and the label generation (prcnn_rpn_labels,
+ * run after, on out_xyz / out_gt_boxes3d / out_num_gt): valid points, removal of the scene points inside the accepted objects'
+ * boxes (h + 2), paste of their database points (y - y_shift), the npoints draw over the edited cloud, label boxes = training
+ * labels then placed boxes, data_augmentation (rotation, scaling, flip; stage 1).  No host round trip, no (N + P) cloud.
+ *   raw .. seed                as prcnn_scene_prepare
+ *   gt_boxes3d (B, G, 7), gt_alpha (B, G), num_gt (B) or NULL: the frame's TRAINING labels (filtrate_objects) and their alphas
+ *   acc_count (B), acc_db_id (B, K), acc_boxes3d (B, K, 7), acc_alpha (B, K), acc_y_shift (B, K) f64, acc_status (B): the outputs of
+ *     prcnn_gt_aug_sample, on the device; acc_count == NULL: GT_AUG_ENABLED false.  Frames with acc_status 1 or 3 are built
+ *     without paste or removal.  K <= 64, G + K <= 128.
+ *   db_points (P, 3), db_intensity (P), db_offsets (D+1) i64: the packed GT database; db_max_points >= every object's point count
+ *   aug_cfg  10 doubles on the HOST: rotation / scaling / flip in cfg.AUG_METHOD_LIST (0 / 1; all 0 = cfg.AUG_DATA false),
+ *            AUG_METHOD_PROB[0..2], -(pi / AUG_ROT_RANGE), pi / AUG_ROT_RANGE, 0.95, 1.05
+ *   out_xyz (B, npoints, 3) augmented points; out_input (B, npoints, 4) = [xyz | feature] or NULL; out_features (B, npoints) =
+ *   intensity - 0.5; out_src (B, npoints): the raw index of a scene point, n_raw[b] + j for the j-th pasted point (accepted order,
+ *   then database point order); nvalid (B) size of the edited cloud; status (B) as prcnn_scene_prepare;
+ *   out_gt_boxes3d (B, G + K, 7) augmented label boxes, zero rows beyond out_num_gt (B);
+ *   aug (B, 8) f64: aug_enable[0..2], angle, cos(angle), sin(angle), scale, flip (0 / 1) as the kernels used them; angle, cos, sin
+ *   are NaN when the rotation did not run, scale when the scaling did not.
+ * Random values: streams 0-2 (draw, shuffle; position = out_src's identity) and 34-36 (augmentation) of scene.hip's table.
+ * ====================================================================================================== */
+size_t prcnn_train_scene_workspace_bytes(int64_t total_points, int B, int K, int db_max_points);
+int prcnn_train_scene_prepare(const float* raw, const int64_t* offsets, int B, int64_t total_points, int max_points_per_frame,
+                              const float* calib, const int32_t* img_hw, const double* scope, int npoints, uint32_t seed,
+                              const float* gt_boxes3d, const float* gt_alpha, const int32_t* num_gt, int G,
+                              const int32_t* acc_count, const int32_t* acc_db_id, const float* acc_boxes3d, const float* acc_alpha,
+                              const double* acc_y_shift, const int32_t* acc_status, int K, const float* db_points,
+                              const float* db_intensity, const int64_t* db_offsets, int D, int db_max_points,
+                              const double* aug_cfg, float* out_xyz, float* out_input, float* out_features, int32_t* out_src,
+                              int32_t* nvalid, int32_t* status, float* out_gt_boxes3d, int32_t* out_num_gt, double* aug,
+                              void* workspace, size_t workspace_bytes, prcnn_stream_t stream);
 
 /* ======================================================================================================
  * Training-mode SharedMLP (csrc/mlp_train.h) -- BASELINE config 4, `train_rcnn.py --train_mode rpn`.

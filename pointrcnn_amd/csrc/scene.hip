@@ -27,7 +27,12 @@
 //   31     train_input.hip: randint(10, GT_EXTRA_NUM) (:419), position 0 -- 10 + below(r, GT_EXTRA_NUM - 10)
 //   32     train_input.hip: per try t, the easy / hard rand() (:437), position t -- u01(r)
 //   33     train_input.hip: per try t, randint(0, len(list)) (:441-448), position t -- below(r, len)
+//   34     train_scene.hip: data_augmentation's aug_enable = 1 - np.random.rand(3) (:521), position i = 0, 1, 2 -- 1 - u01(r)
+//   35     train_scene.hip: angle = np.random.uniform(-pi / AUG_ROT_RANGE, pi / AUG_ROT_RANGE) (:527), position 0 -- lo + (hi - lo) * u01(r)
+//   36     train_scene.hip: scale = np.random.uniform(0.95, 1.05) (:549), position 0 -- lo + (hi - lo) * u01(r)
 //   with u01(r) = fp32(r >> 8) * 2^-24 widened to double, below(r, n) = (r * n) >> 32.
+//   train_scene.hip also uses streams 0-2 for its own draw; there the position is the candidate's identity: the raw index
+//   for a scene point, n_raw + j for the j-th pasted point.
 // Both are exact uniform draws / permutations when r is uniform; the selected SET and the output ORDER depend only on
 // (seed, frame, raw index), never on the order in which the kernels' atomics append.
 //
@@ -36,12 +41,8 @@
 //   scene_sample_kernel : one workgroup per frame: 3-pass radix select of the k-th smallest key among the candidates
 //                         (LDS histograms), ties by raw index, selected entries appended to LDS, sorted by their shuffle
 //                         key with the shared bitonic sort (lds_sort.h), rows recomputed and written in that order.
-#include "lds_sort.h"
-#include "counter_rand.h"
-
-constexpr int SCENE_THREADS = 1024;
-constexpr int SCENE_MAX_TIES = 1024;
-constexpr unsigned SCENE_FAR = 1u << 30;
+// The projection and the draw live in scene_common.h: train_scene.hip (the training branch) uses the same code.
+#include "scene_common.h"
 
 struct SceneParams {
     const float4* raw;          // (total, 4) x y z intensity, lidar frame
@@ -61,27 +62,6 @@ struct SceneParams {
     int32_t* status;            // (B) 0 ok, 1 outside the reference's domain (it raises), 2 no valid point
 };
 
-
-struct RectPoint { float x, y, z; bool valid; };
-
-__device__ __forceinline__ RectPoint scene_project(const float4 p, const float* __restrict__ c, int H, int W, const double* scope,
-                                                   int use_scope) {
-    RectPoint r;
-    r.x = ((p.x * c[0] + p.y * c[3]) + p.z * c[6]) + c[9];
-    r.y = ((p.x * c[1] + p.y * c[4]) + p.z * c[7]) + c[10];
-    r.z = ((p.x * c[2] + p.y * c[5]) + p.z * c[8]) + c[11];
-    const float* P = c + 12;
-    const float h0 = ((r.x * P[0] + r.y * P[1]) + r.z * P[2]) + P[3];
-    const float h1 = ((r.x * P[4] + r.y * P[5]) + r.z * P[6]) + P[7];
-    const float h2 = ((r.x * P[8] + r.y * P[9]) + r.z * P[10]) + P[11];
-    const float u = h0 / r.z, v = h1 / r.z, depth = h2 - P[11];
-    bool ok = (u >= 0.f) && (u < (float)W) && (v >= 0.f) && (v < (float)H) && (depth >= 0.f);
-    if (use_scope)
-        ok = ok && ((double)r.x >= scope[0]) && ((double)r.x <= scope[1]) && ((double)r.y >= scope[2]) && ((double)r.y <= scope[3]) &&
-             ((double)r.z >= scope[4]) && ((double)r.z <= scope[5]);
-    r.valid = ok;
-    return r;
-}
 
 __global__ __launch_bounds__(SCENE_THREADS) void scene_flag_kernel(SceneParams P) {
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -115,25 +95,6 @@ __global__ __launch_bounds__(SCENE_THREADS) void scene_flag_kernel(SceneParams P
     }
 }
 
-// block-wide: given this thread's histogram bin count c (1024 bins = 1024 threads), find the bin where the running count
-// crosses `want` (0-based rank): returns the bin through sel[0] and the rank inside that bin through sel[1]
-__device__ __forceinline__ void scene_pick_bin(int c, int want, int* wsum, int* sel) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int incl = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int before = 0;
-    for (int w = 0; w < wave; w++) before += wsum[w];
-    const int hi = before + incl, lo = hi - c;
-    if (c > 0 && lo <= want && want < hi) { sel[0] = tid; sel[1] = want - lo; }
-    __syncthreads();
-}
-
 __global__ __launch_bounds__(SCENE_THREADS) void scene_sample_kernel(SceneParams P) {
     extern __shared__ u64 keys[];
     __shared__ int hist[1024];
@@ -155,96 +116,8 @@ __global__ __launch_bounds__(SCENE_THREADS) void scene_sample_kernel(SceneParams
         if (tid == 0) P.status[b] = 2;
         return;
     }
-    // what to draw: k candidates with the smallest keys; far points are outside the draw (always kept) when more valid
-    // points than npoints exist, inside it otherwise (top-up from ALL valid points, kitti_rcnn_dataset.py:299-303)
-    int st = 0, k;
-    bool keep_far, keep_all;
-    if (n > np) {
-        keep_all = false;
-        if (f > np) { st = 1; keep_far = false; k = np; }            // the reference's np.random.choice raises (negative size)
-        else { keep_far = true; k = np - f; }
-    } else {
-        keep_all = true; keep_far = false;
-        k = np - n;
-        if (k > n) { st = 1; k = n; }                                // the reference raises (cannot draw k > n without replacement)
-    }
-    const int ncand = keep_far ? n - f : n;
-    // ---- radix select: T = the k-th smallest 30-bit key among the candidates (rank k-1), need = how many of key == T to take
-    unsigned T = 0;
-    int need = 0;
-    if (k > 0 && k < ncand) {
-        unsigned prefix = 0;
-        int want = k - 1;
-        for (int pass = 0; pass < 3; pass++) {
-            const int shift = 20 - 10 * pass;
-            hist[tid] = 0;
-            __syncthreads();
-            for (int e = tid; e < n; e += SCENE_THREADS) {
-                const unsigned code = L[e].x;
-                if (keep_far && (code & SCENE_FAR)) continue;
-                const unsigned key = code & (SCENE_FAR - 1u);
-                if (pass == 0 || (key >> (shift + 10)) == prefix) atomicAdd(&hist[(key >> shift) & 1023u], 1);
-            }
-            __syncthreads();
-            scene_pick_bin(hist[tid], want, wsum, sel);
-            prefix = (prefix << 10) | (unsigned)sel[0];
-            want = sel[1];
-            __syncthreads();
-        }
-        T = prefix;
-        need = want + 1;
-    } else if (k >= ncand) {
-        T = SCENE_FAR;                                   // every candidate key is < 2^30: take them all
-    }                                                    // k == 0: T = 0, need = 0 -> none
-    // ---- ties on key == T: the `need` smallest raw indices
-    if (need > 0) {
-        for (int e = tid; e < n; e += SCENE_THREADS) {
-            const uint2 it = L[e];
-            if (keep_far && (it.x & SCENE_FAR)) continue;
-            if ((it.x & (SCENE_FAR - 1u)) == T) {
-                const int p = atomicAdd(&nties, 1);
-                if (p < SCENE_MAX_TIES) ties[p] = it.y;
-            }
-        }
-    }
-    __syncthreads();
-    const int m = min(nties, SCENE_MAX_TIES);
-    // ---- gather the selection into LDS as (shuffle key << 32 | raw index)
-    for (int e0 = 0; e0 < n; e0 += SCENE_THREADS) {
-        const int e = e0 + tid;
-        if (e < n) {
-            const uint2 it = L[e];
-            const bool isfar = (it.x & SCENE_FAR) != 0u;
-            const unsigned key = it.x & (SCENE_FAR - 1u);
-            const bool cand = !(keep_far && isfar);
-            bool drawn = cand && key < T;
-            if (cand && need > 0 && key == T) {
-                int rank = 0;
-                for (int q = 0; q < m; q++) rank += ties[q] < it.y ? 1 : 0;
-                drawn = rank < need;
-            }
-            if (keep_all || (keep_far && isfar)) {
-                const int p = atomicAdd(&nsel, 1);
-                keys[lds_phys(p)] = ((u64)scene_rand(P.seed, 1u, (unsigned)b, it.y) << 32) | it.y;
-            }
-            if (drawn) {
-                const int p = atomicAdd(&nsel, 1);
-                keys[lds_phys(p)] = ((u64)scene_rand(P.seed, keep_all ? 2u : 1u, (unsigned)b, it.y) << 32) | it.y;
-            }
-        }
-    }
-    __syncthreads();
-    const int total = nsel;                               // == npoints unless st == 1
-    u64 v[16];
-    if (tid * 16 < P.NP) {
-#pragma unroll
-        for (int e = 0; e < 16; e++) {
-            const int j = tid * 16 + e;
-            v[e] = j < total ? keys[lds_phys(j)] : ~0ULL;
-        }
-    }
-    __syncthreads();
-    block_sort16(v, keys, P.NP, tid);
+    const SceneSel ss = scene_select_sort(L, n, f, np, P.NP, P.seed, (unsigned)b, keys, hist, wsum, sel, ties, &nties, &nsel);
+    const int total = ss.total, st = ss.status;              // total == npoints unless st == 1
     // ---- rows in shuffled order (a short selection -- status 1 -- repeats cyclically)
     const float* c = P.calib + b * 24;
     for (int j = tid; j < np; j += SCENE_THREADS) {

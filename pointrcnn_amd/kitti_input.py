@@ -87,6 +87,19 @@ def get_lidar(lidar_file):
     return np.fromfile(lidar_file, dtype=np.float32).reshape(-1, 4)
 
 
+def pack_scans(scans, calibs, img_shapes, pin=True):
+    """The scan part of a packed batch, shared by ScenePreparer.pack and TrainScenePreparer.pack."""
+    sizes = [int(s.shape[0]) for s in scans]
+    off = np.zeros(len(scans) + 1, np.int64)
+    np.cumsum(sizes, out=off[1:])
+    raw = torch.empty((int(off[-1]), 4), dtype=torch.float32, pin_memory=pin and torch.cuda.is_available())
+    for s, a, b in zip(scans, off[:-1], off[1:]):
+        raw[a:b] = torch.from_numpy(np.ascontiguousarray(s, np.float32))
+    calib = torch.from_numpy(np.stack([c.packed() for c in calibs]))
+    hw = torch.tensor([[int(s[0]), int(s[1])] for s in img_shapes], dtype=torch.int32)
+    return {"raw": raw, "offsets": torch.from_numpy(off), "calib": calib, "img_hw": hw, "max_points": max(sizes) if sizes else 0}
+
+
 class ScenePreparer:
     """Batch version of get_rpn_sample's inference branch.  ``npoints`` / ``random_select`` as in KittiRCNNDataset
     (kitti_rcnn_dataset.py:13); area_scope = cfg.PC_AREA_SCOPE or None for cfg.PC_REDUCE_BY_RANGE = False."""
@@ -99,15 +112,7 @@ class ScenePreparer:
     def pack(self, scans, calibs, img_shapes, pin=True):
         """host side of one batch: scans = list of (Ni,4) fp32 arrays, calibs = list of Calibration, img_shapes = list of
         (H, W[, 3]).  Returns pinned host tensors ready for one asynchronous copy each."""
-        sizes = [int(s.shape[0]) for s in scans]
-        off = np.zeros(len(scans) + 1, np.int64)
-        np.cumsum(sizes, out=off[1:])
-        raw = torch.empty((int(off[-1]), 4), dtype=torch.float32, pin_memory=pin and torch.cuda.is_available())
-        for s, a, b in zip(scans, off[:-1], off[1:]):
-            raw[a:b] = torch.from_numpy(np.ascontiguousarray(s, np.float32))
-        calib = torch.from_numpy(np.stack([c.packed() for c in calibs]))
-        hw = torch.tensor([[int(s[0]), int(s[1])] for s in img_shapes], dtype=torch.int32)
-        return {"raw": raw, "offsets": torch.from_numpy(off), "calib": calib, "img_hw": hw, "max_points": max(sizes) if sizes else 0}
+        return pack_scans(scans, calibs, img_shapes, pin)
 
     def __call__(self, packed, seed=0):
         """device side: H2D of the packed batch on the current stream + prcnn_scene_prepare.
@@ -199,3 +204,72 @@ def road_plane_from_lines(lines):
     if plane[1] > 0:
         plane = -plane
     return plane / np.linalg.norm(plane[0:3])
+
+
+class TrainScenePreparer:
+    """Batch version of get_rpn_sample's TRAIN path (lib/datasets/kitti_rcnn_dataset.py:246-362, RPN.FIXED false): raw scans, labels,
+    road planes and the packed GT database in, the dictionary collate_batch would return out, on the device.  Settings carry their
+    cfg names: GT_AUG_ENABLED (with gt_database), GT_EXTRA_NUM, GT_AUG_RAND_NUM, GT_AUG_APPLY_PROB (GT_AUG_HARD_RATIO belongs to the
+    database), AUG_DATA, AUG_METHOD_LIST, AUG_METHOD_PROB, AUG_ROT_RANGE, RPN.USE_INTENSITY as use_intensity; area_scope =
+    cfg.PC_AREA_SCOPE or None for cfg.PC_REDUCE_BY_RANGE false; max_accept bounds the accepted objects per frame (K <= 64)."""
+
+    def __init__(self, npoints=16384, area_scope=PC_AREA_SCOPE, gt_database=None, GT_AUG_ENABLED=True, GT_EXTRA_NUM=15,
+                 GT_AUG_RAND_NUM=True, GT_AUG_APPLY_PROB=1.0, AUG_DATA=True, AUG_METHOD_LIST=("rotation", "scaling", "flip"),
+                 AUG_METHOD_PROB=(1.0, 1.0, 0.5), AUG_ROT_RANGE=18, use_intensity=False, max_accept=16, try_times=100, device="cuda"):
+        self.npoints = npoints
+        self.scope = None if area_scope is None else [float(v) for ax in area_scope for v in ax]
+        self.db = gt_database if GT_AUG_ENABLED else None
+        if GT_AUG_ENABLED and gt_database is None:
+            raise ValueError("TrainScenePreparer: GT_AUG_ENABLED needs the GTDatabase")
+        self.extra_num, self.rand_num, self.apply_prob = int(GT_EXTRA_NUM), bool(GT_AUG_RAND_NUM), float(GT_AUG_APPLY_PROB)
+        self.methods = tuple(AUG_METHOD_LIST) if AUG_DATA else ()
+        self.prob, self.rot_range = tuple(float(p) for p in AUG_METHOD_PROB), AUG_ROT_RANGE
+        self.use_intensity, self.max_accept, self.try_times = bool(use_intensity), int(max_accept), int(try_times)
+        self.device = torch.device(device)
+
+    def pack(self, scans, calibs, img_shapes, gt_boxes3d, gt_alpha, all_gt_boxes3d, planes, pin=True):
+        """ScenePreparer.pack plus, per frame: gt_boxes3d (ni,7) / gt_alpha (ni,) the training labels (filtrate_objects),
+        all_gt_boxes3d (mi,7) the non-DontCare labels the pasted objects must not collide with (filtrate_dc_objects), planes (4,)
+        the road plane (get_road_plane / road_plane_from_lines).  Ragged lists are zero-padded to the batch maximum; with pin every
+        tensor is pinned, so each of __call__'s copies is asynchronous."""
+        packed = pack_scans(scans, calibs, img_shapes, pin)
+        B = len(scans)
+
+        def pad(rows, width):
+            rows = [np.asarray(r, np.float32).reshape((-1,) + width) for r in rows]
+            out = np.zeros((B, max([len(r) for r in rows] + [0])) + width, np.float32)
+            for k, r in enumerate(rows):
+                out[k, :len(r)] = r
+            return torch.from_numpy(out), torch.tensor([len(r) for r in rows], dtype=torch.int32)
+        packed["gt_boxes3d"], packed["num_gt"] = pad(gt_boxes3d, (7,))
+        packed["gt_alpha"], n_alpha = pad(gt_alpha, ())
+        if not torch.equal(n_alpha, packed["num_gt"]):
+            raise ValueError("TrainScenePreparer.pack: one alpha per training label")
+        packed["all_gt_boxes3d"], packed["num_all_gt"] = pad(all_gt_boxes3d, (7,))
+        packed["planes"] = torch.from_numpy(np.asarray(planes, np.float64).reshape(B, 4).copy())
+        if pin and torch.cuda.is_available():
+            packed = {k: v.pin_memory() if isinstance(v, torch.Tensor) and not v.is_pinned() else v for k, v in packed.items()}
+        return packed
+
+    def __call__(self, packed, seed=0):
+        """device side: H2D of the packed batch, prcnn_gt_aug_sample, prcnn_train_scene_prepare and prcnn_rpn_labels on the current
+        stream, no host synchronisation.  -> dict(pts_input, pts_rect, pts_features, rpn_cls_label, rpn_reg_label, gt_boxes3d, num_gt,
+        src, nvalid, status, gt_aug_status, count, db_id, stats, aug)"""
+        dev = self.device
+        t = {k: v.to(dev, non_blocking=True) for k, v in packed.items() if isinstance(v, torch.Tensor)}
+        B = t["calib"].shape[0]
+        acc = None
+        if self.db is not None:
+            acc = self.db.sample(t["all_gt_boxes3d"], t["num_all_gt"], t["planes"], self.extra_num, self.rand_num, self.apply_prob,
+                                 None if self.scope is None else [self.scope[0:2], self.scope[2:4], self.scope[4:6]],
+                                 self.try_times, self.max_accept, seed)
+        out = ops.train_scene_prepare(t["raw"], t["offsets"], packed["max_points"], t["calib"], t["img_hw"], self.scope, self.npoints, seed,
+                                      t["gt_boxes3d"], t["gt_alpha"], t["num_gt"], acc, self.db, self.methods, self.prob, self.rot_range,
+                                      self.use_intensity)
+        out["rpn_cls_label"], out["rpn_reg_label"] = ops.rpn_labels(out["pts_rect"], out["gt_boxes3d"], out["num_gt"])
+        if acc is not None:
+            out.update(gt_aug_status=acc["status"], count=acc["count"], db_id=acc["db_id"], stats=acc["stats"])
+        else:
+            out.update(gt_aug_status=torch.zeros((B,), dtype=torch.int32, device=dev), count=torch.zeros((B,), dtype=torch.int32, device=dev),
+                       db_id=torch.zeros((B, 0), dtype=torch.int32, device=dev), stats=torch.zeros((B, 4), dtype=torch.int32, device=dev))
+        return out

@@ -61,6 +61,56 @@ def emit(name, shape, sec, **kw):
     print(json.dumps(d), flush=True)
 
 
+def train_scene_rows(dev, B=16, n_raw=115000, npoints=16384, D=2000):
+    """The RPN training batch (kitti_input.TrainScenePreparer, default.yaml settings) and, next to it, the separate passes that do
+    comparable work: scene_prepare, gt_aug_sample, gt_aug_edit, rpn_labels.  Every row is the mean of 5 timings of 20 launches,
+    with their spread.  The gt_aug_edit row is a cost row only: the sampler's accepted boxes against a random cloud of the edited
+    cloud's size and 4000 random pasted points, not the scene's own points."""
+    import numpy as np
+    from . import kitti_input
+    r = np.random.default_rng(7)
+    dbb = (r.random((D, 7)) * [60., .8, 60., .3, .3, 1., 6.28] + [-30., 1.2, 5., 1.4, 1.5, 3.4, -3.14]).astype(np.float32)
+    npd = r.integers(5, 400, D)
+    gdb = kitti_input.GTDatabase.from_arrays(dbb, np.zeros(D, np.float32), [r.random((int(n), 3)).astype(np.float32) + dbb[i, :3] for i, n in enumerate(npd)],
+                                             [r.random(int(n)).astype(np.float32) for n in npd], device=dev)
+    calib = kitti_input.Calibration.from_text(kitti_input.KITTI_CALIB_TXT)
+    scans = [kitti_input.synthetic_scan(n_raw + 97 * b, seed=900 + b) for b in range(B)]
+    labels = [(r.random((12, 7)) * [60., .8, 60., .3, .3, 1., 6.28] + [-30., 1.2, 5., 1.4, 1.5, 3.4, -3.14]).astype(np.float32) for _ in range(B)]
+    planes = [[0.0, -1.0, 0.0, 1.65]] * B
+    prep = kitti_input.TrainScenePreparer(npoints=npoints, gt_database=gdb, device=dev)
+    packed = prep.pack(scans, [calib] * B, [(375, 1242)] * B, labels, [np.zeros(12, np.float32)] * B, labels, planes)
+    t = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in packed.items()}
+    inf = kitti_input.ScenePreparer(npoints=npoints, device=dev)
+
+    def row(name, shape, fn):
+        ts = [timeit(fn) for _ in range(5)]
+        d = {"op": name, "shape": shape, "avg_launch_us": round(sum(ts) / 5 * 1e6, 1), "min_us": round(min(ts) * 1e6, 1),
+             "max_us": round(max(ts) * 1e6, 1)}
+        print(json.dumps(d), flush=True)
+        return sum(ts) / 5
+    shape = "B%d ~%dk raw npoints %d D%d" % (B, n_raw // 1000, npoints, D)
+    out = prep(packed, 5)
+    total = row("train_scene_prepare", shape + " (H2D excluded: sampler + train scene + labels)", lambda: _train_scene_device(prep, t, packed["max_points"], 5))
+    parts = row("scene_prepare", shape, lambda: ops.scene_prepare(t["raw"], t["offsets"], packed["max_points"], t["calib"], t["img_hw"], inf.scope, npoints, 5))
+    parts += row("gt_aug_sample", "B%d G12 D%d" % (B, D), lambda: gdb.sample(t["all_gt_boxes3d"], t["num_all_gt"], t["planes"], seed=5))
+    nv = int(out["nvalid"].max())
+    xyz, inten = torch.randn(B, nv, 3, device=dev) * 20.0, torch.rand(B, nv, device=dev)
+    npts, nint = torch.randn(B, 4000, 3, device=dev), torch.rand(B, 4000, device=dev)
+    acc = gdb.sample(t["all_gt_boxes3d"], t["num_all_gt"], t["planes"], seed=5)["boxes3d"]
+    parts += row("gt_aug_edit", "B%d N%d K%d P4000 (random cloud)" % (B, nv, acc.shape[1]), lambda: ops.gt_aug_edit(xyz, inten, acc, npts, nint))
+    parts += row("rpn_labels", "B%d N%d G%d" % (B, npoints, out["gt_boxes3d"].shape[1]), lambda: ops.rpn_labels(out["pts_rect"], out["gt_boxes3d"], out["num_gt"]))
+    print(json.dumps({"op": "train_scene_prepare vs separate passes", "train_scene_prepare_us": round(total * 1e6, 1),
+                      "sum_of_separate_passes_us": round(parts * 1e6, 1)}), flush=True)
+
+
+def _train_scene_device(prep, t, max_points, seed):
+    acc = prep.db.sample(t["all_gt_boxes3d"], t["num_all_gt"], t["planes"], prep.extra_num, prep.rand_num, prep.apply_prob,
+                         [prep.scope[0:2], prep.scope[2:4], prep.scope[4:6]], prep.try_times, prep.max_accept, seed)
+    out = ops.train_scene_prepare(t["raw"], t["offsets"], max_points, t["calib"], t["img_hw"], prep.scope, prep.npoints, seed,
+                                  t["gt_boxes3d"], t["gt_alpha"], t["num_gt"], acc, prep.db, prep.methods, prep.prob, prep.rot_range)
+    return ops.rpn_labels(out["pts_rect"], out["gt_boxes3d"], out["num_gt"])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
@@ -159,6 +209,9 @@ def main():
     planes = torch.tensor([[0.0, -1.0, 0.0, 1.65]] * Bs, dtype=torch.float64, device=dev)
     emit("gt_aug_sample", "B%d G12 D%d (default.yaml: 10-14 extra, 100 tries)" % (Bs, D),
          timeit(lambda: gdb.sample(sg, ngt, planes, seed=5)))
+
+    # ---- the RPN training batch from raw scans (kitti_input.TrainScenePreparer) next to the separate passes
+    train_scene_rows(dev, B=4 if args.quick else 16)
 
     # ---- NMS (default RPN path: normal, 6300 boxes, thr 0.8) and rotated
     c = torch.rand(6300, 2, generator=g) * torch.tensor([80.0, 70.0])

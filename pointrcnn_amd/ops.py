@@ -1017,3 +1017,79 @@ def scene_prepare(raw, offsets, max_points_per_frame, calib, img_hw, scope, npoi
                                       int(seed) & 0xFFFFFFFF, _p(xyz), _p(inten), _p(src), _p(nvalid), _p(status), _p(ws), ws.numel(),
                                       _stream()), "prcnn_scene_prepare")
     return xyz, inten, src, nvalid, status
+
+
+# ---------------------------------------------------------------------------------------------------------
+# RPN training batch (csrc/train_scene.hip)
+# ---------------------------------------------------------------------------------------------------------
+AUG_METHODS = ("rotation", "scaling", "flip")
+
+
+def train_scene_prepare(raw, offsets, max_points_per_frame, calib, img_hw, scope, npoints, seed, gt_boxes3d, gt_alpha, num_gt=None,
+                        accepted=None, db=None, aug_methods=AUG_METHODS, aug_prob=(1.0, 1.0, 0.5), aug_rot_range=18,
+                        use_intensity=False, workspace=None):
+    """get_rpn_sample's TRAIN path between the GT-augmentation sampling loop and the label generation, for a whole batch
+    (prcnn_train_scene_prepare).  raw .. seed as scene_prepare; gt_boxes3d (B,G,7), gt_alpha (B,G), num_gt (B) i32 or None: the
+    training labels; accepted = gt_aug_sample's dict or None (GT_AUG_ENABLED false), db = the packed database (an object with
+    points (P,3), intensity (P,), offsets (D+1,) i64, size, max_points: kitti_input.GTDatabase); aug_methods = the names of
+    cfg.AUG_METHOD_LIST that run (() = cfg.AUG_DATA false), aug_prob = cfg.AUG_METHOD_PROB, aug_rot_range = cfg.AUG_ROT_RANGE.
+    -> dict pts_rect (B,npoints,3), pts_input (the same tensor, or (B,npoints,4) when use_intensity), pts_features (B,npoints,1),
+    gt_boxes3d (B,G+K,7), num_gt (B), src, nvalid, status, aug (B,8) f64 -- see include/prcnn_pointops.h"""
+    import math
+    _chk(raw, "raw", ndim=2); _chk(calib, "calib", ndim=2); _chk(img_hw, "img_hw", _INT, 2)
+    _chk(gt_boxes3d, "gt_boxes3d", ndim=3); _chk(gt_alpha, "gt_alpha", ndim=2)
+    if offsets.dtype != torch.int64 or not offsets.is_contiguous() or offsets.device != raw.device:
+        raise RuntimeError("offsets must be a contiguous int64 tensor on the device of raw")
+    if raw.shape[1] != 4 or calib.shape[1] != 24 or img_hw.shape[1] != 2:
+        raise RuntimeError("expected raw (total,4), calib (B,24), img_hw (B,2)")
+    B, total, dev = offsets.shape[0] - 1, raw.shape[0], raw.device
+    G = gt_boxes3d.shape[1]
+    if calib.shape[0] != B or img_hw.shape[0] != B:
+        raise RuntimeError("calib / img_hw must have one row per frame")
+    if tuple(gt_boxes3d.shape) != (B, G, 7) or tuple(gt_alpha.shape) != (B, G):
+        raise ValueError("train_scene_prepare: gt_boxes3d must be (%d, G, 7), gt_alpha (%d, G)" % (B, B))
+    if num_gt is not None:
+        _chk(num_gt, "num_gt", _INT, 1)
+        if num_gt.shape[0] != B:
+            raise ValueError("train_scene_prepare: num_gt must be (%d,)" % B)
+    unknown = [m for m in aug_methods if m not in AUG_METHODS]
+    if unknown:
+        raise ValueError("train_scene_prepare: unknown augmentation %r" % unknown)
+    K, D, db_max = 0, 0, 0
+    acc = [None] * 6
+    dbt = [None] * 3
+    if accepted is not None:
+        if db is None:
+            raise ValueError("train_scene_prepare: accepted objects need the database they came from")
+        K, D, db_max = accepted["db_id"].shape[1], int(db.size), int(db.max_points)
+        acc = [_chk(accepted["count"], "count", _INT, 1), _chk(accepted["db_id"], "db_id", _INT, 2),
+               _chk(accepted["boxes3d"], "boxes3d", ndim=3), _chk(accepted["alpha"], "alpha", ndim=2),
+               _chk(accepted["y_shift"], "y_shift", torch.float64, 2), _chk(accepted["status"], "status", _INT, 1)]
+        if acc[0].shape[0] != B or tuple(acc[2].shape) != (B, K, 7) or tuple(acc[3].shape) != (B, K) or tuple(acc[4].shape) != (B, K):
+            raise ValueError("train_scene_prepare: the accepted objects must describe %d frames" % B)
+        dbt = [_chk(db.points, "db.points", ndim=2), _chk(db.intensity, "db.intensity", ndim=1), db.offsets]
+        if dbt[2].dtype != torch.int64 or dbt[2].shape[0] != D + 1 or dbt[1].shape[0] != dbt[0].shape[0]:
+            raise ValueError("train_scene_prepare: db.offsets must be (D+1,) int64, db.intensity one value per point")
+    L = _cabi.lib()
+    need = int(L.prcnn_train_scene_workspace_bytes(total, B, K, db_max))
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev) if workspace is None else workspace
+    xyz = torch.empty((B, npoints, 3), dtype=_F32, device=dev)
+    pin = torch.empty((B, npoints, 4), dtype=_F32, device=dev) if use_intensity else None
+    feat = torch.empty((B, npoints), dtype=_F32, device=dev)
+    src = torch.empty((B, npoints), dtype=_INT, device=dev)
+    nvalid = torch.empty((B,), dtype=_INT, device=dev)
+    status = torch.empty((B,), dtype=_INT, device=dev)
+    out_gt = torch.empty((B, G + K, 7), dtype=_F32, device=dev)
+    out_ng = torch.empty((B,), dtype=_INT, device=dev)
+    aug = torch.empty((B, 8), dtype=torch.float64, device=dev)
+    sc = None if scope is None else (ctypes.c_double * 6)(*[float(v) for v in scope])
+    hi = math.pi / aug_rot_range
+    cfg = (ctypes.c_double * 10)(*([1.0 if m in aug_methods else 0.0 for m in AUG_METHODS] + [float(p) for p in aug_prob] +
+                                   [-hi, hi, 0.95, 1.05]))
+    _cabi.check(L.prcnn_train_scene_prepare(
+        _p(raw), _p(offsets), B, total, int(max_points_per_frame), _p(calib), _p(img_hw), sc, int(npoints), int(seed) & 0xFFFFFFFF,
+        _p(gt_boxes3d), _p(gt_alpha), _p(num_gt), G, _p(acc[0]), _p(acc[1]), _p(acc[2]), _p(acc[3]), _p(acc[4]), _p(acc[5]), K,
+        _p(dbt[0]), _p(dbt[1]), _p(dbt[2]), D, db_max, cfg, _p(xyz), _p(pin), _p(feat), _p(src), _p(nvalid), _p(status), _p(out_gt),
+        _p(out_ng), _p(aug), _p(ws), ws.numel(), _stream()), "prcnn_train_scene_prepare")
+    return {"pts_rect": xyz, "pts_input": pin if use_intensity else xyz, "pts_features": feat.unsqueeze(-1), "gt_boxes3d": out_gt,
+            "num_gt": out_ng, "src": src, "nvalid": nvalid, "status": status, "aug": aug}
