@@ -22,7 +22,8 @@
  *     prcnn_last_error() returns a thread-local message for the last failing call;
  *   - every entry point is re-entrant and may be called concurrently from several host threads, each on its own
  *     device (the reference's nn.DataParallel convention).  The only process-wide state is a per-(kernel, device)
- *     "dynamic-LDS limit already raised" bit, updated atomically (csrc/common.h PrcnnLdsLimit).
+ *     "dynamic-LDS limit already raised" bit, updated atomically (csrc/common.h PrcnnLdsLimit), and the snapshot of the
+ *     environment switches, published through one atomic pointer (csrc/switches.h).
  *
  * Arithmetic contract (shared bit-for-bit with oracle/prcnn_oracle.c):
  *   - squared distances are ((dx*dx + dy*dy) + dz*dz) with individually rounded fp32 operations (no FMA; the library is built
@@ -56,7 +57,8 @@ typedef void* prcnn_stream_t; /* hipStream_t */
 #define PRCNN_EHIP (-2)         /* HIP runtime / launch failure */
 #define PRCNN_EUNSUPPORTED (-3) /* valid request this build has no kernel for */
 
-int prcnn_abi_version(void);   /* 11: + prcnn_train_scene_workspace_bytes, prcnn_train_scene_prepare (the RPN training batch on the device);
+int prcnn_abi_version(void);   /* 12: + prcnn_switches_reload, prcnn_switch_get (the PRCNN_* kernel switches are read once, through one table);
+                                 * 11: + prcnn_train_scene_workspace_bytes, prcnn_train_scene_prepare (the RPN training batch on the device);
                                  * 10: + prcnn_corner_iou3d, prcnn_gt_aug_sample (GT-augmentation sampling loop on the device);
                                  * 9: + prcnn_fps_mode, prcnn_ball_query_arith, prcnn_three_nn_arith (comparison mode: the squared distance as nvcc contracts the
                                  * upstream expression); prcnn_nms_workspace_bytes grew by one flag byte per 64 x 64 tile; 8: + prcnn_mlp_group_split;
@@ -70,6 +72,15 @@ const char* prcnn_last_error(void);
 /* hex digest of the kernel sources + compile flags this library was built from (the Python binding compares it with the
  * sources it sits next to and refuses / rebuilds a stale library instead of silently loading it) */
 const char* prcnn_build_id(void);
+/* The PRCNN_* environment variables that select between kernels (csrc/switches.h lists them, INTEGRATION.md describes them)
+ * are read ONCE, on the first call that consults one; later changes of the environment are not seen.
+ * prcnn_switches_reload() reads them again and publishes the new values for every later call, from any thread; a call that
+ * runs concurrently reads each switch from the old or the new set, never a torn value.  The caller must not change the
+ * environment while this function runs (the C library does not allow it to be written while another thread reads it). */
+int prcnn_switches_reload(void);
+/* the library's current view of one switch, by variable name: *set = present, *num = atol of its value (0 if unset); either
+ * pointer may be null.  PRCNN_EINVAL for a name that is not a switch of this library.  For tests; no product path calls it. */
+int prcnn_switch_get(const char* name, int* set, long* num);
 
 /* ---------------------------------------------------------------------------------------------
  * PointNet++ operators.  Replace pointnet2_cuda.* [UPSTREAM sshaoshuai/Pointnet2.PyTorch, not in

@@ -4,6 +4,7 @@ This is the reference-side binding a maintainer would add: raw 
 a hipStream_t, no torch types cross the boundary.  The product path FAILS LOUDLY when the library is
 missing: there is no CPU or PyTorch fallback.
 """
+import contextlib
 import ctypes
 import os
 
@@ -36,13 +37,15 @@ class TrainLayer(ctypes.Structure):
                 ("dW", _P), ("dgamma", _P), ("dbeta", _P)]
 
 
-REQUIRED_ABI = 10                # prcnn_abi_version() the signatures below describe
+REQUIRED_ABI = 12                # prcnn_abi_version() the signatures below describe
 
 # name -> (restype, argtypes); mirrors include/prcnn_pointops.h one for one
 SIGNATURES = {
     "prcnn_abi_version": (_I, []),
     "prcnn_last_error": (ctypes.c_char_p, []),
     "prcnn_build_id": (ctypes.c_char_p, []),
+    "prcnn_switches_reload": (_I, []),
+    "prcnn_switch_get": (_I, [ctypes.c_char_p, ctypes.POINTER(_I), ctypes.POINTER(ctypes.c_long)]),
     "prcnn_fps": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "prcnn_fps_status": (_I, []),
     "prcnn_fps_order": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
@@ -193,3 +196,32 @@ def check(rc, what=""):
     if rc != 0:
         msg = lib().prcnn_last_error()
         raise PointOpsError("%s failed (code %d): %s" % (what or "prcnn call", rc, msg.decode() if msg else "?"))
+
+
+def switch_get(name):
+    """the library's current view of one native switch: (set, num); PointOpsError for a name that is not in csrc/switches.h"""
+    is_set, num = _I(), ctypes.c_long()
+    check(lib().prcnn_switch_get(name.encode(), ctypes.byref(is_set), ctypes.byref(num)), "prcnn_switch_get")
+    return bool(is_set.value), num.value
+
+
+@contextlib.contextmanager
+def switches(**env):
+    """Set (or, with None, unset) native PRCNN_* switches for the body: the library reads its switches once, so this --
+    environment change + prcnn_switches_reload(), undone on exit -- is the only way to flip one in a running process."""
+    for name in env:
+        switch_get(name)
+    old = {name: os.environ.get(name) for name in env}
+
+    def apply(values):
+        for name, value in values.items():
+            if value is None:
+                os.environ.pop(name, None)
+            else:
+                os.environ[name] = value
+        lib().prcnn_switches_reload()
+    apply(env)
+    try:
+        yield
+    finally:
+        apply(old)

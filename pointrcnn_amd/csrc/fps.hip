@@ -20,6 +20,7 @@
 //   is what makes a single barrier per iteration sufficient.
 // Single-wave configurations (N <= 1024) skip LDS and the barrier entirely.
 #include "lds_sort.h"
+#include "switches.h"
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <int PPT> struct fvec_t { typedef float type __attribute__((ext_vector_type(PPT))); };
@@ -1322,15 +1323,13 @@ PRCNN_API int prcnn_fps(const float* xyz, int B, int N, int npoint, float* tmp, 
             return prcnn_fail(PRCNN_EHIP, "prcnn_fps: cannot raise the dynamic LDS limit of the pruned kernel");
         // two-level pruning (fps_slot_kernel): pays at 16 points per lane (16 384 -> 4 096: 3.82 -> 3.56 ms), not at 4 or 8 (+4..9 %: the
         // pair tests and the separate running-maximum pass cost what the skipped slots save); PRCNN_FPS_SLOTS=0 is the A/B switch (same bits)
-        const char* slots_env = getenv("PRCNN_FPS_SLOTS");              // read per call: the tests flip it in-process
-        const bool slots = slots_env == nullptr || atoi(slots_env) != 0;
+        const bool slots = sw_enabled(SW_FPS_SLOTS);
         static PrcnnLdsLimit slot_attr;
         if (slots && N > 8192 && !slot_attr.raise((const void*)fps_slot_kernel<16, 16>, 16 * 4096))
             return prcnn_fail(PRCNN_EHIP, "prcnn_fps: cannot raise the dynamic LDS limit of the slot kernel");
         // two samples per exchange where the second is provable (fps_batch_kernel; same bits): measured 2-3 % SLOWER than the slot kernel
         // (DESIGN.md 8), so it is opt-in, PRCNN_FPS_BATCH=1
-        const char* batch_env = getenv("PRCNN_FPS_BATCH");
-        const bool batch = batch_env != nullptr && atoi(batch_env) != 0;
+        const bool batch = sw_opt_in(SW_FPS_BATCH);
         static PrcnnLdsLimit batch_attr;
         if (slots && batch && N > 8192 && !batch_attr.raise((const void*)fps_batch_kernel<16, 16>, 16 * 4096))
             return prcnn_fail(PRCNN_EHIP, "prcnn_fps: cannot raise the dynamic LDS limit of the batch kernel");
@@ -1355,7 +1354,7 @@ PRCNN_API int prcnn_fps(const float* xyz, int B, int N, int npoint, float* tmp, 
         const int S = prcnn_divup(N, FPS_MULTI_SLICE);
         // multi-workgroup register-resident kernel: the exchange slots (B * 2 * S * 5 granules of 8 bytes) live at the start
         // of tmp, which is 4 N bytes per frame >= 80 S bytes.  Needs every slice of a frame resident at once: up to 256 CUs.
-        static const bool use_mem = getenv("PRCNN_FPS_MEM") != nullptr;       // A/B switch: the L2 re-read kernel (same bits)
+        const bool use_mem = sw_present(SW_FPS_MEM);       // A/B switch: the L2 re-read kernel (same bits)
         if (!use_mem && S <= FPS_MULTI_MAX_SPLIT && ((uintptr_t)tmp & 7) == 0) {
             const size_t slot_bytes = (size_t)B * 2 * S * 5 * sizeof(unsigned long long);
             if (prcnn_fill_words(tmp, 0xFFFFFFFFu, slot_bytes / 4, s) != hipSuccess) return prcnn_fail(PRCNN_EHIP, "prcnn_fps: cannot clear the exchange slots");

@@ -10,7 +10,7 @@
 // in a register, so index traffic is read once (upstream re-reads idx for every channel) and the writes
 // are fully coalesced; the gathered reads are scattered by nature of the (B,C,N) layout.
 #include "common.h"
-#include <stdlib.h>
+#include "switches.h"
 
 #define G_THREADS 256
 
@@ -86,7 +86,7 @@ __global__ __launch_bounds__(GP_THREADS) void gather_pm_kernel(const float* __re
 }
 // -> true when the staged kernel took the call
 static bool launch_gather_pm(const float* feat, const int32_t* idx, int B, int C, int N, long J, float* out, hipStream_t s) {
-    if (getenv("PRCNN_GATHER_DIRECT") != nullptr) return false;                          // A/B switch (same values)
+    if (sw_present(SW_GATHER_DIRECT)) return false;                          // A/B switch (same values)
     const int CGT = 8;
     if (C % CGT || J % 4 || (long)N * CGT * 4 > 128 * 1024 || J < 4L * N || J > 0x7fffffffL) return false;    // (staging must pay: >= 4 outputs per source point)
     if ((((uintptr_t)idx | (uintptr_t)out) & 15) != 0) return false;
@@ -476,14 +476,13 @@ PRCNN_API int prcnn_three_interp(const float* feat, const int32_t* idx, const fl
     if (B == 0 || C == 0 || n == 0) return PRCNN_OK;
     PRCNN_REQUIRE(feat && idx && weight && out, "prcnn_three_interp: null pointer");
     // LDS-staged kernel when a useful number of source rows fits (<= 128 KB) and there are enough points to amortise the staging
-    const bool no_lds = getenv("PRCNN_INTERP_DIRECT") != nullptr;                        // A/B switch (same bits)
+    const bool no_lds = sw_present(SW_INTERP_DIRECT);                        // A/B switch (same bits)
     int CG = (128 * 1024 / 4) / m;
     if (CG > C) CG = C;
     if (CG > 16) CG = 16;                                                                 // (more workgroups beat longer rows)
-    const char* lay = getenv("PRCNN_INTERP_LAYOUT");                                       // "rows": channel-major LDS rows (A/B switch)
-    const char* cge = getenv("PRCNN_INTERP_CGT");                                          // A/B switch: channels per workgroup (same bits)
-    const int CGT = (cge && atoi(cge) == 4) ? 4 : (CG >= 8 ? 8 : 4);
-    if (!no_lds && !(lay && lay[0] == 'r') && CG >= 4 && C % CGT == 0 && n >= 2 * m && (long)B * (C / CGT) >= 16) {
+    const bool lds_rows = sw_c0(SW_INTERP_LAYOUT) == 'r';                                  // "rows": channel-major LDS rows (A/B switch)
+    const int CGT = sw_num(SW_INTERP_CGT, 0) == 4 ? 4 : (CG >= 8 ? 8 : 4);                // A/B switch: channels per workgroup (same bits)
+    if (!no_lds && !lds_rows && CG >= 4 && C % CGT == 0 && n >= 2 * m && (long)B * (C / CGT) >= 16) {
         static PrcnnLdsLimit lim[4];
         const size_t bytes = (size_t)CGT * m * sizeof(float);
         const bool vec = (n % 4 == 0) && (((uintptr_t)idx | (uintptr_t)weight | (uintptr_t)out) & 15) == 0;

@@ -19,7 +19,7 @@
 // Pipeline: global loads for chunk c+1 are issued before the MFMAs of chunk c and written to the other
 // LDS buffer after them (one barrier per chunk).
 #include "common.h"
-#include <stdlib.h>
+#include "switches.h"
 
 #define MLP_BM 128
 #define MLP_BN 64
@@ -2385,10 +2385,7 @@ static int chain_p_grid() {
     return cus > 0 ? cus : 8;
 }
 // PRCNN_CHAIN_PERSIST=0: the per-tile kernels (A/B switch, same bits)
-static bool chain_persist_on() {                           // (read per launch: the tests flip it inside one process)
-    const char* e = getenv("PRCNN_CHAIN_PERSIST");
-    return !(e && atoi(e) == 0);
-}
+static bool chain_persist_on() { return sw_enabled(SW_CHAIN_PERSIST); }
 template <int MODE, int NB1>
 static int launch_chain_p(const ChainParams& C, hipStream_t s) {
     constexpr size_t lds = chain_p_lds_bytes<MODE, NB1>();
@@ -2400,14 +2397,8 @@ static int launch_chain_p(const ChainParams& C, hipStream_t s) {
     hipLaunchKernelGGL((mlp_chain_p_kernel<MODE, NB1, 6>), dim3(grid), dim3(CP_WAVES * 64), lds, s, C);
     return PRCNN_OK;
 }
-static bool chain_coop_on() {                              // (read per launch: the tests flip it inside one process)
-    const char* e = getenv("PRCNN_CHAIN_COOP");
-    return !(e && atoi(e) == 0);
-}
-static bool chain_coop_forced() {                          // 2: the cooperative form also where the lane-is-a-row kernel is the default
-    const char* e = getenv("PRCNN_CHAIN_COOP");
-    return e && atoi(e) == 2;
-}
+static bool chain_coop_on() { return sw_num(SW_CHAIN_COOP, 1) != 0; }
+static bool chain_coop_forced() { return sw_num(SW_CHAIN_COOP, 1) == 2; }      // 2: the cooperative form also where the lane-is-a-row kernel is the default
 
 // =====================================================================================================
 // PERSISTENT chain: the fast chain's arithmetic with ALL layers' packed weights resident in LDS for the lifetime of the
@@ -2696,13 +2687,12 @@ static int launch_mlp(int mode, MlpParams& P, hipStream_t s) {
     // batch size (a frame's result is the same bits in a batch of 1 and of 32).  PRCNN_SPLIT_MIN_TILES (dev A/B) sends launches of
     // fewer tiles to the fp32 kernels, which have forms for few rows.
     const long split_tiles_wide = (long)prcnn_divup(P.rows, MLP_BM) * prcnn_divup(P.NB, 4), split_tiles_narrow = (long)prcnn_divup(P.rows, MLP_BM) * prcnn_divup(P.NB, 2);
-    static const long split_min = getenv("PRCNN_SPLIT_MIN_TILES") ? atol(getenv("PRCNN_SPLIT_MIN_TILES")) : 0;
+    const long split_min = sw_num(SW_SPLIT_MIN_TILES, 0);
     // the hoisted grouped form (prcnn_mlp_group_split); PRCNN_GROUP_SPLIT=0: A/B switch back to the fp32 layer kernel
-    static const bool group_split_on = !(getenv("PRCNN_GROUP_SPLIT") && atoi(getenv("PRCNN_GROUP_SPLIT")) == 0);
-    const bool split_group = group_split_on && mode == MODE_GROUP && P.act == 1 && P.C == P.K && !P.addY;
+    const bool split_group = sw_enabled(SW_GROUP_SPLIT) && mode == MODE_GROUP && P.act == 1 && P.C == P.K && !P.addY;
     if (P.wsplit && (mode == MODE_PLAIN || split_group) && P.K % MLP_BK == 0 && P.vec_a && split_tiles_narrow >= split_min) {
         PRCNN_REQUIRE(aligned16(P.wsplit) && (P.split_terms == 3 || P.split_terms == 6), "prcnn_mlp: bad split image / terms=%d", P.split_terms);
-        static const long split_wide_min = getenv("PRCNN_SPLIT_WIDE_MIN") ? atol(getenv("PRCNN_SPLIT_WIDE_MIN")) : 192;
+        const long split_wide_min = sw_num(SW_SPLIT_WIDE_MIN, 192);
         const bool wide = P.NB >= 4 && split_tiles_wide >= split_wide_min;
         dim3 grid(prcnn_divup(P.rows, MLP_BM), prcnn_divup(P.NB, wide ? 4 : 2));
         if (!P.seg_cnt) {
@@ -2711,8 +2701,7 @@ static int launch_mlp(int mode, MlpParams& P, hipStream_t s) {
         }
         // a launch sized for the CAPACITY of a compacted list (device-side row count): 2048 workgroups (four rounds of the 512 resident
         // ones, a multiple of the 8 XCDs) walk the live tiles instead of one workgroup per tile of capacity; PRCNN_BOUNDED_GRID=0: A/B
-        static const bool bounded_on = !(getenv("PRCNN_BOUNDED_GRID") && atoi(getenv("PRCNN_BOUNDED_GRID")) == 0);
-        const bool bounded = bounded_on && P.rows_dev && !P.seg_cnt && !P.addY && grid.x > 2048u;
+        const bool bounded = sw_enabled(SW_BOUNDED_GRID) && P.rows_dev && !P.seg_cnt && !P.addY && grid.x > 2048u;
         if (bounded) grid = dim3(2048u, 1);
 #define SPL_LAUNCH(W, T)                                                                                                  \
     do {                                                                                                                  \
@@ -2732,15 +2721,14 @@ static int launch_mlp(int mode, MlpParams& P, hipStream_t s) {
     // >= 97 output channels: 128x128 workgroup tile -- unless that leaves most of the 256 CUs without a workgroup
     // (few rows, e.g. FP3's 2048 known points): then the 128x64 tile doubles the number of workgroups
     // (a device-side row count means a compacted list: P.rows is its worst case, the live part is expected to be small)
-    static const long wide_min = getenv("PRCNN_WIDE_MIN_TILES") ? atol(getenv("PRCNN_WIDE_MIN_TILES")) : 192;
-    static const bool wide_lists = getenv("PRCNN_WIDE_LISTS") != nullptr;
+    const long wide_min = sw_num(SW_WIDE_MIN_TILES, 192);
+    const bool wide_lists = sw_present(SW_WIDE_LISTS);
     bool wide = P.NB >= 4 && (!P.rows_dev || wide_lists) && (long)prcnn_divup(P.rows, MLP_BM) * prcnn_divup(P.NB, 4) >= wide_min;
     dim3 grid(prcnn_divup(P.rows, MLP_BM), prcnn_divup(P.NB, wide ? 4 : 2));
     // v2 (B operand straight from L2, up to four workgroups per CU) is the default; PRCNN_LAYER_V1=1 is the A/B switch (same bits).
-    static const bool force_v1 = getenv("PRCNN_LAYER_V1") != nullptr;
-    const bool v2 = !force_v1;
+    const bool v2 = !sw_present(SW_LAYER_V1);
     const bool fast = P.K % MLP_BK == 0 && P.vec_a && (mode == MODE_PLAIN || (mode == MODE_GROUP && P.act == 1 && P.C == P.K));
-    if (v2 && fast && mode == MODE_PLAIN && wide && getenv("PRCNN_WIDE_MIN_TILES") == nullptr) {
+    if (v2 && fast && mode == MODE_PLAIN && wide && !sw_present(SW_WIDE_MIN_TILES)) {
         // four workgroups per CU = 1024 resident tiles: with >= 1024 wide tiles the narrow tile (twice as many, half as long)
         // runs in more, staggered rounds, so one round's store epilogue overlaps the next one's main loop (measured: 32768 x
         // 512 -> 512 171 -> 160 us, 131072 x 256 -> 256 173 -> 167 us); between 384 and 1023 wide tiles the wide tile's better
@@ -2749,7 +2737,7 @@ static int launch_mlp(int mode, MlpParams& P, hipStream_t s) {
         wide = tiles_wide >= 384 && tiles_wide < 1024;
     }
     grid = dim3(prcnn_divup(P.rows, MLP_BM), prcnn_divup(P.NB, wide ? 4 : 2));
-    if (v2 && mode == MODE_PLAIN && !P.seg_cnt && P.xcd_tpf == 0 && getenv("PRCNN_NO_WGM") == nullptr) {
+    if (v2 && mode == MODE_PLAIN && !P.seg_cnt && P.xcd_tpf == 0 && !sw_present(SW_NO_WGM)) {
         P.wgm_cols = (int)grid.y;
         grid = dim3((unsigned)(prcnn_divup(grid.x, 8) * 8 * grid.y), 1);
     }
@@ -2883,8 +2871,7 @@ PRCNN_API int prcnn_mlp_rows_addinterp_split(const float* in, int ld_in, int K, 
     P.in = in; P.ld_in = ld_in;
     P.vec_a = aligned16(in) && (ld_in % 4 == 0);
     P.addY = y_cl; P.ldY = ld_y; P.idx3 = idx3; P.w3 = w3; P.n = n; P.m = m;
-    static const int addy_phase = getenv("PRCNN_ADDY_PHASE") ? atoi(getenv("PRCNN_ADDY_PHASE")) : 2;      // A/B switch: 0 = all in the epilogue
-    P.addy_phase = addy_phase;
+    P.addy_phase = (int)sw_num(SW_ADDY_PHASE, 2);      // A/B switch: 0 = all in the epilogue
     P.rows_unit = 1;
     P.wsplit = wsplit; P.split_terms = terms;
     return launch_mlp(MODE_PLAIN, P, (hipStream_t)stream);
@@ -2931,8 +2918,7 @@ PRCNN_API int prcnn_mlp_rows_addinterp(const float* in, int ld_in, int K, const 
     P.in = in; P.ld_in = ld_in;
     P.vec_a = aligned16(in) && (ld_in % 4 == 0);
     P.addY = y_cl; P.ldY = ld_y; P.idx3 = idx3; P.w3 = w3; P.n = n; P.m = m;
-    static const int addy_phase = getenv("PRCNN_ADDY_PHASE") ? atoi(getenv("PRCNN_ADDY_PHASE")) : 2;      // A/B switch: 0 = all in the epilogue
-    P.addy_phase = addy_phase;
+    P.addy_phase = (int)sw_num(SW_ADDY_PHASE, 2);      // A/B switch: 0 = all in the epilogue
     return launch_mlp(MODE_PLAIN, P, (hipStream_t)stream);
 }
 
@@ -3346,8 +3332,7 @@ __global__ __launch_bounds__(256, 1) void mlp_rows32_kernel(const MlpParams Pin,
 }
 
 static bool rows32_ok(int mode, const MlpParams& P) {
-    static const bool off = getenv("PRCNN_NO_ROWS32") != nullptr;    // A/B switch (the layer kernel gives the same bits)
-    return !off && mode == MODE_PLAIN && !P.addY && P.pool_ns == 0 && !P.seg_cnt && P.vec_a && P.K % 8 == 0 && P.K >= 256 &&
+    return !sw_present(SW_NO_ROWS32) && mode == MODE_PLAIN && !P.addY && P.pool_ns == 0 && !P.seg_cnt && P.vec_a && P.K % 8 == 0 && P.K >= 256 &&
            P.K <= R32_MAX_K && P.Nout >= 128 && P.rows <= 4096;
 }
 
@@ -3391,7 +3376,7 @@ PRCNN_API int prcnn_mlp_chain_supported(int mode, int nlayers, const int* nout, 
     if (!(pool_ns == 0 || pool_ns == 16 || pool_ns == 32)) return 0;
     // two wide layers on an un-pooled grouped list: the stack kernel (hoisted form, nsample 1 -- checked again at dispatch)
     if (mode == MODE_GROUP && nlayers == 2 && pool_ns == 0 && nout[0] > 0 && nout[1] > 0 && (nout[0] > 128 || nout[1] > 128) &&
-        nb32(nout[0]) <= ST_MAX_NB0 && nb32(nout[1]) <= 16 && getenv("PRCNN_NO_STACK") == nullptr)
+        nb32(nout[0]) <= ST_MAX_NB0 && nb32(nout[1]) <= 16 && !sw_present(SW_NO_STACK))
         return 1;
     for (int l = 0; l < nlayers; l++)
         if (nout[l] <= 0 || nout[l] > 128) return 0;
@@ -3428,7 +3413,7 @@ static int dispatch_chain(int mode, ChainParams& C, hipStream_t s) {
     // (pooled groups, or -- nsample 1, no pooling -- the flat row list of the padding-free path: the same kernel writes rows)
     if (mode == MODE_GROUP && P.C == 0 && !P.act && P.K == 3 && C.nlayers == 3 && P.new_xyz &&
         (P.pool_ns == P.ns || (P.pool_ns == 0 && P.ns == 1)) && C.N2 % 4 == 0 &&
-        getenv("PRCNN_NO_SA0") == nullptr) {              // (A/B switch; the generic chain kernel gives the same bits)
+        !sw_present(SW_NO_SA0)) {              // (A/B switch; the generic chain kernel gives the same bits)
         // persistent: one resident workgroup per occupancy slot (256 CUs x 3 or 2 workgroups at 115 / 243 registers)
 #define SA0_CASE(W0, W1, NBL, NSV)                                                                                        \
         if (P.Nout == W0 && C.N1 == W1 && n2 == NBL && P.ns == NSV) {                                                   \
@@ -3446,7 +3431,7 @@ static int dispatch_chain(int mode, ChainParams& C, hipStream_t s) {
     // Opt-in (PRCNN_PERSISTENT_CHAIN=1): 6-12 % faster per launch with ONE batch in flight, but a persistent workgroup
     // holds its CU's LDS for the whole kernel, which starves the other in-flight batches' kernels (FPS sort, layer tiles):
     // measured -6 % RPN throughput at 3 batches in flight, so the default keeps the per-tile workgroups.
-    if (chain_fast_ok(mode, C, n0, n1, n2) && !P.seg_cnt && getenv("PRCNN_PERSISTENT_CHAIN") != nullptr) {
+    if (chain_fast_ok(mode, C, n0, n1, n2) && !P.seg_cnt && sw_present(SW_PERSISTENT_CHAIN)) {
         // persistent form: weights of the whole stack resident in LDS, one 8-wave workgroup per CU
 #define PERS_CASE(M, KB0V, A, B, CC)                                                                                         \
         if (mode == M && P.KB == KB0V && n0 == A && n1 == B && n2 == CC) {                                                    \
@@ -3466,7 +3451,7 @@ static int dispatch_chain(int mode, ChainParams& C, hipStream_t s) {
         PERS_CASE(MODE_PLAIN, 16, 4, 3, 0)
 #undef PERS_CASE
     }
-    if (chain_fast_ok(mode, C, n0, n1, n2) && getenv("PRCNN_NO_FAST_CHAIN") == nullptr) {      // (A/B switch, same bits)
+    if (chain_fast_ok(mode, C, n0, n1, n2) && !sw_present(SW_NO_FAST_CHAIN)) {      // (A/B switch, same bits)
 #define FAST_CASE(M, A, B, CC) if (mode == M && n0 == A && n1 == B && n2 == CC) { launch_chain_fast<M, A, B, CC>(C, s); PRCNN_LAUNCH_CHECK("prcnn_mlp_chain(fast)"); return PRCNN_OK; }
         FAST_CASE(MODE_GROUP, 2, 4, 0)
         FAST_CASE(MODE_GROUP, 3, 4, 0)
@@ -3567,7 +3552,7 @@ PRCNN_API int prcnn_mlp_chain_interp(const float* known_cl, int ld_known, const 
     C.a.vec_b = C1 > 0 && aligned16(skip_cl) && (ld_skip % 4 == 0) && (C2 % 4 == 0);
     rc = set_interp_act(C.a, act_bias, C2, C1);
     if (rc) return rc;
-    if (B % 8 == 0 && n % 128 == 0 && getenv("PRCNN_NO_XCD_ORDER") == nullptr) C.a.xcd_tpf = n / 128;
+    if (B % 8 == 0 && n % 128 == 0 && !sw_present(SW_NO_XCD_ORDER)) C.a.xcd_tpf = n / 128;
     return dispatch_chain(MODE_INTERP, C, (hipStream_t)stream);
 }
 
@@ -3589,7 +3574,7 @@ PRCNN_API int prcnn_mlp_chain_interp_split(const float* known_cl, int ld_known, 
     P.vec_a = 1; P.act = 2; P.act_bias = act_bias;
     P.wsplit = wchain; P.split_terms = terms; P.wpack = wpack;
     C.nlayers = 1;
-    if (B % 8 == 0 && n % 128 == 0 && getenv("PRCNN_NO_XCD_ORDER") == nullptr) P.xcd_tpf = n / 128;
+    if (B % 8 == 0 && n % 128 == 0 && !sw_present(SW_NO_XCD_ORDER)) P.xcd_tpf = n / 128;
     const dim3 grid(prcnn_divup(P.rows, 128));
     if (terms == 6 && chain_coop_on() && chain_persist_on() && (long)B * m * ld_known < (1L << 30)) {
         const int rc = launch_chain_p<MODE_INTERP, 0>(C, (hipStream_t)stream);

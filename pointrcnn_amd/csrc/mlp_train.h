@@ -1362,7 +1362,7 @@ PRCNN_API int prcnn_train_stack_fwd(const prcnn_train_src_t* src, const prcnn_tr
         else hipLaunchKernelGGL((train_fwd_kernel<M, 1>), grid, dim3(MLP_THREADS), 0, s, T);                    \
     } while (0)
         const bool fastp = mode == MODE_PLAIN && P.vec_a && K % 4 == 0 && K >= 4 && P.ld_in % 4 == 0 && aligned16(P.in) &&
-                           (!T.pro_scale || l > 0) && !getenv("PRCNN_TRAIN_FWD_GENERIC");
+                           (!T.pro_scale || l > 0) && !sw_present(SW_TRAIN_FWD_GENERIC);
         if (fastp) {
             if (wide) hipLaunchKernelGGL((train_fwd_kernel<MODE_PLAIN, 2, true>), grid, dim3(MLP_THREADS), 0, s, T);
             else hipLaunchKernelGGL((train_fwd_kernel<MODE_PLAIN, 1, true>), grid, dim3(MLP_THREADS), 0, s, T);
@@ -1450,7 +1450,7 @@ PRCNN_API int prcnn_train_stack_bwd(const prcnn_train_src_t* src, const prcnn_tr
         else if (p.KQ == 2 && p.WK == 1) launch_wgrad<2, 2, 1, 2>(Wg, p, s);
         else if (p.NQ == 1) launch_wgrad<2, 1, 2, 1>(Wg, p, s);
         else if (p.WN == 1) launch_wgrad<2, 2, 2, 1>(Wg, p, s);
-        else if (Wg.lda % 4 == 0 && aligned16(Wg.a) && !getenv("PRCNN_WGRAD_DIRECT")) {
+        else if (Wg.lda % 4 == 0 && aligned16(Wg.a) && !sw_present(SW_WGRAD_DIRECT)) {
             const dim3 wg(p.splits, p.tiles_k, p.tiles_n);
             if (Wg.B.pool_ns == 0) { if (Wg.B.mult) launch_wgrad_lds<0, true>(Wg, wg, s); else launch_wgrad_lds<0, false>(Wg, wg, s); }
             else if (Wg.B.pool_ns > 0) launch_wgrad_lds<1, false>(Wg, wg, s);

@@ -19,6 +19,7 @@
 // prcnn_cpu_nms_batched) operation for operation; results are bit-identical to it.
 #include "iou3d_geom.h"
 #include "lds_sort.h"
+#include "switches.h"
 
 // ====================================================================================================
 // decode_bbox_target
@@ -976,10 +977,9 @@ static int launch_greedy_nms_kind(const char* op, const NmsParams& P, int B, hip
 static int launch_greedy_nms(const char* op, int kind, const NmsParams& P, int B, hipStream_t s) {
     if (kind == PRCNN_NMS_ROTATED) {
         // the prefiltered kernel where its batch fits beside the kept list (it always does for the proposal layer's 70 / 30 and the
-        // detection select's 100); PRCNN_NMS_PREFILTER=0 is the A/B switch (same keep lists), read per call: the tests flip it in-process
-        const char* e = getenv("PRCNN_NMS_PREFILTER");
+        // detection select's 100); PRCNN_NMS_PREFILTER=0 is the A/B switch (same keep lists)
         const size_t lds = greedy_nms_rot_lds_bytes(max(P.post1, P.post2));
-        if ((e == nullptr || atoi(e) != 0) && lds <= LDS_BUDGET) {
+        if (sw_enabled(SW_NMS_PREFILTER) && lds <= LDS_BUDGET) {
             static PrcnnLdsLimit attr_set;
             if (!attr_set.raise((const void*)greedy_nms_rot_kernel, LDS_BUDGET))
                 return prcnn_fail(PRCNN_EHIP, "%s: cannot raise the dynamic LDS limit", op);
@@ -990,9 +990,8 @@ static int launch_greedy_nms(const char* op, int kind, const NmsParams& P, int B
         return launch_greedy_nms_kind<PRCNN_NMS_ROTATED>(op, P, B, s);
     }
     {
-        const char* e = getenv("PRCNN_NMS_PREFILTER");
         const size_t lds = greedy_nms_pre_lds_bytes(max(P.post1, P.post2));
-        if ((e == nullptr || atoi(e) != 0) && lds <= LDS_BUDGET) {
+        if (sw_enabled(SW_NMS_PREFILTER) && lds <= LDS_BUDGET) {
             static PrcnnLdsLimit attr_set;
             if (!attr_set.raise((const void*)greedy_nms_pre_kernel, LDS_BUDGET))
                 return prcnn_fail(PRCNN_EHIP, "%s: cannot raise the dynamic LDS limit", op);

@@ -317,11 +317,11 @@ def test_hoisted_interp_equals_unhoisted_oracle(dev, cpu):
     np.testing.assert_allclose(got_t, want, atol=mlp_tol(want), rtol=0)
 
 
-def test_chain_kernel_variants_are_bit_identical(dev, cpu, monkeypatch):
+def test_chain_kernel_variants_are_bit_identical(dev, cpu):
     """The register-chain has four code paths for the same arithmetic -- generic (bounds-checked), straight-line "fast",
     persistent with LDS-resident weights (opt-in) and the persistent register-weight kernel of SA level 0 -- selected
     by shape and environment.  They must agree bit for bit (same MFMA order, same activation expressions)."""
-    from pointrcnn_amd import ops
+    from pointrcnn_amd import _cabi, ops
     r = np.random.default_rng(33)
     B, N, M = 2, 1500, 70
 
@@ -329,13 +329,8 @@ def test_chain_kernel_variants_are_bit_identical(dev, cpu, monkeypatch):
         outs = {}
         for name, env in (("default", {}), ("generic", {"PRCNN_NO_FAST_CHAIN": "1", "PRCNN_NO_SA0": "1"}),
                           ("persistent", {"PRCNN_PERSISTENT_CHAIN": "1"})):
-            for k in ("PRCNN_NO_FAST_CHAIN", "PRCNN_NO_SA0", "PRCNN_PERSISTENT_CHAIN"):
-                monkeypatch.delenv(k, raising=False)
-            for k, v in env.items():
-                monkeypatch.setenv(k, v)
-            outs[name] = fn().clone()
-        for k in ("PRCNN_NO_FAST_CHAIN", "PRCNN_NO_SA0", "PRCNN_PERSISTENT_CHAIN"):
-            monkeypatch.delenv(k, raising=False)
+            with _cabi.switches(**{"PRCNN_NO_FAST_CHAIN": None, "PRCNN_NO_SA0": None, "PRCNN_PERSISTENT_CHAIN": None, **env}):
+                outs[name] = fn().clone()
         assert torch.equal(outs["default"], outs["generic"]) and torch.equal(outs["default"], outs["persistent"])
         return outs["default"]
 
@@ -375,11 +370,11 @@ def test_chain_kernel_variants_are_bit_identical(dev, cpu, monkeypatch):
         run_all(lambda: ops.mlp_chain_rows(feat, layers))
 
 
-def test_tile_order_remaps_are_bit_identical(dev, monkeypatch):
+def test_tile_order_remaps_are_bit_identical(dev):
     """Workgroup -> tile remaps must not change a byte: the XCD-aware frame order of the interp chain (B % 8 == 0, n % 128 == 0:
     XCD x walks frames x, x+8, ...) and the live-prefix order of segment-skipping launches (tile q of segment s taken by
     workgroup q * nseg + s).  Dead rows are compared only where they are live."""
-    from pointrcnn_amd import ops
+    from pointrcnn_amd import _cabi, ops
     r = np.random.default_rng(44)
     B, n, m = 16, 384, 96                        # 3 tiles per frame, 16 frames: every XCD gets two frames
     unknown, known = T(unit_cloud(B, n, seed=3), dev), T(unit_cloud(B, m, seed=4), dev)
@@ -388,11 +383,10 @@ def test_tile_order_remaps_are_bit_identical(dev, monkeypatch):
     ws, bs = _stack(r, (128, 128), 0.1)
     b0 = T(r.normal(size=(128,)).astype(np.float32), dev)
     l1 = lin(dev, ws[0], bs[0], True)
-    monkeypatch.delenv("PRCNN_NO_XCD_ORDER", raising=False)
-    a = ops.mlp_chain_interp(y, idx3, w3, None, [l1], act_bias=b0).clone()
-    monkeypatch.setenv("PRCNN_NO_XCD_ORDER", "1")
-    b = ops.mlp_chain_interp(y, idx3, w3, None, [l1], act_bias=b0).clone()
-    monkeypatch.delenv("PRCNN_NO_XCD_ORDER", raising=False)
+    with _cabi.switches(PRCNN_NO_XCD_ORDER=None):
+        a = ops.mlp_chain_interp(y, idx3, w3, None, [l1], act_bias=b0).clone()
+    with _cabi.switches(PRCNN_NO_XCD_ORDER="1"):
+        b = ops.mlp_chain_interp(y, idx3, w3, None, [l1], act_bias=b0).clone()
     assert torch.equal(a, b)
     # segment-prefix live rows: 40 segments of 256 rows, live counts from 1 to 256 (both tiles of a segment live or not)
     S, nseg = 256, 40
@@ -797,7 +791,7 @@ def test_split_chain_forms_are_bit_identical(dev, monkeypatch):
     (mlp_chain_p_kernel: hoisted FP0 and the single-channel head).  Same products in the same order: the outputs must be the same
     BITS, on ragged row counts (last tile partly empty, fewer tiles than waves), frames a multiple of 8 (XCD-aware tile order) and
     not, and with a non-finite input row (every form redoes the wave's rows on the fp32 pipe)."""
-    from pointrcnn_amd import ops
+    from pointrcnn_amd import _cabi, ops
     monkeypatch.setattr(ops, "MLP_SPLIT_TERMS", 6)
     r = np.random.default_rng(77)
     w0 = (r.normal(size=(128, 128)) * 0.1).astype(np.float32)
@@ -808,11 +802,8 @@ def test_split_chain_forms_are_bit_identical(dev, monkeypatch):
     def forms(fn):
         outs = []
         for coop, persist in (("0", "0"), ("1", "0"), ("2", "0"), ("1", "1")):
-            monkeypatch.setenv("PRCNN_CHAIN_COOP", coop)
-            monkeypatch.setenv("PRCNN_CHAIN_PERSIST", persist)
-            outs.append(fn().clone())
-        monkeypatch.delenv("PRCNN_CHAIN_COOP")
-        monkeypatch.delenv("PRCNN_CHAIN_PERSIST")
+            with _cabi.switches(PRCNN_CHAIN_COOP=coop, PRCNN_CHAIN_PERSIST=persist):
+                outs.append(fn().clone())
         return outs
 
     for rows in (40000 + 17, 300, 31, 128 * 2048):

@@ -30,13 +30,13 @@ def _nms_sorted(X, thresh, dev):
     return keep.cpu().numpy()[:int(num.cpu()[0])]
 
 
-def _nms_batched_both(boxes3d, sc, thresh, monkeypatch, max_keep=0, rotated=True):
-    from pointrcnn_amd import ops
+def _nms_batched_both(boxes3d, sc, thresh, max_keep=0, rotated=True):
+    from pointrcnn_amd import _cabi, ops
     out = {}
     for flag in ("1", "0"):
-        monkeypatch.setenv("PRCNN_NMS_PREFILTER", flag)
-        k, n = ops.nms_batched(boxes3d, sc, None, thresh, rotated, max_keep=max_keep)
-        out[flag] = (k.cpu().numpy(), n.cpu().numpy())
+        with _cabi.switches(PRCNN_NMS_PREFILTER=flag):
+            k, n = ops.nms_batched(boxes3d, sc, None, thresh, rotated, max_keep=max_keep)
+            out[flag] = (k.cpu().numpy(), n.cpu().numpy())
     return out
 
 
@@ -54,14 +54,14 @@ def test_seed_pair_through_nms_sorted_and_the_dropin(dev, cpu):
     assert n == 1 and int(keep[0]) == 0
 
 
-def test_seed_pair_through_nms_batched(dev, cpu, monkeypatch):
+def test_seed_pair_through_nms_batched(dev, cpu):
     kind, seed, (i, j) = SEED_PAIR_3D_OF
     P = family_boxes3d(kind, seed)[[i, j]][None]
     sc = np.array([[1.0, 0.5]], f)
     assert np.array_equal(_unguarded_keep(cpu, bev(P[0]), 0.1), [0, 1])   # the BEV the kernel computes is collinear (checked, not assumed)
     ok, on = cpu.nms_batched(P, sc, None, 0.1)
     assert on.tolist() == [1] and ok.tolist() == [[0, -1]]
-    for flag, (k, n) in _nms_batched_both(_t(P, dev), _t(sc, dev), 0.1, monkeypatch).items():
+    for flag, (k, n) in _nms_batched_both(_t(P, dev), _t(sc, dev), 0.1).items():
         assert np.array_equal(n, on) and np.array_equal(k, ok), flag
 
 
@@ -80,23 +80,23 @@ def _case(c):
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "-".join(str(v) for v in c))
-def test_family_sets_every_entry_point_equals_the_oracle(dev, cpu, monkeypatch, case):
+def test_family_sets_every_entry_point_equals_the_oracle(dev, cpu, case):
     import oracle
-    from pointrcnn_amd import ops
+    from pointrcnn_amd import _cabi, ops
     X, B3 = _case(case)
     n = X.shape[0]
     sc = np.linspace(1.0, 0.0, n, dtype=f)[None]              # sorted order == row order (no ties)
     for thresh in (0.1, 0.3, 0.8, 0.85, -1.0):
         assert np.array_equal(_nms_sorted(X, thresh, dev), cpu.nms(X, thresh)), thresh
         ok, on = cpu.nms_batched(B3[None], sc, None, thresh)
-        for flag, (k, nk) in _nms_batched_both(_t(B3[None], dev), _t(sc, dev), thresh, monkeypatch).items():
+        for flag, (k, nk) in _nms_batched_both(_t(B3[None], dev), _t(sc, dev), thresh).items():
             assert np.array_equal(nk, on) and np.array_equal(k, ok), (thresh, flag)
         for flag in ("1", "0"):
-            monkeypatch.setenv("PRCNN_NMS_PREFILTER", flag)
-            rois, scores, cnt = ops.proposal_layer(_t(sc, dev), _t(B3[None], dev), (6300, 2700), (70, 30), thresh, rotated=True)
-            o = cpu.proposal_layer(sc, B3[None], (6300, 2700), (70, 30), thresh, "rotated")
-            assert np.array_equal(cnt.cpu().numpy(), o[2]) and np.array_equal(rois.cpu().numpy(), o[0]), (thresh, flag)
-            assert np.array_equal(scores.cpu().numpy(), o[1]), (thresh, flag)
+            with _cabi.switches(PRCNN_NMS_PREFILTER=flag):
+                rois, scores, cnt = ops.proposal_layer(_t(sc, dev), _t(B3[None], dev), (6300, 2700), (70, 30), thresh, rotated=True)
+                o = cpu.proposal_layer(sc, B3[None], (6300, 2700), (70, 30), thresh, "rotated")
+                assert np.array_equal(cnt.cpu().numpy(), o[2]) and np.array_equal(rois.cpu().numpy(), o[0]), (thresh, flag)
+                assert np.array_equal(scores.cpu().numpy(), o[1]), (thresh, flag)
     # the pair kernels: bit for bit
     Xd, Bd = _t(X, dev), _t(B3, dev)
     ov, iou = ops.boxes_overlap_bev(Xd, Xd).cpu().numpy(), ops.boxes_iou_bev(Xd, Xd).cpu().numpy()
@@ -144,24 +144,24 @@ def _scattered(M, seed):
 
 
 @pytest.mark.parametrize("kind,edge", [("rotated", "prefilter"), ("rotated", "chunk"), ("normal", "prefilter"), ("normal", "chunk")])
-def test_nms_batched_on_both_sides_of_each_lds_boundary(dev, cpu, monkeypatch, kind, edge):
+def test_nms_batched_on_both_sides_of_each_lds_boundary(dev, cpu, kind, edge):
     """max_keep at the boundary and one above: the prefiltered kernels fall back to the chunk kernel (same keep lists), the chunk
     kernels refuse with PRCNN_EUNSUPPORTED"""
-    from pointrcnn_amd import ops
+    from pointrcnn_amd import _cabi, ops
     from pointrcnn_amd._cabi import PointOpsError
     mk = _largest_max_keep((kind, edge))
     M = mk + mk // 6 + 64
     boxes, sc = _scattered(M, seed=mk)
     ok_at, on_at = cpu.nms_batched(boxes, sc, None, 0.1, kind, max_keep=mk)
     assert on_at[0] == mk                                       # the kept list really fills up to max_keep
-    for flag, (k, n) in _nms_batched_both(_t(boxes, dev), _t(sc, dev), 0.1, monkeypatch, mk, kind == "rotated").items():
+    for flag, (k, n) in _nms_batched_both(_t(boxes, dev), _t(sc, dev), 0.1, mk, kind == "rotated").items():
         assert np.array_equal(n, on_at) and np.array_equal(k, ok_at), flag
     if edge == "prefilter":
         ok, on = cpu.nms_batched(boxes, sc, None, 0.1, kind, max_keep=mk + 1)
-        for flag, (k, n) in _nms_batched_both(_t(boxes, dev), _t(sc, dev), 0.1, monkeypatch, mk + 1, kind == "rotated").items():
+        for flag, (k, n) in _nms_batched_both(_t(boxes, dev), _t(sc, dev), 0.1, mk + 1, kind == "rotated").items():
             assert np.array_equal(n, on) and np.array_equal(k, ok), flag
     else:
         for flag in ("1", "0"):
-            monkeypatch.setenv("PRCNN_NMS_PREFILTER", flag)
-            with pytest.raises(PointOpsError, match=r"code -3\).*LDS"):
-                ops.nms_batched(_t(boxes, dev), _t(sc, dev), None, 0.1, kind == "rotated", max_keep=mk + 1)
+            with _cabi.switches(PRCNN_NMS_PREFILTER=flag):
+                with pytest.raises(PointOpsError, match=r"code -3\).*LDS"):
+                    ops.nms_batched(_t(boxes, dev), _t(sc, dev), None, 0.1, kind == "rotated", max_keep=mk + 1)

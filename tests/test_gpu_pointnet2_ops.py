@@ -133,24 +133,22 @@ def test_gather_group_interp_forward_exact(dev, cpu):
 
 
 @pytest.mark.parametrize("B,C,m,n", [(4, 64, 1024, 4096), (2, 37, 513, 3000), (8, 256, 4096, 16384), (3, 36, 6000, 12001)])
-def test_three_interpolate_lds_staged_kernel_is_bit_identical(dev, cpu, monkeypatch, B, C, m, n):
+def test_three_interpolate_lds_staged_kernel_is_bit_identical(dev, cpu, B, C, m, n):
     """n >= 2 m with enough (frame, channel group) workgroups: the source rows are staged in LDS (point-major
     three_interp_pm_kernel<8 | 4> when the channel count divides, channel-major three_interp_lds_kernel otherwise /
     PRCNN_INTERP_LAYOUT=rows); bit-equal to the oracle and to the direct kernel (PRCNN_INTERP_DIRECT=1), odd m / ragged
     channel groups included"""
-    from pointrcnn_amd import ops
+    from pointrcnn_amd import _cabi, ops
     r = np.random.default_rng(m + n)
     feat = r.normal(size=(B, C, m)).astype(np.float32)
     i3 = r.integers(0, m, (B, n, 3)).astype(np.int32)
     w3 = r.random((B, n, 3)).astype(np.float32)
-    monkeypatch.delenv("PRCNN_INTERP_DIRECT", raising=False)
-    got = ops.three_interpolate(T(feat, dev), T(i3, dev), T(w3, dev))
-    monkeypatch.setenv("PRCNN_INTERP_DIRECT", "1")
-    direct = ops.three_interpolate(T(feat, dev), T(i3, dev), T(w3, dev))
-    monkeypatch.delenv("PRCNN_INTERP_DIRECT", raising=False)
-    monkeypatch.setenv("PRCNN_INTERP_LAYOUT", "rows")
-    rows = ops.three_interpolate(T(feat, dev), T(i3, dev), T(w3, dev))
-    monkeypatch.delenv("PRCNN_INTERP_LAYOUT", raising=False)
+    with _cabi.switches(PRCNN_INTERP_DIRECT=None):
+        got = ops.three_interpolate(T(feat, dev), T(i3, dev), T(w3, dev))
+    with _cabi.switches(PRCNN_INTERP_DIRECT="1"):
+        direct = ops.three_interpolate(T(feat, dev), T(i3, dev), T(w3, dev))
+    with _cabi.switches(PRCNN_INTERP_DIRECT=None, PRCNN_INTERP_LAYOUT="rows"):
+        rows = ops.three_interpolate(T(feat, dev), T(i3, dev), T(w3, dev))
     assert torch.equal(got, direct) and torch.equal(rows, direct)
     if B * C * n <= 4_000_000:
         assert np.array_equal(got.cpu().numpy(), cpu.three_interp(feat, i3, w3))
@@ -198,18 +196,19 @@ def test_op_argument_errors(dev):
 
 @pytest.mark.parametrize("pruned", [True, "one-level", "batch", False])
 @pytest.mark.parametrize("B,N,npoint", [(2, 16384, 2048), (2, 12000, 1500), (2, 4096, 1024), (1, 8192, 700), (2, 5000, 333), (1, 2049, 64)])
-def test_fps_pruned_and_plain_variants_are_bit_identical(dev, cpu, monkeypatch, B, N, npoint, pruned):
+def test_fps_pruned_and_plain_variants_are_bit_identical(dev, cpu, B, N, npoint, pruned):
     """the FPS kernels for 2048 < N <= 16384 -- the spatially pruned ones (Morton pre-sort + exact bounding-box skip, csrc/fps.hip:
     two-level for N > 8192, the default, and one-level, PRCNN_FPS_SLOTS=0) and the plain register-resident one
     (PRCNN_FPS_PRUNED=0) -- return exactly the oracle's indices, on distinct points, duplicated points (original-index
     tie-break) and lattices"""
-    from pointrcnn_amd import ops
+    from pointrcnn_amd import _cabi, ops
     old = ops.FPS_PRUNED
     ops.FPS_PRUNED = bool(pruned)
+    env = {}
     if pruned == "one-level":
-        monkeypatch.setenv("PRCNN_FPS_SLOTS", "0")
+        env["PRCNN_FPS_SLOTS"] = "0"
     if pruned == "batch":                                             # two samples per exchange where the second is provable (opt-in)
-        monkeypatch.setenv("PRCNN_FPS_BATCH", "1")
+        env["PRCNN_FPS_BATCH"] = "1"
     try:
         clouds = [kitti_cloud(B, N, seed=N)]
         dup = clouds[0].copy()
@@ -220,23 +219,25 @@ def test_fps_pruned_and_plain_variants_are_bit_identical(dev, cpu, monkeypatch, 
         for xyz in clouds:
             if xyz is None:
                 continue
-            got = ops.furthest_point_sample(T(xyz, dev), npoint).cpu().numpy()
+            with _cabi.switches(**env):
+                got = ops.furthest_point_sample(T(xyz, dev), npoint).cpu().numpy()
             assert np.array_equal(got, cpu.fps(xyz, npoint))
     finally:
         ops.FPS_PRUNED = old
 
 
 @pytest.mark.parametrize("busy", [False, True, "batch"])
-def test_fps_slot_masks_on_ties_in_every_slot_alone_and_under_co_resident_waves(dev, cpu, busy, monkeypatch):
+def test_fps_slot_masks_on_ties_in_every_slot_alone_and_under_co_resident_waves(dev, cpu, busy):
     """round-5 advisor finding: the hand-scheduled slot-mask blocks (csrc/fps.hip WaveMaxEq / wave_max_eq2_16) read a compare's
     SGPR pair from a v_addc the hazard recognizer cannot see.  Directed at them: clouds on which the maximum is held by SEVERAL slots of
     one lane in every sample -- each point 16 / 8 / 2 times (equal Morton codes: the copies are neighbours in the sorted order, so they
     sit in the slots of one lane or of adjacent lanes, 0/1/8/9 included) and a 32 x 16 x 32 lattice -- on the 16-slot kernel (16384 -> 4096), the 4-slot kernel
     (4096 -> 1024) and the single-wave kernels, once on an idle chip and once while matrix products from another stream share the CUs
     (the VALU co-issue conditions differ).  Indices must equal the oracle's (ties -> lowest original index)."""
-    from pointrcnn_amd import ops
+    from pointrcnn_amd import _cabi, ops
+    env = {}
     if busy == "batch":                      # the same clouds through fps_batch_kernel (ties fail its proof: one sample per round)
-        monkeypatch.setenv("PRCNN_FPS_BATCH", "1")
+        env["PRCNN_FPS_BATCH"] = "1"
         busy = False
     side = torch.cuda.Stream()
     a = torch.randn(4096, 4096, device=dev)
@@ -261,7 +262,8 @@ def test_fps_slot_masks_on_ties_in_every_slot_alone_and_under_co_resident_waves(
         want = cpu.fps(xyz, npoint)
         if busy:
             spin()
-        got = ops.furthest_point_sample(T(xyz, dev), npoint).cpu().numpy()
+        with _cabi.switches(**env):
+            got = ops.furthest_point_sample(T(xyz, dev), npoint).cpu().numpy()
         assert np.array_equal(got, want), (xyz.shape, npoint, int((got != want).sum()))
     torch.cuda.synchronize()
     del stop
@@ -295,11 +297,11 @@ def test_backward_kernels_at_training_shapes(dev, cpu):
 
 
 @pytest.mark.parametrize("B,C,N,M,ns", [(2, 96, 4096, 1024, 32), (3, 16, 1000, 260, 16), (1, 8, 64, 64, 4), (2, 24, 4096, 512, 64)])
-def test_grouping_lds_staged_kernel_is_exact(dev, cpu, monkeypatch, B, C, N, M, ns):
+def test_grouping_lds_staged_kernel_is_exact(dev, cpu, B, C, N, M, ns):
     """round 6: grouping_operation with the source rows staged point-major in LDS (C a multiple of 8, at least four outputs per source
     point) == the plain gather kernel (PRCNN_GATHER_DIRECT=1) == the oracle, element for element (pure copies); output slices per
     workgroup when B x C / 8 alone would not fill the chip"""
-    from pointrcnn_amd import ops
+    from pointrcnn_amd import _cabi, ops
     r = np.random.default_rng(B * 1000 + C)
     feat = r.normal(size=(B, C, N)).astype(np.float32)
     idx = r.integers(0, N, size=(B, M, ns)).astype(np.int32)
@@ -308,5 +310,5 @@ def test_grouping_lds_staged_kernel_is_exact(dev, cpu, monkeypatch, B, C, N, M, 
     want = cpu.group(feat, idx)
     got = ops.group(T(feat, dev), T(idx, dev)).cpu().numpy()
     assert np.array_equal(got, want)
-    monkeypatch.setenv("PRCNN_GATHER_DIRECT", "1")
-    assert np.array_equal(ops.group(T(feat, dev), T(idx, dev)).cpu().numpy(), want)
+    with _cabi.switches(PRCNN_GATHER_DIRECT="1"):
+        assert np.array_equal(ops.group(T(feat, dev), T(idx, dev)).cpu().numpy(), want)

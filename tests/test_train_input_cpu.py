@@ -114,4 +114,4 @@ def test_header_and_binding_declare_the_sampling_entry_points():
         names = re.findall(r"^(?:int|size_t)\s+(prcnn_\w+)\s*\(", f.read(), flags=re.M)
     for n in ("prcnn_corner_iou3d", "prcnn_gt_aug_sample"):
         assert n in names and n in _cabi.SIGNATURES
-    assert _cabi.REQUIRED_ABI == 10
+    assert _cabi.REQUIRED_ABI == 12

@@ -172,7 +172,7 @@ def test_header_and_bindings_declare_the_entry_points():
         assert name in _cabi.SIGNATURES, name
     m = re.search(r"int prcnn_train_scene_prepare\((.*?)\);", hdr, re.S)
     assert len(m.group(1).split(",")) == len(_cabi.SIGNATURES["prcnn_train_scene_prepare"][1])
-    assert re.search(r"prcnn_abi_version\(void\)\s*\{\s*return 11;", open(os.path.join(REPO, "pointrcnn_amd", "csrc", "cabi_common.hip")).read())
+    assert re.search(r"prcnn_abi_version\(void\)\s*\{\s*return 12;", open(os.path.join(REPO, "pointrcnn_amd", "csrc", "cabi_common.hip")).read())
 
 
 def test_stream_table_lists_the_augmentation_streams():

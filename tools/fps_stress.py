@@ -2,13 +2,12 @@
 kernel take data-dependent paths: a candidate that survives an update, a second sample proved or not) -- uniform, LiDAR-like, saturated,
 duplicated and lattice clouds, 16 384 -> 4 096, 12 000 -> 3 000, 4 096 -> 1 024, 8 192 -> 2 048.
     python tools/fps_stress.py [frames per kind, default 24]"""
-import os
 import sys
 import numpy as np
 import torch
 sys.path.insert(0, ".")
 import oracle
-from pointrcnn_amd import ops, rpn
+from pointrcnn_amd import _cabi, ops, rpn
 
 cpu = oracle.cpu()
 dev = torch.device("cuda:0")
@@ -24,8 +23,8 @@ for kind, gen in (("uniform", rpn.synthetic_clouds), ("lidar", rpn.lidar_like_cl
             xyz = np.ascontiguousarray(cl[:, :N])
             want = cpu.fps(xyz, npoint)
             for batch in ("0", "1"):
-                os.environ["PRCNN_FPS_BATCH"] = batch
-                got = ops.furthest_point_sample(torch.from_numpy(xyz).to(dev), npoint).cpu().numpy()
+                with _cabi.switches(PRCNN_FPS_BATCH=batch):
+                    got = ops.furthest_point_sample(torch.from_numpy(xyz).to(dev), npoint).cpu().numpy()
                 ok = np.array_equal(got, want)
                 bad += 0 if ok else 1
                 print("%-18s %5d -> %4d  batch=%s  frames %3d  %s" % (tag, N, npoint, batch, xyz.shape[0], "identical" if ok else "MISMATCH in %d frames" % int((got != want).any(1).sum())), flush=True)
