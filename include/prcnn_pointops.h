@@ -58,6 +58,8 @@ typedef void* prcnn_stream_t; /* hipStream_t */
 #define PRCNN_EUNSUPPORTED (-3) /* valid request this build has no kernel for */
 
 int prcnn_abi_version(void);   /* 12: + prcnn_switches_reload, prcnn_switch_get (the PRCNN_* kernel switches are read once, through one table);
+                                 * still 12 (additive, no caller breaks): + prcnn_gt_database_workspace_bytes, prcnn_gt_database_count,
+                                 * prcnn_gt_database_fill (the GT-augmentation database built on the device);
                                  * 11: + prcnn_train_scene_workspace_bytes, prcnn_train_scene_prepare (the RPN training batch on the device);
                                  * 10: + prcnn_corner_iou3d, prcnn_gt_aug_sample (GT-augmentation sampling loop on the device);
                                  * 9: + prcnn_fps_mode, prcnn_ball_query_arith, prcnn_three_nn_arith (comparison mode: the squared distance as nvcc contracts the
@@ -623,6 +625,32 @@ int prcnn_train_scene_prepare(const float* raw, const int64_t* offsets, int B, i
                               const double* aug_cfg, float* out_xyz, float* out_input, float* out_features, int32_t* out_src,
                               int32_t* nvalid, int32_t* status, float* out_gt_boxes3d, int32_t* out_num_gt, double* aug,
                               void* workspace, size_t workspace_bytes, prcnn_stream_t stream);
+
+/* ======================================================================================================
+ * GT-augmentation database builder (gt_database.hip).  tools/generate_gt_database.py:50-84 for a batch of frames: the rect-camera
+ * points of the WHOLE scan (no FOV, image or PC_AREA_SCOPE filter) that lie in each labelled object's box, in ascending raw index,
+ * each with its intensity and raw index.  rect = the canonical lidar -> rect of prcnn_scene_prepare; membership = the test of
+ * prcnn_pts_in_boxes3d (roipool3d.cpp:82-95, 10 m gate included).  A point inside two boxes belongs to both objects.
+ *   raw, offsets, max_points_per_frame, calib   as prcnn_scene_prepare (of calib only M is read)
+ *   boxes3d (B, G, 7) [x y z h w l ry], num_boxes (B) i32: the frame's kept labels; G <= 128
+ * The output size depends on the data, so the caller allocates between two calls that share one workspace (its content must
+ * survive from the count to the fill):
+ *   prcnn_gt_database_count  -> npts (B, G) i32, zero at and beyond num_boxes[b]; per-tile hit counts go to the workspace.
+ *   prcnn_gt_database_fill   <- obj_offsets (B * G + 1) i64 = the exclusive scan of npts (objects frame-major, then in label order),
+ *                               total_out = obj_offsets[B * G] = the rows the three output buffers hold
+ *                            -> points (total_out, 3) rect coordinates, intensity (total_out), src (total_out) i32 raw index in the frame.
+ * A row's position is object offset + prefix sums of hit counts (tile, wave, lane), never the order of an atomic append: two runs
+ * give identical bytes.  No row outside [0, total_out) is written, whatever obj_offsets holds.
+ * PRCNN_EINVAL for G > 128, a null pointer, or a workspace smaller than prcnn_gt_database_workspace_bytes.
+ * ====================================================================================================== */
+size_t prcnn_gt_database_workspace_bytes(int64_t max_points_per_frame, int B, int G);
+int prcnn_gt_database_count(const float* raw, const int64_t* offsets, int B, int64_t total_points, int max_points_per_frame,
+                            const float* calib, const float* boxes3d, const int32_t* num_boxes, int G, int32_t* npts,
+                            void* workspace, size_t workspace_bytes, prcnn_stream_t stream);
+int prcnn_gt_database_fill(const float* raw, const int64_t* offsets, int B, int64_t total_points, int max_points_per_frame,
+                           const float* calib, const float* boxes3d, const int32_t* num_boxes, int G, const int64_t* obj_offsets,
+                           int64_t total_out, float* points, float* intensity, int32_t* src, void* workspace,
+                           size_t workspace_bytes, prcnn_stream_t stream);
 
 /* ======================================================================================================
  * Training-mode SharedMLP (csrc/mlp_train.h) -- BASELINE config 4, `train_rcnn.py --train_mode rpn`.

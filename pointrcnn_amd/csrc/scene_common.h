@@ -12,12 +12,17 @@ constexpr unsigned SCENE_FAR = 1u << 30;
 
 struct RectPoint { float x, y, z; bool valid; };
 
+// lidar -> rect (calibration.py:51-59) under the canonical contract; c = M, 4x3 row-major.  Shared with gt_database.hip.
+__device__ __forceinline__ void scene_rect(const float4 p, const float* __restrict__ c, float& x, float& y, float& z) {
+    x = ((p.x * c[0] + p.y * c[3]) + p.z * c[6]) + c[9];
+    y = ((p.x * c[1] + p.y * c[4]) + p.z * c[7]) + c[10];
+    z = ((p.x * c[2] + p.y * c[5]) + p.z * c[8]) + c[11];
+}
+
 __device__ __forceinline__ RectPoint scene_project(const float4 p, const float* __restrict__ c, int H, int W, const double* scope,
                                                    int use_scope) {
     RectPoint r;
-    r.x = ((p.x * c[0] + p.y * c[3]) + p.z * c[6]) + c[9];
-    r.y = ((p.x * c[1] + p.y * c[4]) + p.z * c[7]) + c[10];
-    r.z = ((p.x * c[2] + p.y * c[5]) + p.z * c[8]) + c[11];
+    scene_rect(p, c, r.x, r.y, r.z);
     const float* P = c + 12;
     const float h0 = ((r.x * P[0] + r.y * P[1]) + r.z * P[2]) + P[3];
     const float h1 = ((r.x * P[4] + r.y * P[5]) + r.z * P[6]) + P[7];

@@ -139,12 +139,59 @@ def gt_aug_edit_scene(pts_rect, pts_intensity, accepted_boxes3d, new_pts_list, n
     return out_pts[0, :n].cpu().numpy(), out_int[0, :n].cpu().numpy()
 
 
+# tools/generate_gt_database.py:22-29: the label classes each --class_name keeps
+GT_DATABASE_CLASSES = {"Car": ("Car",), "People": ("Pedestrian", "Cyclist"), "Pedestrian": ("Pedestrian",), "Cyclist": ("Cyclist",)}
+
+
+def read_label_lines(lines):
+    """KITTI training labels (label_2 lines, field order of lib/utils/object3d.py:12-30) as plain arrays, one row per line:
+    cls_type (K,) str, truncation / occlusion / alpha (K,) f64, box2d (K,4) f32, boxes3d (K,7) f32 [x, y, z, h, w, l, ry] as
+    generate_gt_database.py:63-66 forms its rows (every field rounded from the parsed double), score (K,) f64 (-1 without a 16th
+    field) and level (K,) i32: 1 Easy, 2 Moderate, 3 Hard, 4 UnKnown by the rule of object3d.py:31-45 (2-D height from the fp32
+    box2d, truncation, occlusion)."""
+    rows = [ln.strip().split(" ") for ln in lines if ln.strip()]
+    K = len(rows)
+    num = np.array([[float(v) for v in r[1:15]] for r in rows], np.float64).reshape(K, 14)
+    box2d = num[:, 3:7].astype(np.float32)
+    trunc, occ = num[:, 0], num[:, 1]
+    height = box2d[:, 3].astype(np.float64) - box2d[:, 1].astype(np.float64) + 1
+    level = np.full(K, 4, np.int32)
+    level[(height >= 25) & (trunc <= 0.5) & (occ <= 2)] = 3
+    level[(height >= 25) & (trunc <= 0.3) & (occ <= 1)] = 2
+    level[(height >= 40) & (trunc <= 0.15) & (occ <= 0)] = 1
+    return {"cls_type": np.array([r[0] for r in rows], dtype=np.str_).reshape(K), "truncation": trunc.copy(), "occlusion": occ.copy(),
+            "alpha": num[:, 2].copy(), "box2d": box2d, "boxes3d": num[:, [10, 11, 12, 7, 8, 9, 13]].astype(np.float32),
+            "score": np.array([float(r[15]) if len(r) == 16 else -1.0 for r in rows], np.float64), "level": level}
+
+
+def lidar_to_rect_host(pts_lidar, M):
+    """The canonical lidar -> rect of csrc/scene.hip's contract in numpy: fp32, every operation rounded on its own, left to
+    right (elementwise numpy arithmetic does exactly that).  pts_lidar (n, >=3), M (4,3) fp32 -> (n,3) fp32"""
+    p = np.ascontiguousarray(pts_lidar, np.float32)
+    M = np.asarray(M, np.float32)
+    return np.stack([((p[:, 0] * M[0, c] + p[:, 1] * M[1, c]) + p[:, 2] * M[2, c]) + M[3, c] for c in range(3)], 1)
+
+
+def _gt_objects_host(scan, calib, boxes3d):
+    """one frame of the database on the host: lidar_to_rect_host + the library's host twin of pts_in_boxes3d_cpu
+    -> per box (rect points, intensity, raw index), in raw order"""
+    from . import _cabi
+    rect = np.ascontiguousarray(lidar_to_rect_host(scan, calib.lidar_to_rect_matrix()))
+    boxes3d = np.ascontiguousarray(boxes3d, np.float32).reshape(-1, 7)
+    flags = np.zeros((boxes3d.shape[0], rect.shape[0]), np.int64)
+    _cabi.check(_cabi.lib().prcnn_host_pts_in_boxes3d(rect.ctypes.data, boxes3d.ctypes.data, rect.shape[0], boxes3d.shape[0],
+                                                      flags.ctypes.data), "prcnn_host_pts_in_boxes3d")
+    inten = np.ascontiguousarray(scan[:, 3], np.float32)
+    return [(rect[m == 1], inten[m == 1], np.nonzero(m == 1)[0].astype(np.int32)) for m in flags]
+
+
 class GTDatabase:
     """The GT database of the reference's GT augmentation (generate_gt_database.py:78-84, kitti_rcnn_dataset.py:62-76), packed once
     into device tensors: boxes (D,7), alpha (D,), npts (D,) i32, point offsets (D+1,) i64, points (P,3), intensity (P,); and the
-    easy (> 100 points) / hard id lists of GT_AUG_HARD_RATIO > 0 (in database order, as the reference builds its two lists)."""
+    easy (> 100 points) / hard id lists of GT_AUG_HARD_RATIO > 0 (in database order, as the reference builds its two lists).
+    from_kitti builds it from a KITTI tree (csrc/gt_database.hip), save / load keep it in one .npz of plain arrays."""
 
-    def __init__(self, boxes, alpha, points, intensity, hard_ratio=0.6, device="cuda"):
+    def __init__(self, boxes, alpha, points, intensity, hard_ratio=0.6, device="cuda", sample_id=None, cls_type=None):
         boxes = np.ascontiguousarray(boxes, np.float32).reshape(-1, 7)
         D = boxes.shape[0]
         if len(points) != D or len(intensity) != D or np.asarray(alpha).reshape(-1).shape[0] != D:
@@ -174,6 +221,12 @@ class GTDatabase:
         self.boxes, self.alpha, self.npts = T(boxes), T(np.asarray(alpha, np.float32).reshape(-1)), T(npts)
         self.offsets, self.points, self.intensity = T(off), T(pts), T(inten)
         self.easy_idx, self.hard_idx = T(easy), T(hard)
+        # where every object came from (host arrays; -1 / "" when the caller did not say): from_kitti, save / load, entries
+        self.sample_id = np.full(D, -1, np.int64) if sample_id is None else np.asarray(sample_id, np.int64).reshape(-1)
+        self.cls_type = np.full(D, "", np.str_) if cls_type is None else np.asarray(cls_type, np.str_).reshape(-1)
+        self.src = None                     # (P,) i32 raw index of every point in its frame's scan: from_kitti only, not saved
+        if self.sample_id.shape[0] != D or self.cls_type.shape[0] != D:
+            raise ValueError("GTDatabase: one sample_id and one cls_type per object")
 
     @classmethod
     def from_arrays(cls, boxes, alpha, points, intensity, hard_ratio=0.6, device="cuda"):
@@ -188,6 +241,99 @@ class GTDatabase:
             db = pickle.load(f)
         return cls([d["gt_box3d"] for d in db], [d["obj"].alpha for d in db], [d["points"] for d in db],
                    [d["intensity"] for d in db], hard_ratio, device)
+
+    @classmethod
+    def _from_packed(cls, boxes, alpha, npts, points, intensity, sample_id, cls_type, hard_ratio, device, src=None):
+        cuts = np.cumsum(np.asarray(npts, np.int64))[:-1]
+        D = len(npts)
+        db = cls(boxes, alpha, np.split(np.asarray(points, np.float32).reshape(-1, 3), cuts) if D else [],
+                 np.split(np.asarray(intensity, np.float32).reshape(-1), cuts) if D else [], hard_ratio, device, sample_id, cls_type)
+        if src is not None:
+            db.src = torch.from_numpy(np.ascontiguousarray(src, np.int32)).to(db.points.device)
+        return db
+
+    @classmethod
+    def from_kitti(cls, root_dir, split="train", class_name="Car", hard_ratio=0.6, device="cuda", frames_per_batch=8, backend="device"):
+        """tools/generate_gt_database.py on a KITTI tree (<root_dir>/KITTI/ImageSets/<split>.txt, <root_dir>/KITTI/object/training/
+        {velodyne, calib, label_2}), with no pickle and no Object3d: per frame the labels whose class belongs to class_name ('Car',
+        'People', 'Pedestrian', 'Cyclist'; :22-29) and whose level is Easy, Moderate or Hard (:39-48), and per such object the rect
+        points of the whole scan inside its box, in raw order.  Frames with no such object contribute nothing.
+        backend 'device': frames_per_batch frames per prcnn_gt_database_count / _fill call; 'host': the same result with no GPU
+        (lidar_to_rect_host + the library's host twin of pts_in_boxes3d_cpu)."""
+        if class_name not in GT_DATABASE_CLASSES:
+            raise ValueError("GTDatabase.from_kitti: class_name %r is not one of %s" % (class_name, sorted(GT_DATABASE_CLASSES)))
+        if backend not in ("device", "host"):
+            raise ValueError("GTDatabase.from_kitti: backend %r is not 'device' or 'host'" % (backend,))
+        split_file = os.path.join(root_dir, "KITTI", "ImageSets", split + ".txt")
+        if not os.path.isfile(split_file):
+            raise FileNotFoundError("GTDatabase.from_kitti: no split file %s" % split_file)
+        base = os.path.join(root_dir, "KITTI", "object", "testing" if split == "test" else "training")
+        with open(split_file) as f:
+            frames = [x.strip() for x in f.readlines() if x.strip()]
+        keep_cls = GT_DATABASE_CLASSES[class_name]
+        boxes, alpha, npts, pts, inten, src, sid, ctype = [], [], [], [], [], [], [], []
+        batch = []
+
+        def flush():
+            if not batch:
+                return
+            if backend == "host":
+                for scan, calib, b3 in batch:
+                    for p, v, i in _gt_objects_host(scan, calib, b3):
+                        npts.append(len(p)); pts.append(p); inten.append(v); src.append(i)
+            else:
+                G = max(len(b3) for _, _, b3 in batch)
+                packed = pack_scans([s for s, _, _ in batch], [c for _, c, _ in batch], [(0, 0)] * len(batch))
+                pad = np.zeros((len(batch), G, 7), np.float32)
+                for k, (_, _, b3) in enumerate(batch):
+                    pad[k, :len(b3)] = b3
+                dev = torch.device(device)
+                n, _, p, v, i = ops.gt_database_build(packed["raw"].to(dev), packed["offsets"].to(dev), packed["max_points"], packed["calib"].to(dev),
+                                                      torch.from_numpy(pad).to(dev), torch.tensor([len(b3) for _, _, b3 in batch], dtype=torch.int32, device=dev))
+                n = n.cpu().numpy()
+                for k, (_, _, b3) in enumerate(batch):                    # padded slots hold no point: the rows are in database order
+                    npts.extend(int(c) for c in n[k, :len(b3)])
+                pts.append(p.cpu().numpy()); inten.append(v.cpu().numpy()); src.append(i.cpu().numpy())
+            batch.clear()
+        for fid in frames:
+            with open(os.path.join(base, "label_2", "%06d.txt" % int(fid))) as f:
+                lab = read_label_lines(f.readlines())
+            keep = np.isin(lab["cls_type"], keep_cls) & (lab["level"] <= 3)
+            if not keep.any():
+                continue
+            boxes.append(lab["boxes3d"][keep]); alpha.append(lab["alpha"][keep]); ctype.extend(lab["cls_type"][keep])
+            sid.extend([int(fid)] * int(keep.sum()))
+            batch.append((get_lidar(os.path.join(base, "velodyne", "%06d.bin" % int(fid))),
+                          Calibration(os.path.join(base, "calib", "%06d.txt" % int(fid))), lab["boxes3d"][keep]))
+            if len(batch) >= max(1, int(frames_per_batch)):
+                flush()
+        flush()
+        cat = lambda rows, shape, dt: np.concatenate(rows).astype(dt) if rows else np.zeros(shape, dt)      # noqa: E731
+        return cls._from_packed(cat(boxes, (0, 7), np.float32), cat(alpha, (0,), np.float32), np.asarray(npts, np.int64),
+                                cat(pts, (0, 3), np.float32), cat(inten, (0,), np.float32), sid, ctype, hard_ratio, device,
+                                cat(src, (0,), np.int32))
+
+    def save(self, path):
+        """one .npz of plain arrays (no pickled object): boxes, alpha, npts, points, intensity, sample_id, cls_type"""
+        with open(path, "wb") as f:
+            np.savez(f, boxes=self.boxes.cpu().numpy(), alpha=self.alpha.cpu().numpy(), npts=self.npts.cpu().numpy(),
+                     points=self.points.cpu().numpy(), intensity=self.intensity.cpu().numpy(), sample_id=self.sample_id,
+                     cls_type=self.cls_type)
+
+    @classmethod
+    def load(cls, path, hard_ratio=0.6, device="cuda"):
+        """a file written by save"""
+        with np.load(path, allow_pickle=False) as z:
+            return cls._from_packed(z["boxes"], z["alpha"], z["npts"], z["points"], z["intensity"], z["sample_id"], z["cls_type"],
+                                    hard_ratio, device)
+
+    def entries(self):
+        """the database as generate_gt_database.py:78-84 lists it, without its 'obj': one dict per object with sample_id, cls_type,
+        gt_box3d (7,), points (n,3), intensity (n,) -- host arrays, for comparison and export"""
+        off = self.offsets.cpu().numpy()
+        boxes, pts, inten = self.boxes.cpu().numpy(), self.points.cpu().numpy(), self.intensity.cpu().numpy()
+        return [{"sample_id": int(self.sample_id[k]), "cls_type": str(self.cls_type[k]), "gt_box3d": boxes[k],
+                 "points": pts[off[k]:off[k + 1]], "intensity": inten[off[k]:off[k + 1]]} for k in range(self.size)]
 
     def sample(self, gt_boxes3d, num_gt, planes, extra_num=15, rand_num=True, apply_prob=1.0, area_scope=PC_AREA_SCOPE,
                try_times=100, max_accept=16, seed=0):

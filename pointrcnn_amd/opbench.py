@@ -111,6 +111,28 @@ def _train_scene_device(prep, t, max_points, seed):
     return ops.rpn_labels(out["pts_rect"], out["gt_boxes3d"], out["num_gt"])
 
 
+def gt_database_row(dev, B=8, n_raw=120000, nbox=8):
+    """The GT-database builder (kitti_input.GTDatabase.from_kitti's device pass) at one KITTI-sized batch: count, scan, the host read
+    of the total, fill.  Next to its time the traffic floor: the raw scans read twice (once per pass) plus the outputs written."""
+    import numpy as np
+    from . import kitti_input
+    r = np.random.default_rng(17)
+    calib = kitti_input.Calibration.from_text(kitti_input.KITTI_CALIB_TXT)
+    scans = [kitti_input.synthetic_scan(n_raw, seed=300 + b) for b in range(B)]
+    boxes = np.zeros((B, nbox, 7), np.float32)
+    for b, sc in enumerate(scans):                                   # car-sized boxes on scan points in front of the camera
+        rect = kitti_input.lidar_to_rect_host(sc, calib.lidar_to_rect_matrix())
+        c = rect[r.choice(np.nonzero((rect[:, 2] > 5) & (rect[:, 2] < 40) & (np.abs(rect[:, 0]) < 20))[0], nbox)]
+        boxes[b] = np.concatenate([c[:, :1], c[:, 1:2] + 0.8, c[:, 2:3], np.tile([[1.6, 1.7, 4.0]], (nbox, 1)), r.uniform(-3.14, 3.14, (nbox, 1))], 1)
+    pk = kitti_input.pack_scans(scans, [calib] * B, [(375, 1242)] * B, pin=False)
+    raw, off, cal = pk["raw"].to(dev), pk["offsets"].to(dev), pk["calib"].to(dev)
+    bx, nb = torch.from_numpy(boxes).to(dev), torch.full((B,), nbox, dtype=torch.int32, device=dev)
+    P = ops.gt_database_build(raw, off, pk["max_points"], cal, bx, nb)[2].shape[0]
+    emit("gt_database_build", "B%d x %d raw points x %d boxes (%d points kept; includes the host read of the total)" % (B, n_raw, nbox, P),
+         timeit(lambda: ops.gt_database_build(raw, off, pk["max_points"], cal, bx, nb)),
+         bytes=2 * raw.numel() * 4 + P * 20 + B * nbox * 4, kernels=[("gtdb_kernel", 0), ("gtdb_scan_kernel", 0)])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
@@ -212,6 +234,9 @@ def main():
 
     # ---- the RPN training batch from raw scans (kitti_input.TrainScenePreparer) next to the separate passes
     train_scene_rows(dev, B=4 if args.quick else 16)
+
+    # ---- the GT-augmentation database from raw scans and labels (kitti_input.GTDatabase.from_kitti)
+    gt_database_row(dev)
 
     # ---- NMS (default RPN path: normal, 6300 boxes, thr 0.8) and rotated
     c = torch.rand(6300, 2, generator=g) * torch.tensor([80.0, 70.0])

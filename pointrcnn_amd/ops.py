@@ -1093,3 +1093,42 @@ def train_scene_prepare(raw, offsets, max_points_per_frame, calib, img_hw, scope
         _p(out_ng), _p(aug), _p(ws), ws.numel(), _stream()), "prcnn_train_scene_prepare")
     return {"pts_rect": xyz, "pts_input": pin if use_intensity else xyz, "pts_features": feat.unsqueeze(-1), "gt_boxes3d": out_gt,
             "num_gt": out_ng, "src": src, "nvalid": nvalid, "status": status, "aug": aug}
+
+
+# ---------------------------------------------------------------------------------------------------------
+# GT-augmentation database builder (csrc/gt_database.hip)
+# ---------------------------------------------------------------------------------------------------------
+def gt_database_build(raw, offsets, max_points_per_frame, calib, boxes3d, num_boxes):
+    """raw (total,4) f32, offsets (B+1) i64, calib (B,24) f32 as scene_prepare; boxes3d (B,G,7) f32 + num_boxes (B) i32: the kept
+    labels of every frame (G <= 128) -- all on the device.
+    -> npts (B,G) i32, offsets (B*G+1) i64 (exclusive scan of npts: objects frame-major, then label order), points (P,3) rect
+    coordinates, intensity (P), src (P) i32 raw index in the frame; each object's points in ascending raw index
+    [tools/generate_gt_database.py:50-84 for a batch of frames; see prcnn_gt_database_count / prcnn_gt_database_fill].
+    One host read (P) between the two passes."""
+    _chk(raw, "raw", ndim=2)
+    _chk(calib, "calib", ndim=2)
+    _chk(boxes3d, "boxes3d", ndim=3)
+    _chk(num_boxes, "num_boxes", _INT, 1)
+    if offsets.dtype != torch.int64 or not offsets.is_contiguous() or offsets.device != raw.device:
+        raise RuntimeError("offsets must be a contiguous int64 tensor on the device of raw")
+    B, total, dev = offsets.shape[0] - 1, raw.shape[0], raw.device
+    G = boxes3d.shape[1]
+    if raw.shape[1] != 4 or calib.shape[1] != 24 or calib.shape[0] != B:
+        raise RuntimeError("expected raw (total,4), calib (B,24)")
+    if tuple(boxes3d.shape) != (B, G, 7) or num_boxes.shape[0] != B:
+        raise ValueError("gt_database_build: boxes3d must be (%d, G, 7), num_boxes (%d,)" % (B, B))
+    L = _cabi.lib()
+    mp = int(max_points_per_frame)
+    ws = torch.empty((int(L.prcnn_gt_database_workspace_bytes(mp, B, G)),), dtype=torch.uint8, device=dev)
+    npts = torch.empty((B, G), dtype=_INT, device=dev)
+    _cabi.check(L.prcnn_gt_database_count(_p(raw), _p(offsets), B, total, mp, _p(calib), _p(boxes3d), _p(num_boxes), G, _p(npts), _p(ws),
+                                          ws.numel(), _stream()), "prcnn_gt_database_count")
+    off = torch.zeros((B * G + 1,), dtype=torch.int64, device=dev)
+    off[1:] = torch.cumsum(npts.reshape(-1), 0, dtype=torch.int64)
+    P = int(off[-1])                                    # the one host read: the outputs are sized by the data
+    points = torch.empty((P, 3), dtype=_F32, device=dev)
+    inten = torch.empty((P,), dtype=_F32, device=dev)
+    src = torch.empty((P,), dtype=_INT, device=dev)
+    _cabi.check(L.prcnn_gt_database_fill(_p(raw), _p(offsets), B, total, mp, _p(calib), _p(boxes3d), _p(num_boxes), G, _p(off), P, _p(points),
+                                         _p(inten), _p(src), _p(ws), ws.numel(), _stream()), "prcnn_gt_database_fill")
+    return npts, off, points, inten, src
