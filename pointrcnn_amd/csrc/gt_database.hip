@@ -152,13 +152,11 @@ PRCNN_API size_t prcnn_gt_database_workspace_bytes(int64_t max_points_per_frame,
 static int gtdb_common(const char* who, GtdbParams& P, const float* raw, const int64_t* offsets, int B, int64_t total_points,
                        int max_points_per_frame, const float* calib, const float* boxes3d, const int32_t* num_boxes, int G, void* workspace,
                        size_t workspace_bytes) {
-    PRCNN_REQUIRE(B >= 0 && B <= 65535 && total_points >= 0 && max_points_per_frame >= 0, "%s: bad shape B=%d total=%ld", who, B, (long)total_points);
+    PRCNN_REQUIRE(B <= 65535, "%s: bad shape B=%d total=%ld", who, B, (long)total_points);
     PRCNN_REQUIRE(G >= 0 && G <= GTDB_MAX_BOXES, "%s: G=%d (at most %d boxes per frame: their constants are LDS-resident)", who, G, GTDB_MAX_BOXES);
-    if (B == 0 || G == 0) return PRCNN_OK;
-    PRCNN_REQUIRE(offsets && calib && boxes3d && num_boxes, "%s: null pointer", who);
-    PRCNN_REQUIRE(total_points == 0 || raw, "%s: null raw points", who);
-    PRCNN_REQUIRE(((uintptr_t)raw % 16) == 0, "%s: raw points must be 16-byte aligned", who);
-    PRCNN_REQUIRE((long)max_points_per_frame < (1L << 31) - GTDB_THREADS, "%s: frame too large", who);
+    const int rc = scene_check_frames(who, raw, offsets, B, total_points, max_points_per_frame, calib, 0, GTDB_THREADS, G == 0);
+    if (rc != PRCNN_OK || B == 0 || G == 0) return rc;
+    PRCNN_REQUIRE(boxes3d && num_boxes, "%s: null pointer", who);
     PRCNN_REQUIRE(workspace && ((uintptr_t)workspace % 4) == 0 && workspace_bytes >= prcnn_gt_database_workspace_bytes(max_points_per_frame, B, G),
                   "%s: workspace too small", who);
     P.raw = reinterpret_cast<const float4*>(raw); P.off = offsets; P.calib = calib; P.boxes = boxes3d; P.num_boxes = num_boxes;

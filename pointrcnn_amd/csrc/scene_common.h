@@ -1,5 +1,11 @@
-// scene_common.h -- what the two input builders share (scene.hip: inference branch, train_scene.hip: training branch): the
-// lidar -> rect -> image projection with get_valid_flag, and the npoints draw (radix select, ties, LDS bitonic shuffle).
+// scene_common.h -- the one home of what the passes over raw velodyne frames share.  Users: scene.hip (inference input),
+// train_scene.hip (RPN training batch), gt_database.hip (GT-augmentation database: the rect transform and the frame checks).
+// A new pass takes its prelude from here:
+//   device  SceneFrames (head of the kernel params), scene_rect / scene_project (lidar -> rect -> image, get_valid_flag),
+//           scene_append (a block's valid points -> the frame's candidate list), SceneLds + scene_select_sort (the npoints draw:
+//           radix select, ties, LDS bitonic shuffle), scene_empty_frame (the rows of a frame without candidates);
+//   host    scene_check_frames, scene_fill_frames (scope, NP, the counters | list workspace), scene_reset_counters,
+//           scene_launch_sample -- each takes the entry point's name (`who`) for its messages.
 // The arithmetic contract and the random streams are stated in scene.hip's header comment.
 #pragma once
 #include "lds_sort.h"
@@ -9,10 +15,27 @@ constexpr int SCENE_THREADS = 1024;
 constexpr int SCENE_MAX_TIES = 1024;
 constexpr unsigned SCENE_FAR = 1u << 30;
 
+// head of the kernel params of a pass that draws npoints of every frame: SceneParams and TrainSceneParams derive from it
+struct SceneFrames {
+    const float4* raw;          // (total, 4) x y z intensity, lidar frame
+    const int64_t* off;         // (B+1) first raw point of every frame
+    const float* calib;         // (B, 24): M (4x3 row-major), P2 (3x4 row-major)
+    const int32_t* img_hw;      // (B, 2) image height, width
+    double scope[6];            // x0 x1 y0 y1 z0 z1 (PC_AREA_SCOPE)
+    int use_scope;
+    int B, npoints, NP;         // NP: npoints rounded up to a power of two >= 16, what the shuffle sorts
+    unsigned seed;
+    uint2* list;                // candidate entries (class | 30-bit key, identity); where frame b starts is the pass's own layout
+    int32_t* counters;          // (B, 2) candidates, far ones -- zeroed by scene_reset_counters
+    float* out_xyz;             // (B, npoints, 3)
+    int32_t* out_src;           // (B, npoints) identity of every output point
+    int32_t* nvalid;            // (B)
+    int32_t* status;            // (B) 0 ok, 1 outside the reference's domain (it raises), 2 no valid point
+};
 
 struct RectPoint { float x, y, z; bool valid; };
 
-// lidar -> rect (calibration.py:51-59) under the canonical contract; c = M, 4x3 row-major.  Shared with gt_database.hip.
+// lidar -> rect (calibration.py:51-59) under the canonical contract; c = M, 4x3 row-major
 __device__ __forceinline__ void scene_rect(const float4 p, const float* __restrict__ c, float& x, float& y, float& z) {
     x = ((p.x * c[0] + p.y * c[3]) + p.z * c[6]) + c[9];
     y = ((p.x * c[1] + p.y * c[4]) + p.z * c[7]) + c[10];
@@ -36,6 +59,39 @@ __device__ __forceinline__ RectPoint scene_project(const float4 p, const float* 
     return r;
 }
 
+// block-wide (SCENE_THREADS threads, one point i of frame b each): the valid points are appended, unordered, to the frame's
+// candidate list as (far bit | 30-bit draw key, i), with one atomic per block on each of the frame's two counters
+__device__ __forceinline__ void scene_append(bool valid, bool far, int i, uint2* list, int32_t* counters_b, unsigned seed, int b) {
+    __shared__ int wv[SCENE_THREADS / 64], wf[SCENE_THREADS / 64];
+    __shared__ int base;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned long long bv = __ballot(valid), bf = __ballot(far);
+    if (lane == 0) { wv[wave] = (int)__popcll(bv); wf[wave] = (int)__popcll(bf); }
+    __syncthreads();
+    if (tid == 0) {
+        int tv = 0, tf = 0;
+        for (int w = 0; w < SCENE_THREADS / 64; w++) { tv += wv[w]; tf += wf[w]; }
+        base = tv > 0 ? atomicAdd(counters_b, tv) : 0;
+        if (tf > 0) atomicAdd(counters_b + 1, tf);
+    }
+    __syncthreads();
+    if (valid) {
+        int pos = base + (int)__popcll(bv & ((1ULL << lane) - 1ULL));
+        for (int w = 0; w < wave; w++) pos += wv[w];
+        const unsigned key = scene_rand(seed, 0u, (unsigned)b, (unsigned)i) >> 2;
+        list[pos] = make_uint2(key | (far ? SCENE_FAR : 0u), (unsigned)i);
+    }
+}
+
+// the static LDS of the draw; a sample kernel declares one, __shared__, next to the dynamic `keys`
+struct SceneLds {
+    int hist[1024];
+    int wsum[SCENE_THREADS / 64];
+    int sel[2];
+    unsigned ties[SCENE_MAX_TIES];
+    int nties, nsel;
+};
+
 // block-wide: given this thread's histogram bin count c (1024 bins = 1024 threads), find the bin where the running count
 // crosses `want` (0-based rank): returns the bin through sel[0] and the rank inside that bin through sel[1]
 __device__ __forceinline__ void scene_pick_bin(int c, int want, int* wsum, int* sel) {
@@ -55,14 +111,14 @@ __device__ __forceinline__ void scene_pick_bin(int c, int want, int* wsum, int* 
     __syncthreads();
 }
 
-
-// block-wide (SCENE_THREADS threads): the draw and the shuffle of one frame.  L holds the frame's n candidates (f of them far) as
-// (class | 30-bit key, identity); afterwards keys[lds_phys(0 .. total-1)] hold (shuffle key << 32 | identity) in output order.
-// *nties and *nsel must have been zeroed by one thread (a barrier inside orders that write).  -> (total, status)
+// block-wide (SCENE_THREADS threads): the draw and the shuffle of one frame.  L holds the frame's n > 0 candidates (f of them far)
+// as (class | 30-bit key, identity); afterwards keys[lds_phys(0 .. total-1)] hold (shuffle key << 32 | identity) in output order.
+// -> (total, status)
 struct SceneSel { int total, status; };
 __device__ __forceinline__ SceneSel scene_select_sort(const uint2* __restrict__ L, int n, int f, int np, int NP, unsigned seed, unsigned b,
-                                                      u64* keys, int* hist, int* wsum, int* sel, unsigned* ties, int* nties, int* nsel) {
+                                                      u64* keys, SceneLds& S) {
     const int tid = threadIdx.x;
+    if (tid == 0) { S.nties = 0; S.nsel = 0; }           // ordered before their first use by the barriers below
     // what to draw: k candidates with the smallest keys; far points are outside the draw (always kept) when more valid
     // points than npoints exist, inside it otherwise (top-up from ALL valid points, kitti_rcnn_dataset.py:299-303)
     int st = 0, k;
@@ -85,18 +141,18 @@ __device__ __forceinline__ SceneSel scene_select_sort(const uint2* __restrict__ 
         int want = k - 1;
         for (int pass = 0; pass < 3; pass++) {
             const int shift = 20 - 10 * pass;
-            hist[tid] = 0;
+            S.hist[tid] = 0;
             __syncthreads();
             for (int e = tid; e < n; e += SCENE_THREADS) {
                 const unsigned code = L[e].x;
                 if (keep_far && (code & SCENE_FAR)) continue;
                 const unsigned key = code & (SCENE_FAR - 1u);
-                if (pass == 0 || (key >> (shift + 10)) == prefix) atomicAdd(&hist[(key >> shift) & 1023u], 1);
+                if (pass == 0 || (key >> (shift + 10)) == prefix) atomicAdd(&S.hist[(key >> shift) & 1023u], 1);
             }
             __syncthreads();
-            scene_pick_bin(hist[tid], want, wsum, sel);
-            prefix = (prefix << 10) | (unsigned)sel[0];
-            want = sel[1];
+            scene_pick_bin(S.hist[tid], want, S.wsum, S.sel);
+            prefix = (prefix << 10) | (unsigned)S.sel[0];
+            want = S.sel[1];
             __syncthreads();
         }
         T = prefix;
@@ -110,13 +166,13 @@ __device__ __forceinline__ SceneSel scene_select_sort(const uint2* __restrict__ 
             const uint2 it = L[e];
             if (keep_far && (it.x & SCENE_FAR)) continue;
             if ((it.x & (SCENE_FAR - 1u)) == T) {
-                const int p = atomicAdd(nties, 1);
-                if (p < SCENE_MAX_TIES) ties[p] = it.y;
+                const int p = atomicAdd(&S.nties, 1);
+                if (p < SCENE_MAX_TIES) S.ties[p] = it.y;
             }
         }
     }
     __syncthreads();
-    const int m = min(*nties, SCENE_MAX_TIES);
+    const int m = min(S.nties, SCENE_MAX_TIES);
     // ---- gather the selection into LDS as (shuffle key << 32 | raw index)
     for (int e0 = 0; e0 < n; e0 += SCENE_THREADS) {
         const int e = e0 + tid;
@@ -128,21 +184,21 @@ __device__ __forceinline__ SceneSel scene_select_sort(const uint2* __restrict__ 
             bool drawn = cand && key < T;
             if (cand && need > 0 && key == T) {
                 int rank = 0;
-                for (int q = 0; q < m; q++) rank += ties[q] < it.y ? 1 : 0;
+                for (int q = 0; q < m; q++) rank += S.ties[q] < it.y ? 1 : 0;
                 drawn = rank < need;
             }
             if (keep_all || (keep_far && isfar)) {
-                const int p = atomicAdd(nsel, 1);
+                const int p = atomicAdd(&S.nsel, 1);
                 keys[lds_phys(p)] = ((u64)scene_rand(seed, 1u, b, it.y) << 32) | it.y;
             }
             if (drawn) {
-                const int p = atomicAdd(nsel, 1);
+                const int p = atomicAdd(&S.nsel, 1);
                 keys[lds_phys(p)] = ((u64)scene_rand(seed, keep_all ? 2u : 1u, b, it.y) << 32) | it.y;
             }
         }
     }
     __syncthreads();
-    const int total = *nsel;                               // == npoints unless st == 1
+    const int total = S.nsel;                              // == npoints unless st == 1
     u64 v[16];
     if (tid * 16 < NP) {
 #pragma unroll
@@ -156,4 +212,64 @@ __device__ __forceinline__ SceneSel scene_select_sort(const uint2* __restrict__ 
     SceneSel r;
     r.total = total; r.status = st;
     return r;
+}
+
+// block-wide: frame b has no candidate: zero rows, source -1, status 2.  feat = the pass's (B, npoints) feature output,
+// in4 = its optional (B, npoints, 4) input output (NULL: none)
+__device__ __forceinline__ void scene_empty_frame(const SceneFrames& F, int b, float* feat, float* in4) {
+    const size_t row0 = (size_t)b * F.npoints;
+    for (size_t j = row0 + threadIdx.x; j < row0 + F.npoints; j += SCENE_THREADS) {
+        F.out_xyz[j * 3] = 0.f; F.out_xyz[j * 3 + 1] = 0.f; F.out_xyz[j * 3 + 2] = 0.f; feat[j] = 0.f; F.out_src[j] = -1;
+        if (in4) { in4[j * 4] = 0.f; in4[j * 4 + 1] = 0.f; in4[j * 4 + 2] = 0.f; in4[j * 4 + 3] = 0.f; }
+    }
+    if (threadIdx.x == 0) F.status[b] = 2;
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------------------
+// What every pass requires of the frames it is given.  `threads` = the block size of its per-point kernel, extra_per_frame = what
+// the pass adds to a frame's candidates.  With B == 0, or idle (nothing to do whatever the frames hold), the pointers may be NULL.
+// A guard on the frames themselves (offsets that do not describe raw, a bound on B) belongs here.
+static int scene_check_frames(const char* who, const float* raw, const int64_t* offsets, int B, int64_t total_points, int max_points_per_frame,
+                              const float* calib, long extra_per_frame, int threads, bool idle = false) {
+    PRCNN_REQUIRE(B >= 0 && total_points >= 0 && max_points_per_frame >= 0, "%s: bad shape B=%d total=%ld", who, B, (long)total_points);
+    if (B == 0 || idle) return PRCNN_OK;
+    PRCNN_REQUIRE(offsets && calib, "%s: null pointer", who);
+    PRCNN_REQUIRE(total_points == 0 || raw, "%s: null raw points", who);
+    PRCNN_REQUIRE(((uintptr_t)raw % 16) == 0, "%s: raw points must be 16-byte aligned", who);
+    PRCNN_REQUIRE((long)max_points_per_frame + extra_per_frame < (1L << 31) - threads, "%s: frame too large", who);
+    return PRCNN_OK;
+}
+
+// the workspace of a drawing pass is  counters (B, 2) | candidate list, the list on the next 64-byte boundary
+static size_t scene_counters_bytes(int B) { return (size_t)B * 2 * sizeof(int32_t); }
+static size_t scene_list_offset(int B) { return ((scene_counters_bytes(B) + 63) / 64) * 64; }
+
+static void scene_fill_frames(SceneFrames& F, const float* raw, const int64_t* offsets, int B, const float* calib, const int32_t* img_hw,
+                              const double* scope, int npoints, uint32_t seed, void* workspace, float* out_xyz, int32_t* out_src,
+                              int32_t* nvalid, int32_t* status) {
+    F.raw = reinterpret_cast<const float4*>(raw); F.off = offsets; F.calib = calib; F.img_hw = img_hw;
+    F.use_scope = scope != nullptr;
+    for (int q = 0; q < 6; q++) F.scope[q] = scope ? scope[q] : 0.0;
+    F.B = B; F.npoints = npoints; F.seed = seed;
+    F.NP = 16;
+    while (F.NP < npoints) F.NP <<= 1;
+    F.counters = static_cast<int32_t*>(workspace);
+    F.list = reinterpret_cast<uint2*>(static_cast<char*>(workspace) + scene_list_offset(B));
+    F.out_xyz = out_xyz; F.out_src = out_src; F.nvalid = nvalid; F.status = status;
+}
+
+static int scene_reset_counters(const char* who, const SceneFrames& F, hipStream_t s) {
+    if (prcnn_fill_words(F.counters, 0u, (size_t)F.B * 2, s) != hipSuccess) return prcnn_fail(PRCNN_EHIP, "%s: memset failed", who);
+    return PRCNN_OK;
+}
+
+// one SCENE_THREADS workgroup per frame with the LDS of the NP-key sort; the first launch on a device raises the kernel's limit
+template <auto KERNEL, class Params>
+static int scene_launch_sample(const char* who, const Params& P, hipStream_t s) {
+    static PrcnnLdsLimit attr;
+    if (!attr.raise((const void*)KERNEL, (int)lds_sort_bytes(16384))) return prcnn_fail(PRCNN_EHIP, "%s: cannot raise the dynamic LDS limit", who);
+    hipLaunchKernelGGL(KERNEL, dim3(P.B), dim3(SCENE_THREADS), lds_sort_bytes(P.NP), s, P);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return prcnn_fail(PRCNN_EHIP, "%s(sample): launch failed: %s", who, hipGetErrorString(e));
+    return PRCNN_OK;
 }

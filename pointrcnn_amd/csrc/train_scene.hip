@@ -21,12 +21,13 @@
 //
 //   tscene_box_kernel    : one workgroup per frame: draws the frame's augmentation (reported through `aug`, which the sample pass
 //                          reads back), builds the (G + K)-row augmented gt_boxes3d.
-//   tscene_flag_kernel   : scene_flag_kernel plus the accepted-box test (<= 64 BoxConst in LDS); removed points never enter
-//                          the candidate list.
+//   tscene_flag_kernel   : scene_flag_kernel with the accepted-box test (<= 64 BoxConst in LDS) between scene_project and
+//                          scene_append: removed points never enter the candidate list.
 //   tscene_paste_kernel  : one workgroup per (accepted object, frame): appends the object's points to the same list with their
 //                          far bit and draw key (one atomic per object).
-//   tscene_sample_kernel : one 1024-thread workgroup per frame: scene_select_sort (scene_common.h); the row writer reads the raw
-//                          scan (recomputing the rect row) or the database (applying y_shift) and applies step 5 as it writes.
+//   tscene_sample_kernel : one workgroup per frame: scene_select_sort; the row writer reads the raw scan (scene_rect) or the
+//                          database (applying y_shift) and applies step 5 as it writes.
+// The frame head of the params, the projection, the append, the draw and the host prelude are scene_common.h's.
 // No (N + P) cloud is materialised and nothing synchronises with the host between the launches.  The selected set and the output
 // order depend on (seed, frame, identity) only, never on the order in which the atomics append.
 #include "common.h"
@@ -38,15 +39,7 @@ constexpr int TS_MAX_BOXES = 128;          // G + K: what prcnn_rpn_labels takes
 constexpr int TS_PASTE_THREADS = 256;
 constexpr float TS_PI = 3.14159274101257324f;      // fp32(np.pi)
 
-struct TrainSceneParams {
-    const float4* raw;          // (total, 4) x y z intensity, lidar frame
-    const int64_t* off;         // (B+1)
-    const float* calib;         // (B, 24)
-    const int32_t* img_hw;      // (B, 2)
-    double scope[6];
-    int use_scope;
-    int B, npoints, NP;
-    unsigned seed;
+struct TrainSceneParams : SceneFrames {      // list: frame b at off[b] + b * K * db_max; out_src: raw index, or n_raw + j (pasted)
     const float* gt;            // (B, G, 7) training labels
     const float* gt_alpha;      // (B, G)
     const int32_t* num_gt;      // (B) or NULL
@@ -64,14 +57,8 @@ struct TrainSceneParams {
     int D, db_max;
     int methods;                // bit 0 rotation, 1 scaling, 2 flip in AUG_METHOD_LIST
     double prob[3], rot_lo, rot_hi, sc_lo, sc_hi;
-    uint2* list;                // candidate entries, frame b at off[b] + b * K * db_max
-    int32_t* counters;          // (B, 2) candidates, far ones -- zeroed by the launcher
-    float* out_xyz;             // (B, npoints, 3)
     float* out_input;           // (B, npoints, 4) or NULL
     float* out_feat;            // (B, npoints)
-    int32_t* out_src;           // (B, npoints)
-    int32_t* nvalid;            // (B)
-    int32_t* status;            // (B)
     float* out_gt;              // (B, G + K, 7)
     int32_t* out_num_gt;        // (B)
     double* aug;                // (B, 8) enable[3], angle, cos, sin, scale, flip
@@ -159,9 +146,7 @@ __global__ __launch_bounds__(TS_MAX_BOXES) void tscene_box_kernel(TrainScenePara
 
 __global__ __launch_bounds__(SCENE_THREADS) void tscene_flag_kernel(TrainSceneParams P) {
     __shared__ BoxConst sbox[TS_MAX_ACCEPT];
-    __shared__ int wv[SCENE_THREADS / 64], wf[SCENE_THREADS / 64];
-    __shared__ int base;
-    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.y, tid = threadIdx.x;
     const int64_t o = P.off[b];
     const int n = (int)(P.off[b + 1] - o);
     if ((int64_t)blockIdx.x * SCENE_THREADS >= n) return;
@@ -187,22 +172,7 @@ __global__ __launch_bounds__(SCENE_THREADS) void tscene_flag_kernel(TrainScenePa
         }
         far = valid && !(r.z < 40.0f);                         // kitti_rcnn_dataset.py:288: near = depth < 40.0
     }
-    const unsigned long long bv = __ballot(valid), bf = __ballot(far);
-    if (lane == 0) { wv[wave] = (int)__popcll(bv); wf[wave] = (int)__popcll(bf); }
-    __syncthreads();
-    if (tid == 0) {
-        int tv = 0, tf = 0;
-        for (int w = 0; w < SCENE_THREADS / 64; w++) { tv += wv[w]; tf += wf[w]; }
-        base = tv > 0 ? atomicAdd(P.counters + b * 2, tv) : 0;
-        if (tf > 0) atomicAdd(P.counters + b * 2 + 1, tf);
-    }
-    __syncthreads();
-    if (valid) {
-        int pos = base + (int)__popcll(bv & ((1ULL << lane) - 1ULL));
-        for (int w = 0; w < wave; w++) pos += wv[w];
-        const unsigned key = scene_rand(P.seed, 0u, (unsigned)b, (unsigned)i) >> 2;
-        ts_list(P, b)[pos] = make_uint2(key | (far ? SCENE_FAR : 0u), (unsigned)i);
-    }
+    scene_append(valid, far, i, ts_list(P, b), P.counters + b * 2, P.seed, b);
 }
 
 __global__ __launch_bounds__(TS_PASTE_THREADS) void tscene_paste_kernel(TrainSceneParams P) {
@@ -234,11 +204,7 @@ __global__ __launch_bounds__(TS_PASTE_THREADS) void tscene_paste_kernel(TrainSce
 
 __global__ __launch_bounds__(SCENE_THREADS) void tscene_sample_kernel(TrainSceneParams P) {
     extern __shared__ u64 keys[];
-    __shared__ int hist[1024];
-    __shared__ int wsum[SCENE_THREADS / 64];
-    __shared__ int sel[2];
-    __shared__ unsigned ties[SCENE_MAX_TIES];
-    __shared__ int nties, nsel;
+    __shared__ SceneLds lds;
     __shared__ unsigned pbase[TS_MAX_ACCEPT + 1];               // identity (minus n_raw) of every accepted object's first point
     __shared__ int64_t pfirst[TS_MAX_ACCEPT];                   // its first database row
     __shared__ double pshift[TS_MAX_ACCEPT];
@@ -254,7 +220,7 @@ __global__ __launch_bounds__(SCENE_THREADS) void tscene_sample_kernel(TrainScene
     int32_t* osrc = P.out_src + (size_t)b * np;
     const int na = ts_accepted(P, b);
     if (tid == 0) {
-        P.nvalid[b] = n; nties = 0; nsel = 0;
+        P.nvalid[b] = n;
         unsigned run = 0;
         for (int a = 0; a < na; ++a) {
             int64_t first;
@@ -265,14 +231,10 @@ __global__ __launch_bounds__(SCENE_THREADS) void tscene_sample_kernel(TrainScene
         pbase[na] = run;
     }
     if (n == 0) {
-        for (int j = tid; j < np; j += SCENE_THREADS) {
-            oxyz[j * 3] = 0.f; oxyz[j * 3 + 1] = 0.f; oxyz[j * 3 + 2] = 0.f; ofeat[j] = 0.f; osrc[j] = -1;
-            if (oin) { oin[j * 4] = 0.f; oin[j * 4 + 1] = 0.f; oin[j * 4 + 2] = 0.f; oin[j * 4 + 3] = 0.f; }
-        }
-        if (tid == 0) P.status[b] = 2;
+        scene_empty_frame(P, b, P.out_feat, P.out_input);
         return;
     }
-    const SceneSel ss = scene_select_sort(L, n, f, np, P.NP, P.seed, (unsigned)b, keys, hist, wsum, sel, ties, &nties, &nsel);
+    const SceneSel ss = scene_select_sort(L, n, f, np, P.NP, P.seed, (unsigned)b, keys, lds);
     const int total = ss.total;                                 // == npoints unless the status is 1
     // ---- rows in shuffled order (a short selection -- status 1 -- repeats cyclically), augmented as they are written
     const double* A = P.aug + (size_t)b * 8;
@@ -285,9 +247,7 @@ __global__ __launch_bounds__(SCENE_THREADS) void tscene_sample_kernel(TrainScene
         float x, y, z, w;
         if (i < n_raw) {
             const float4 p = P.raw[o + i];
-            x = ((p.x * c[0] + p.y * c[3]) + p.z * c[6]) + c[9];
-            y = ((p.x * c[1] + p.y * c[4]) + p.z * c[7]) + c[10];
-            z = ((p.x * c[2] + p.y * c[5]) + p.z * c[8]) + c[11];
+            scene_rect(p, c, x, y, z);
             w = p.w;
         } else {
             const unsigned jj = i - n_raw;
@@ -318,7 +278,7 @@ __global__ __launch_bounds__(SCENE_THREADS) void tscene_sample_kernel(TrainScene
 PRCNN_API size_t prcnn_train_scene_workspace_bytes(int64_t total_points, int B, int K, int db_max_points) {
     if (total_points < 0 || B < 0 || K < 0 || db_max_points < 0) return 0;
     const size_t entries = (size_t)total_points + (size_t)B * K * db_max_points;     // frame b holds n_raw[b] + K * db_max_points
-    return entries * sizeof(uint2) + (((size_t)B * 2 * sizeof(int32_t) + 63) / 64) * 64 + 64;
+    return entries * sizeof(uint2) + scene_list_offset(B) + 64;
 }
 
 PRCNN_API int prcnn_train_scene_prepare(const float* raw, const int64_t* offsets, int B, int64_t total_points, int max_points_per_frame,
@@ -330,36 +290,28 @@ PRCNN_API int prcnn_train_scene_prepare(const float* raw, const int64_t* offsets
                                         const double* aug_cfg, float* out_xyz, float* out_input, float* out_features, int32_t* out_src,
                                         int32_t* nvalid, int32_t* status, float* out_gt_boxes3d, int32_t* out_num_gt, double* aug,
                                         void* workspace, size_t workspace_bytes, prcnn_stream_t stream) {
-    PRCNN_REQUIRE(B >= 0 && total_points >= 0 && max_points_per_frame >= 0, "prcnn_train_scene_prepare: bad shape B=%d total=%ld", B, (long)total_points);
+    const char* who = "prcnn_train_scene_prepare";
     PRCNN_REQUIRE(npoints > 0 && npoints <= 16384, "prcnn_train_scene_prepare: npoints=%d (1..16384: the shuffle is one LDS-resident sort per frame)", npoints);
     PRCNN_REQUIRE(G >= 0 && K >= 0 && K <= TS_MAX_ACCEPT, "prcnn_train_scene_prepare: G=%d K=%d (K: 0..%d accepted objects per frame)", G, K, TS_MAX_ACCEPT);
     PRCNN_REQUIRE(G + K <= TS_MAX_BOXES, "prcnn_train_scene_prepare: G + K = %d > %d (what prcnn_rpn_labels takes per frame)", G + K, TS_MAX_BOXES);
     PRCNN_REQUIRE(D >= 0 && db_max_points >= 0, "prcnn_train_scene_prepare: bad database shape D=%d max=%d", D, db_max_points);
     PRCNN_REQUIRE(aug_cfg, "prcnn_train_scene_prepare: null aug_cfg");
-    if (B == 0) return PRCNN_OK;
-    PRCNN_REQUIRE(offsets && calib && img_hw && out_xyz && out_features && out_src && nvalid && status && out_num_gt && aug,
+    const bool paste = acc_count != nullptr && K > 0;
+    const int Kp = paste ? K : 0;
+    int rc = scene_check_frames(who, raw, offsets, B, total_points, max_points_per_frame, calib, (long)Kp * db_max_points, SCENE_THREADS);
+    if (rc != PRCNN_OK || B == 0) return rc;
+    PRCNN_REQUIRE(img_hw && out_xyz && out_features && out_src && nvalid && status && out_num_gt && aug,
                   "prcnn_train_scene_prepare: null pointer");
     PRCNN_REQUIRE(G + K == 0 || out_gt_boxes3d, "prcnn_train_scene_prepare: null out_gt_boxes3d");
     PRCNN_REQUIRE(G == 0 || (gt_boxes3d && gt_alpha), "prcnn_train_scene_prepare: null gt_boxes3d / gt_alpha");
-    const bool paste = acc_count != nullptr && K > 0;
     PRCNN_REQUIRE(!paste || (acc_db_id && acc_boxes3d && acc_alpha && acc_y_shift && acc_status && db_offsets &&
                              (db_max_points == 0 || (db_points && db_intensity))),
                   "prcnn_train_scene_prepare: the accepted objects need db_id, boxes3d, alpha, y_shift, status and the database");
-    PRCNN_REQUIRE(total_points == 0 || raw, "prcnn_train_scene_prepare: null raw points");
-    PRCNN_REQUIRE(((uintptr_t)raw % 16) == 0, "prcnn_train_scene_prepare: raw points must be 16-byte aligned");
-    const int Kp = paste ? K : 0;
     PRCNN_REQUIRE(workspace && workspace_bytes >= prcnn_train_scene_workspace_bytes(total_points, B, Kp, db_max_points),
                   "prcnn_train_scene_prepare: workspace too small");
-    PRCNN_REQUIRE((long)max_points_per_frame + (long)Kp * db_max_points < (1L << 31) - SCENE_THREADS, "prcnn_train_scene_prepare: frame too large");
     hipStream_t s = (hipStream_t)stream;
     TrainSceneParams P = {};
-    P.raw = reinterpret_cast<const float4*>(raw); P.off = offsets; P.calib = calib; P.img_hw = img_hw;
-    P.use_scope = scope != nullptr;
-    for (int q = 0; q < 6; q++) P.scope[q] = scope ? scope[q] : 0.0;
-    P.B = B; P.npoints = npoints; P.seed = seed;
-    int NP = 16;
-    while (NP < npoints) NP <<= 1;
-    P.NP = NP;
+    scene_fill_frames(P, raw, offsets, B, calib, img_hw, scope, npoints, seed, workspace, out_xyz, out_src, nvalid, status);
     P.gt = gt_boxes3d; P.gt_alpha = gt_alpha; P.num_gt = num_gt; P.G = G;
     P.acc_count = paste ? acc_count : nullptr; P.acc_id = acc_db_id; P.acc_boxes = acc_boxes3d; P.acc_alpha = acc_alpha;
     P.acc_shift = acc_y_shift; P.acc_status = acc_status; P.K = K;
@@ -367,12 +319,8 @@ PRCNN_API int prcnn_train_scene_prepare(const float* raw, const int64_t* offsets
     P.methods = (aug_cfg[0] != 0.0 ? 1 : 0) | (aug_cfg[1] != 0.0 ? 2 : 0) | (aug_cfg[2] != 0.0 ? 4 : 0);
     for (int q = 0; q < 3; q++) P.prob[q] = aug_cfg[3 + q];
     P.rot_lo = aug_cfg[6]; P.rot_hi = aug_cfg[7]; P.sc_lo = aug_cfg[8]; P.sc_hi = aug_cfg[9];
-    char* w = static_cast<char*>(workspace);
-    P.counters = reinterpret_cast<int32_t*>(w);
-    P.list = reinterpret_cast<uint2*>(w + (((size_t)B * 2 * sizeof(int32_t) + 63) / 64) * 64);
-    P.out_xyz = out_xyz; P.out_input = out_input; P.out_feat = out_features; P.out_src = out_src; P.nvalid = nvalid; P.status = status;
-    P.out_gt = out_gt_boxes3d; P.out_num_gt = out_num_gt; P.aug = aug;
-    if (prcnn_fill_words(P.counters, 0u, (size_t)B * 2, s) != hipSuccess) return prcnn_fail(PRCNN_EHIP, "prcnn_train_scene_prepare: memset failed");
+    P.out_input = out_input; P.out_feat = out_features; P.out_gt = out_gt_boxes3d; P.out_num_gt = out_num_gt; P.aug = aug;
+    if ((rc = scene_reset_counters(who, P, s)) != PRCNN_OK) return rc;
     hipLaunchKernelGGL(tscene_box_kernel, dim3(B), dim3(TS_MAX_BOXES), 0, s, P);
     PRCNN_LAUNCH_CHECK("prcnn_train_scene_prepare(boxes)");
     if (max_points_per_frame > 0) {
@@ -383,10 +331,5 @@ PRCNN_API int prcnn_train_scene_prepare(const float* raw, const int64_t* offsets
         hipLaunchKernelGGL(tscene_paste_kernel, dim3(K, B), dim3(TS_PASTE_THREADS), 0, s, P);
         PRCNN_LAUNCH_CHECK("prcnn_train_scene_prepare(paste)");
     }
-    static PrcnnLdsLimit attr;
-    if (!attr.raise((const void*)tscene_sample_kernel, (int)lds_sort_bytes(16384)))
-        return prcnn_fail(PRCNN_EHIP, "prcnn_train_scene_prepare: cannot raise the dynamic LDS limit");
-    hipLaunchKernelGGL(tscene_sample_kernel, dim3(B), dim3(SCENE_THREADS), lds_sort_bytes(NP), s, P);
-    PRCNN_LAUNCH_CHECK("prcnn_train_scene_prepare(sample)");
-    return PRCNN_OK;
+    return scene_launch_sample<tscene_sample_kernel>(who, P, s);
 }

@@ -5,6 +5,7 @@ libprcnn_pointops.so on torch's CURRENT stream (so it composes with torch.cuda.g
 Shapes and argument meaning mirror the reference op surface (see each function's citation).
 """
 import ctypes
+import math
 import os
 import threading
 
@@ -987,6 +988,34 @@ def scatter_rows(src, rows_list, count, dst, col_off):
                                                dst.stride(-2), int(col_off), _stream()), "prcnn_scatter_rows")
 
 
+# what the wrappers of the passes over raw frames share (the native side of it is csrc/scene_common.h)
+def _frames(raw, offsets, calib, *img_hw):
+    """raw (total,4) f32, offsets (B+1) i64, calib (B,24) f32 and, where the pass takes one, img_hw (B,2) i32 -> (B, total, device)"""
+    _chk(raw, "raw", ndim=2)
+    _chk(calib, "calib", ndim=2)
+    for hw in img_hw:
+        _chk(hw, "img_hw", _INT, 2)
+    if offsets.dtype != torch.int64 or not offsets.is_contiguous() or offsets.device != raw.device:
+        raise RuntimeError("offsets must be a contiguous int64 tensor on the device of raw")
+    B = offsets.shape[0] - 1
+    if raw.shape[1] != 4 or calib.shape[1] != 24 or any(hw.shape[1] != 2 for hw in img_hw):
+        raise RuntimeError("expected raw (total,4), calib (B,24), img_hw (B,2)")
+    if calib.shape[0] != B or any(hw.shape[0] != B for hw in img_hw):
+        raise RuntimeError("calib / img_hw must have one row per frame")
+    return B, raw.shape[0], raw.device
+
+
+def _scope(scope):
+    """PC_AREA_SCOPE as the library takes it: 6 doubles [x0 x1 y0 y1 z0 z1], or NULL for no range crop"""
+    return None if scope is None else (ctypes.c_double * 6)(*[float(v) for v in scope])
+
+
+def _sample_outputs(B, npoints, dev):
+    """-> xyz (B,npoints,3), src (B,npoints) i32, nvalid (B) i32, status (B) i32: what every npoints draw writes"""
+    return (torch.empty((B, npoints, 3), dtype=_F32, device=dev), torch.empty((B, npoints), dtype=_INT, device=dev),
+            torch.empty((B,), dtype=_INT, device=dev), torch.empty((B,), dtype=_INT, device=dev))
+
+
 # ---------------------------------------------------------------------------------------------------------
 # RPN input builder (csrc/scene.hip)
 # ---------------------------------------------------------------------------------------------------------
@@ -995,27 +1024,14 @@ def scene_prepare(raw, offsets, max_points_per_frame, calib, img_hw, scope, npoi
     the device; scope: 6 host floats [x0 x1 y0 y1 z0 z1] or None.
     -> pts_rect (B,npoints,3), intensity - 0.5 (B,npoints), src index (B,npoints) i32, nvalid (B) i32, status (B) i32
     [lib/datasets/kitti_rcnn_dataset.py:246-310 for a whole batch; see prcnn_scene_prepare]"""
-    _chk(raw, "raw", ndim=2)
-    _chk(calib, "calib", ndim=2)
-    _chk(img_hw, "img_hw", _INT, 2)
-    if offsets.dtype != torch.int64 or not offsets.is_contiguous() or offsets.device != raw.device:
-        raise RuntimeError("offsets must be a contiguous int64 tensor on the device of raw")
-    if raw.shape[1] != 4 or calib.shape[1] != 24 or img_hw.shape[1] != 2:
-        raise RuntimeError("expected raw (total,4), calib (B,24), img_hw (B,2)")
-    B, total, dev = offsets.shape[0] - 1, raw.shape[0], raw.device
-    if calib.shape[0] != B or img_hw.shape[0] != B:
-        raise RuntimeError("calib / img_hw must have one row per frame")
+    B, total, dev = _frames(raw, offsets, calib, img_hw)
     L = _cabi.lib()
     ws = torch.empty((int(L.prcnn_scene_workspace_bytes(total, B)),), dtype=torch.uint8, device=dev)
-    xyz = torch.empty((B, npoints, 3), dtype=_F32, device=dev)
+    xyz, src, nvalid, status = _sample_outputs(B, npoints, dev)
     inten = torch.empty((B, npoints), dtype=_F32, device=dev)
-    src = torch.empty((B, npoints), dtype=_INT, device=dev)
-    nvalid = torch.empty((B,), dtype=_INT, device=dev)
-    status = torch.empty((B,), dtype=_INT, device=dev)
-    sc = None if scope is None else (ctypes.c_double * 6)(*[float(v) for v in scope])
-    _cabi.check(L.prcnn_scene_prepare(_p(raw), _p(offsets), B, total, int(max_points_per_frame), _p(calib), _p(img_hw), sc, int(npoints),
-                                      int(seed) & 0xFFFFFFFF, _p(xyz), _p(inten), _p(src), _p(nvalid), _p(status), _p(ws), ws.numel(),
-                                      _stream()), "prcnn_scene_prepare")
+    _cabi.check(L.prcnn_scene_prepare(_p(raw), _p(offsets), B, total, int(max_points_per_frame), _p(calib), _p(img_hw), _scope(scope),
+                                      int(npoints), int(seed) & 0xFFFFFFFF, _p(xyz), _p(inten), _p(src), _p(nvalid), _p(status), _p(ws),
+                                      ws.numel(), _stream()), "prcnn_scene_prepare")
     return xyz, inten, src, nvalid, status
 
 
@@ -1035,17 +1051,9 @@ def train_scene_prepare(raw, offsets, max_points_per_frame, calib, img_hw, scope
     cfg.AUG_METHOD_LIST that run (() = cfg.AUG_DATA false), aug_prob = cfg.AUG_METHOD_PROB, aug_rot_range = cfg.AUG_ROT_RANGE.
     -> dict pts_rect (B,npoints,3), pts_input (the same tensor, or (B,npoints,4) when use_intensity), pts_features (B,npoints,1),
     gt_boxes3d (B,G+K,7), num_gt (B), src, nvalid, status, aug (B,8) f64 -- see include/prcnn_pointops.h"""
-    import math
-    _chk(raw, "raw", ndim=2); _chk(calib, "calib", ndim=2); _chk(img_hw, "img_hw", _INT, 2)
+    B, total, dev = _frames(raw, offsets, calib, img_hw)
     _chk(gt_boxes3d, "gt_boxes3d", ndim=3); _chk(gt_alpha, "gt_alpha", ndim=2)
-    if offsets.dtype != torch.int64 or not offsets.is_contiguous() or offsets.device != raw.device:
-        raise RuntimeError("offsets must be a contiguous int64 tensor on the device of raw")
-    if raw.shape[1] != 4 or calib.shape[1] != 24 or img_hw.shape[1] != 2:
-        raise RuntimeError("expected raw (total,4), calib (B,24), img_hw (B,2)")
-    B, total, dev = offsets.shape[0] - 1, raw.shape[0], raw.device
     G = gt_boxes3d.shape[1]
-    if calib.shape[0] != B or img_hw.shape[0] != B:
-        raise RuntimeError("calib / img_hw must have one row per frame")
     if tuple(gt_boxes3d.shape) != (B, G, 7) or tuple(gt_alpha.shape) != (B, G):
         raise ValueError("train_scene_prepare: gt_boxes3d must be (%d, G, 7), gt_alpha (%d, G)" % (B, B))
     if num_gt is not None:
@@ -1073,22 +1081,18 @@ def train_scene_prepare(raw, offsets, max_points_per_frame, calib, img_hw, scope
     L = _cabi.lib()
     need = int(L.prcnn_train_scene_workspace_bytes(total, B, K, db_max))
     ws = torch.empty((need,), dtype=torch.uint8, device=dev) if workspace is None else workspace
-    xyz = torch.empty((B, npoints, 3), dtype=_F32, device=dev)
+    xyz, src, nvalid, status = _sample_outputs(B, npoints, dev)
     pin = torch.empty((B, npoints, 4), dtype=_F32, device=dev) if use_intensity else None
     feat = torch.empty((B, npoints), dtype=_F32, device=dev)
-    src = torch.empty((B, npoints), dtype=_INT, device=dev)
-    nvalid = torch.empty((B,), dtype=_INT, device=dev)
-    status = torch.empty((B,), dtype=_INT, device=dev)
     out_gt = torch.empty((B, G + K, 7), dtype=_F32, device=dev)
     out_ng = torch.empty((B,), dtype=_INT, device=dev)
     aug = torch.empty((B, 8), dtype=torch.float64, device=dev)
-    sc = None if scope is None else (ctypes.c_double * 6)(*[float(v) for v in scope])
     hi = math.pi / aug_rot_range
     cfg = (ctypes.c_double * 10)(*([1.0 if m in aug_methods else 0.0 for m in AUG_METHODS] + [float(p) for p in aug_prob] +
                                    [-hi, hi, 0.95, 1.05]))
     _cabi.check(L.prcnn_train_scene_prepare(
-        _p(raw), _p(offsets), B, total, int(max_points_per_frame), _p(calib), _p(img_hw), sc, int(npoints), int(seed) & 0xFFFFFFFF,
-        _p(gt_boxes3d), _p(gt_alpha), _p(num_gt), G, _p(acc[0]), _p(acc[1]), _p(acc[2]), _p(acc[3]), _p(acc[4]), _p(acc[5]), K,
+        _p(raw), _p(offsets), B, total, int(max_points_per_frame), _p(calib), _p(img_hw), _scope(scope), int(npoints),
+        int(seed) & 0xFFFFFFFF, _p(gt_boxes3d), _p(gt_alpha), _p(num_gt), G, _p(acc[0]), _p(acc[1]), _p(acc[2]), _p(acc[3]), _p(acc[4]), _p(acc[5]), K,
         _p(dbt[0]), _p(dbt[1]), _p(dbt[2]), D, db_max, cfg, _p(xyz), _p(pin), _p(feat), _p(src), _p(nvalid), _p(status), _p(out_gt),
         _p(out_ng), _p(aug), _p(ws), ws.numel(), _stream()), "prcnn_train_scene_prepare")
     return {"pts_rect": xyz, "pts_input": pin if use_intensity else xyz, "pts_features": feat.unsqueeze(-1), "gt_boxes3d": out_gt,
@@ -1105,16 +1109,10 @@ def gt_database_build(raw, offsets, max_points_per_frame, calib, boxes3d, num_bo
     coordinates, intensity (P), src (P) i32 raw index in the frame; each object's points in ascending raw index
     [tools/generate_gt_database.py:50-84 for a batch of frames; see prcnn_gt_database_count / prcnn_gt_database_fill].
     One host read (P) between the two passes."""
-    _chk(raw, "raw", ndim=2)
-    _chk(calib, "calib", ndim=2)
+    B, total, dev = _frames(raw, offsets, calib)
     _chk(boxes3d, "boxes3d", ndim=3)
     _chk(num_boxes, "num_boxes", _INT, 1)
-    if offsets.dtype != torch.int64 or not offsets.is_contiguous() or offsets.device != raw.device:
-        raise RuntimeError("offsets must be a contiguous int64 tensor on the device of raw")
-    B, total, dev = offsets.shape[0] - 1, raw.shape[0], raw.device
     G = boxes3d.shape[1]
-    if raw.shape[1] != 4 or calib.shape[1] != 24 or calib.shape[0] != B:
-        raise RuntimeError("expected raw (total,4), calib (B,24)")
     if tuple(boxes3d.shape) != (B, G, 7) or num_boxes.shape[0] != B:
         raise ValueError("gt_database_build: boxes3d must be (%d, G, 7), num_boxes (%d,)" % (B, B))
     L = _cabi.lib()
