@@ -2376,29 +2376,6 @@ __global__ __launch_bounds__(CP_WAVES * 64, 1) void mlp_chain_p_kernel(const Cha
 template <int MODE, int NB1> static constexpr size_t chain_p_lds_bytes() {
     return (size_t)4 * SStage<4>::U4 * 16 + (size_t)CP_WAVES * 32 * CC_LD * 4 + 2 * 128 * 4;
 }
-static int chain_p_grid() {
-    static const int cus = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        return n & ~7;                                        // a multiple of 8: the XCD-aware tile order counts on it
-    }();
-    return cus > 0 ? cus : 8;
-}
-// PRCNN_CHAIN_PERSIST=0: the per-tile kernels (A/B switch, same bits)
-static bool chain_persist_on() { return sw_enabled(SW_CHAIN_PERSIST); }
-template <int MODE, int NB1>
-static int launch_chain_p(const ChainParams& C, hipStream_t s) {
-    constexpr size_t lds = chain_p_lds_bytes<MODE, NB1>();
-    static PrcnnLdsLimit attr;
-    if (!attr.raise((const void*)mlp_chain_p_kernel<MODE, NB1, 6>, (int)lds))
-        return prcnn_fail(PRCNN_EHIP, "prcnn_mlp_chain(persistent split): cannot raise the dynamic LDS limit");
-    const long tiles = (C.a.rows + 31) / 32;
-    const int grid = (int)min((long)chain_p_grid(), (tiles + CP_WAVES - 1) / CP_WAVES);
-    hipLaunchKernelGGL((mlp_chain_p_kernel<MODE, NB1, 6>), dim3(grid), dim3(CP_WAVES * 64), lds, s, C);
-    return PRCNN_OK;
-}
-static bool chain_coop_on() { return sw_num(SW_CHAIN_COOP, 1) != 0; }
-static bool chain_coop_forced() { return sw_num(SW_CHAIN_COOP, 1) == 2; }      // 2: the cooperative form also where the lane-is-a-row kernel is the default
 
 // =====================================================================================================
 // PERSISTENT chain: the fast chain's arithmetic with ALL layers' packed weights resident in LDS for the lifetime of the
@@ -2667,379 +2644,6 @@ __global__ void maxpool_rows_kernel(const float* __restrict__ in, int ld_in, lon
     for (int s = 1; s < ns; s++) m = fmaxf(m, p[(long)s * ld_in]);
     out[r * ld_out + col_off + c] = m;
 }
-
-
-static bool rows32_ok(int mode, const MlpParams& P);
-static int launch_rows32(MlpParams& P, hipStream_t s);
-
-static int launch_mlp(int mode, MlpParams& P, hipStream_t s) {
-    PRCNN_REQUIRE(P.wpack && P.out, "prcnn_mlp: null weight/output pointer");
-    PRCNN_REQUIRE(P.rows >= 0 && P.K > 0 && P.Nout > 0, "prcnn_mlp: bad shape rows=%ld K=%d Nout=%d", P.rows, P.K, P.Nout);
-    PRCNN_REQUIRE(P.pool_ns == 0 || P.pool_ns == 16 || P.pool_ns == 32 || P.pool_ns == 64,
-                  "prcnn_mlp: pool_ns=%d unsupported (use 16/32/64, or store + prcnn_maxpool_rows)", P.pool_ns);
-    PRCNN_REQUIRE(P.pool_ns == 0 || P.rows % P.pool_ns == 0, "prcnn_mlp: rows %ld not a multiple of pool_ns %d", P.rows, P.pool_ns);
-    PRCNN_REQUIRE(aligned16(P.wpack), "prcnn_mlp: wpack must be 16-byte aligned");
-    if (P.rows == 0) return PRCNN_OK;
-    P.KB = (P.K + 7) / 8;
-    P.NB = (P.Nout + 31) / 32;
-    // split-bf16 variant: 128 x 128 tiles while they give most CUs a workgroup (two are resident per CU), else 128 x 64.  Every
-    // launch of a supported shape takes it, however few its rows: which arithmetic a layer is computed in must not depend on the
-    // batch size (a frame's result is the same bits in a batch of 1 and of 32).  PRCNN_SPLIT_MIN_TILES (dev A/B) sends launches of
-    // fewer tiles to the fp32 kernels, which have forms for few rows.
-    const long split_tiles_wide = (long)prcnn_divup(P.rows, MLP_BM) * prcnn_divup(P.NB, 4), split_tiles_narrow = (long)prcnn_divup(P.rows, MLP_BM) * prcnn_divup(P.NB, 2);
-    const long split_min = sw_num(SW_SPLIT_MIN_TILES, 0);
-    // the hoisted grouped form (prcnn_mlp_group_split); PRCNN_GROUP_SPLIT=0: A/B switch back to the fp32 layer kernel
-    const bool split_group = sw_enabled(SW_GROUP_SPLIT) && mode == MODE_GROUP && P.act == 1 && P.C == P.K && !P.addY;
-    if (P.wsplit && (mode == MODE_PLAIN || split_group) && P.K % MLP_BK == 0 && P.vec_a && split_tiles_narrow >= split_min) {
-        PRCNN_REQUIRE(aligned16(P.wsplit) && (P.split_terms == 3 || P.split_terms == 6), "prcnn_mlp: bad split image / terms=%d", P.split_terms);
-        const long split_wide_min = sw_num(SW_SPLIT_WIDE_MIN, 192);
-        const bool wide = P.NB >= 4 && split_tiles_wide >= split_wide_min;
-        dim3 grid(prcnn_divup(P.rows, MLP_BM), prcnn_divup(P.NB, wide ? 4 : 2));
-        if (!P.seg_cnt) {
-            P.wgm_cols = (int)grid.y;
-            grid = dim3((unsigned)(prcnn_divup(grid.x, 8) * 8 * grid.y), 1);
-        }
-        // a launch sized for the CAPACITY of a compacted list (device-side row count): 2048 workgroups (four rounds of the 512 resident
-        // ones, a multiple of the 8 XCDs) walk the live tiles instead of one workgroup per tile of capacity; PRCNN_BOUNDED_GRID=0: A/B
-        const bool bounded = sw_enabled(SW_BOUNDED_GRID) && P.rows_dev && !P.seg_cnt && !P.addY && grid.x > 2048u;
-        if (bounded) grid = dim3(2048u, 1);
-#define SPL_LAUNCH(W, T)                                                                                                  \
-    do {                                                                                                                  \
-        if (split_group && bounded) hipLaunchKernelGGL((mlp_layer_s_kernel<MODE_GROUP, W, T, false, true>), grid, dim3(MLP_THREADS), 0, s, P);   \
-        else if (split_group) hipLaunchKernelGGL((mlp_layer_s_kernel<MODE_GROUP, W, T, false, false>), grid, dim3(MLP_THREADS), 0, s, P);        \
-        else if (P.addY) hipLaunchKernelGGL((mlp_layer_s_kernel<MODE_PLAIN, W, T, true, false>), grid, dim3(MLP_THREADS), 0, s, P);        \
-        else if (bounded) hipLaunchKernelGGL((mlp_layer_s_kernel<MODE_PLAIN, W, T, false, true>), grid, dim3(MLP_THREADS), 0, s, P);  \
-        else hipLaunchKernelGGL((mlp_layer_s_kernel<MODE_PLAIN, W, T, false, false>), grid, dim3(MLP_THREADS), 0, s, P);              \
-    } while (0)
-        if (wide) { if (P.split_terms == 6) SPL_LAUNCH(2, 6); else SPL_LAUNCH(2, 3); }
-        else { if (P.split_terms == 6) SPL_LAUNCH(1, 6); else SPL_LAUNCH(1, 3); }
-#undef SPL_LAUNCH
-        PRCNN_LAUNCH_CHECK("prcnn_mlp (split-bf16)");
-        return PRCNN_OK;
-    }
-    if (rows32_ok(mode, P)) return launch_rows32(P, s);
-    // >= 97 output channels: 128x128 workgroup tile -- unless that leaves most of the 256 CUs without a workgroup
-    // (few rows, e.g. FP3's 2048 known points): then the 128x64 tile doubles the number of workgroups
-    // (a device-side row count means a compacted list: P.rows is its worst case, the live part is expected to be small)
-    const long wide_min = sw_num(SW_WIDE_MIN_TILES, 192);
-    const bool wide_lists = sw_present(SW_WIDE_LISTS);
-    bool wide = P.NB >= 4 && (!P.rows_dev || wide_lists) && (long)prcnn_divup(P.rows, MLP_BM) * prcnn_divup(P.NB, 4) >= wide_min;
-    dim3 grid(prcnn_divup(P.rows, MLP_BM), prcnn_divup(P.NB, wide ? 4 : 2));
-    // v2 (B operand straight from L2, up to four workgroups per CU) is the default; PRCNN_LAYER_V1=1 is the A/B switch (same bits).
-    const bool v2 = !sw_present(SW_LAYER_V1);
-    const bool fast = P.K % MLP_BK == 0 && P.vec_a && (mode == MODE_PLAIN || (mode == MODE_GROUP && P.act == 1 && P.C == P.K));
-    if (v2 && fast && mode == MODE_PLAIN && wide && !sw_present(SW_WIDE_MIN_TILES)) {
-        // four workgroups per CU = 1024 resident tiles: with >= 1024 wide tiles the narrow tile (twice as many, half as long)
-        // runs in more, staggered rounds, so one round's store epilogue overlaps the next one's main loop (measured: 32768 x
-        // 512 -> 512 171 -> 160 us, 131072 x 256 -> 256 173 -> 167 us); between 384 and 1023 wide tiles the wide tile's better
-        // MFMA : LDS-read ratio wins (32768 x 512 -> 256: 74 vs 81 us)
-        const long tiles_wide = (long)prcnn_divup(P.rows, MLP_BM) * prcnn_divup(P.NB, 4);
-        wide = tiles_wide >= 384 && tiles_wide < 1024;
-    }
-    grid = dim3(prcnn_divup(P.rows, MLP_BM), prcnn_divup(P.NB, wide ? 4 : 2));
-    if (v2 && mode == MODE_PLAIN && !P.seg_cnt && P.xcd_tpf == 0 && !sw_present(SW_NO_WGM)) {
-        P.wgm_cols = (int)grid.y;
-        grid = dim3((unsigned)(prcnn_divup(grid.x, 8) * 8 * grid.y), 1);
-    }
-    // (fast = straight-line main loop, see mlp_layer_b_kernel: whole 32-wide chunks, 16-byte rows; grouped: the hoisted form only)
-#define MLP_LAUNCH_B(M, W, F)                                                                                            \
-    do {                                                                                                                 \
-        if (M == MODE_PLAIN && P.addY) hipLaunchKernelGGL((mlp_layer_b_kernel<M, W, F, (M == MODE_PLAIN)>), grid, dim3(MLP_THREADS), 0, s, P); \
-        else hipLaunchKernelGGL((mlp_layer_b_kernel<M, W, F, false>), grid, dim3(MLP_THREADS), 0, s, P);              \
-    } while (0)
-#define MLP_LAUNCH(M)                                                                                         \
-    do {                                                                                                      \
-        if (v2) {                                                                                             \
-            if (M != MODE_INTERP && fast) { if (wide) MLP_LAUNCH_B(M, 2, (M != MODE_INTERP)); else MLP_LAUNCH_B(M, 1, (M != MODE_INTERP)); } \
-            else if (wide) MLP_LAUNCH_B(M, 2, false);                                                         \
-            else MLP_LAUNCH_B(M, 1, false);                                                                   \
-        } else if (wide) hipLaunchKernelGGL((mlp_layer_kernel<M, 2>), grid, dim3(MLP_THREADS), 0, s, P);      \
-        else hipLaunchKernelGGL((mlp_layer_kernel<M, 1>), grid, dim3(MLP_THREADS), 0, s, P);                  \
-    } while (0)
-    if (mode == MODE_PLAIN) MLP_LAUNCH(MODE_PLAIN);
-    else if (mode == MODE_GROUP) MLP_LAUNCH(MODE_GROUP);
-    else MLP_LAUNCH(MODE_INTERP);
-#undef MLP_LAUNCH
-#undef MLP_LAUNCH_B
-    PRCNN_LAUNCH_CHECK("prcnn_mlp");
-    return PRCNN_OK;
-}
-
-PRCNN_API size_t prcnn_wpack_floats(int Nout, int K) {
-    if (Nout <= 0 || K <= 0) return 0;
-    return (size_t)((Nout + 31) / 32) * ((K + 7) / 8) * 256;
-}
-
-PRCNN_API int prcnn_pack_weight(const float* w, int Nout, int K, int k_rot, float* wpack, prcnn_stream_t stream) {
-    PRCNN_REQUIRE(w && wpack, "prcnn_pack_weight: null pointer");
-    PRCNN_REQUIRE(Nout > 0 && K > 0 && k_rot >= 0 && k_rot <= K, "prcnn_pack_weight: bad shape Nout=%d K=%d k_rot=%d", Nout, K, k_rot);
-    int KB = (K + 7) / 8, NB = (Nout + 31) / 32;
-    long total = (long)NB * KB * 256;
-    hipLaunchKernelGGL(pack_weight_kernel, dim3(prcnn_divup(total, 256)), dim3(256), 0, (hipStream_t)stream, w, Nout, K,
-                       k_rot, KB, NB, wpack);
-    PRCNN_LAUNCH_CHECK("prcnn_pack_weight");
-    return PRCNN_OK;
-}
-
-PRCNN_API size_t prcnn_wsplit_bytes(int Nout, int K) {
-    if (Nout <= 0 || K <= 0) return 0;
-    return (size_t)((Nout + 31) / 32) * ((K + 15) / 16) * 3 * 1024;
-}
-
-PRCNN_API int prcnn_pack_weight_split(const float* w, int Nout, int K, int chain, void* wsplit, prcnn_stream_t stream) {
-    PRCNN_REQUIRE(w && wsplit && aligned16(wsplit), "prcnn_pack_weight_split: null / misaligned pointer");
-    PRCNN_REQUIRE(Nout > 0 && K > 0 && (chain == 0 || chain == 1), "prcnn_pack_weight_split: bad shape Nout=%d K=%d chain=%d", Nout, K, chain);
-    const int KS = (K + 15) / 16, NB = (Nout + 31) / 32;
-    hipLaunchKernelGGL(pack_weight_split_kernel, dim3(prcnn_divup((long)NB * KS * 64, 256)), dim3(256), 0, (hipStream_t)stream, w,
-                       Nout, K, KS, NB, chain, reinterpret_cast<uint4*>(wsplit));
-    PRCNN_LAUNCH_CHECK("prcnn_pack_weight_split");
-    return PRCNN_OK;
-}
-
-// Two-layer plain-row chain on the split kernels; shapes: K = 128, nout[0] = 128, nout[1] = 1 or 65..128 (the RPN heads).
-// wchain[l]: prcnn_pack_weight_split(chain = 1) images; wpack1: the fp32 pack image of layer 1 (read by the single-channel output).
-// PRCNN_EUNSUPPORTED for any other shape: the caller issues prcnn_mlp_chain_rows.
-PRCNN_API int prcnn_mlp_chain_rows_split(const float* in, int ld_in, int64_t rows, int K, const void* const* wchain, const float* const* wpack,
-                                         const float* const* bias, const int* nout, const int* relu, int terms, float* out, int ld_out,
-                                         int col_off, prcnn_stream_t stream) {
-    PRCNN_REQUIRE(in && wchain && wpack && bias && nout && relu && out, "prcnn_mlp_chain_rows_split: null pointer");
-    PRCNN_REQUIRE(terms == 3 || terms == 6, "prcnn_mlp_chain_rows_split: terms=%d (3 or 6)", terms);
-    PRCNN_REQUIRE(wpack[0] && wpack[1] && aligned16(wpack[0]) && aligned16(wpack[1]), "prcnn_mlp_chain_rows_split: the fp32 pack images of both layers are needed (non-finite rows, single-channel output)");
-    const float* wpack1 = wpack[1];
-    const bool ok = K == 128 && nout[0] == 128 && (nout[1] == 1 || (nout[1] > 64 && nout[1] <= 128)) && aligned16(in) && ld_in % 4 == 0 &&
-                    ld_in >= K && wchain[0] && (nout[1] == 1 || wchain[1] != nullptr);
-    if (!ok) return PRCNN_EUNSUPPORTED;
-    PRCNN_REQUIRE(ld_out >= col_off + nout[1], "prcnn_mlp_chain_rows_split: ld_out=%d < col_off+Nout", ld_out);
-    if (rows == 0) return PRCNN_OK;
-    ChainParams C = {};
-    MlpParams& P = C.a;
-    P.rows = rows; P.K = K; P.in = in; P.ld_in = ld_in; P.bias = bias[0]; P.Nout = nout[0]; P.relu = relu[0];
-    P.out = out; P.ld_out = ld_out; P.col_off = col_off; P.rows_unit = 1;
-    P.wsplit = wchain[0]; P.split_terms = terms; P.wpack = wpack[0];
-    C.wsplit1 = wchain[1]; C.wpack1 = wpack1; C.bias1 = bias[1]; C.N1 = nout[1]; C.relu1 = relu[1]; C.KB1 = 16; C.nlayers = 2;
-    const dim3 grid(prcnn_divup(rows, 128));
-    const hipStream_t s = (hipStream_t)stream;
-#define SCH_LAUNCH(NB1)                                                                                        \
-    do {                                                                                                       \
-        /* plain rows, two layers: the lane-is-a-row kernel stays the default (its 32 rows are 16 contiguous KB that the 16 k-steps */ \
-        /* re-read from L1: 168 vs 179 us for the reg head); PRCNN_CHAIN_COOP=2 selects the cooperative form (same bits)            */ \
-        if (terms == 6 && chain_coop_forced()) hipLaunchKernelGGL((mlp_chain_c_kernel<MODE_PLAIN, NB1, 6>), grid, dim3(256), 0, s, C); \
-        else if (terms == 6) hipLaunchKernelGGL((mlp_chain_s_kernel<MODE_PLAIN, NB1, 6>), grid, dim3(256), 0, s, C); \
-        else hipLaunchKernelGGL((mlp_chain_s_kernel<MODE_PLAIN, NB1, 3>), grid, dim3(256), 0, s, C);            \
-    } while (0)
-    if (nout[1] == 1 && terms == 6 && chain_coop_on() && chain_persist_on() && (long)rows * ld_in < (1L << 30)) {
-        const int rc = launch_chain_p<MODE_PLAIN, 1>(C, s);                     // (row offsets in floats fit 32 bits)
-        if (rc) return rc;
-    } else if (nout[1] == 1) SCH_LAUNCH(1);
-    else if (nout[1] <= 96) SCH_LAUNCH(3);
-    else SCH_LAUNCH(4);
-#undef SCH_LAUNCH
-    PRCNN_LAUNCH_CHECK("prcnn_mlp_chain_rows_split");
-    return PRCNN_OK;
-}
-
-PRCNN_API int prcnn_mlp_rows_split(const float* in, int ld_in, int64_t rows, int K, const float* wpack, const void* wsplit, int terms,
-                                   const float* bias, int Nout, int relu, float* out, int ld_out, int col_off, int pool_ns,
-                                   const int32_t* rows_dev, int rows_unit, const int32_t* seg_cnt, int seg_rows, prcnn_stream_t stream) {
-    PRCNN_REQUIRE(in && wsplit, "prcnn_mlp_rows_split: null pointer");
-    PRCNN_REQUIRE(ld_in >= K && ld_out >= col_off + Nout, "prcnn_mlp_rows_split: bad strides ld_in=%d K=%d ld_out=%d", ld_in, K, ld_out);
-    PRCNN_REQUIRE(terms == 3 || terms == 6, "prcnn_mlp_rows_split: terms=%d (3 or 6)", terms);
-    MlpParams P = {};
-    P.rows = rows; P.K = K; P.wpack = wpack; P.bias = bias; P.Nout = Nout; P.relu = relu;
-    P.out = out; P.ld_out = ld_out; P.col_off = col_off; P.pool_ns = pool_ns;
-    P.in = in; P.ld_in = ld_in;
-    P.vec_a = aligned16(in) && (ld_in % 4 == 0);
-    P.rows_dev = rows_dev; P.rows_unit = rows_unit > 0 ? rows_unit : 1;
-    PRCNN_REQUIRE(!seg_cnt || (seg_rows > 0 && seg_rows % MLP_BM == 0 && rows % seg_rows == 0 && pool_ns == 0 && !rows_dev),
-                  "prcnn_mlp_rows_split: seg_rows=%d must be a multiple of %d dividing rows (no pooling, no rows_dev)", seg_rows, MLP_BM);
-    P.seg_cnt = seg_cnt; P.seg_rows = seg_rows;
-    P.wsplit = wsplit; P.split_terms = terms;
-    return launch_mlp(MODE_PLAIN, P, (hipStream_t)stream);
-}
-
-PRCNN_API int prcnn_mlp_rows_addinterp_split(const float* in, int ld_in, int K, const float* wpack, const void* wsplit, int terms,
-                                             const float* bias, int Nout, int relu, const float* y_cl, int ld_y, const int32_t* idx3,
-                                             const float* w3, int B, int n, int m, float* out, int ld_out, int col_off,
-                                             prcnn_stream_t stream) {
-    PRCNN_REQUIRE(in && y_cl && idx3 && w3 && wsplit, "prcnn_mlp_rows_addinterp_split: null pointer");
-    PRCNN_REQUIRE(B >= 0 && n > 0 && m > 0 && ld_in >= K && ld_y >= Nout && ld_out >= col_off + Nout,
-                  "prcnn_mlp_rows_addinterp_split: bad shape B=%d n=%d m=%d K=%d Nout=%d", B, n, m, K, Nout);
-    PRCNN_REQUIRE(terms == 3 || terms == 6, "prcnn_mlp_rows_addinterp_split: terms=%d (3 or 6)", terms);
-    MlpParams P = {};
-    P.rows = (long)B * n; P.K = K; P.wpack = wpack; P.bias = bias; P.Nout = Nout; P.relu = relu;
-    P.out = out; P.ld_out = ld_out; P.col_off = col_off; P.pool_ns = 0;
-    P.in = in; P.ld_in = ld_in;
-    P.vec_a = aligned16(in) && (ld_in % 4 == 0);
-    P.addY = y_cl; P.ldY = ld_y; P.idx3 = idx3; P.w3 = w3; P.n = n; P.m = m;
-    P.addy_phase = (int)sw_num(SW_ADDY_PHASE, 2);      // A/B switch: 0 = all in the epilogue
-    P.rows_unit = 1;
-    P.wsplit = wsplit; P.split_terms = terms;
-    return launch_mlp(MODE_PLAIN, P, (hipStream_t)stream);
-}
-
-PRCNN_API int prcnn_mlp_rows(const float* in, int ld_in, int64_t rows, int K, const float* wpack, const float* bias,
-                             int Nout, int relu, float* out, int ld_out, int col_off, int pool_ns,
-                             const int32_t* rows_dev, int rows_unit, const int32_t* seg_cnt, int seg_rows,
-                             prcnn_stream_t stream) {
-    PRCNN_REQUIRE(in, "prcnn_mlp_rows: null input");
-    PRCNN_REQUIRE(ld_in >= K && ld_out >= col_off + Nout, "prcnn_mlp_rows: bad strides ld_in=%d K=%d ld_out=%d", ld_in, K, ld_out);
-    MlpParams P = {};
-    P.rows = rows; P.K = K; P.wpack = wpack; P.bias = bias; P.Nout = Nout; P.relu = relu;
-    P.out = out; P.ld_out = ld_out; P.col_off = col_off; P.pool_ns = pool_ns;
-    P.in = in; P.ld_in = ld_in;
-    P.vec_a = aligned16(in) && (ld_in % 4 == 0);
-    P.rows_dev = rows_dev; P.rows_unit = rows_unit > 0 ? rows_unit : 1;
-    PRCNN_REQUIRE(!seg_cnt || (seg_rows > 0 && seg_rows % MLP_BM == 0 && rows % seg_rows == 0 && pool_ns == 0 && !rows_dev),
-                  "prcnn_mlp_rows: seg_rows=%d must be a multiple of %d dividing rows (no pooling, no rows_dev)", seg_rows, MLP_BM);
-    P.seg_cnt = seg_cnt; P.seg_rows = seg_rows;
-    return launch_mlp(MODE_PLAIN, P, (hipStream_t)stream);
-}
-
-// act_wx / act_bias non-null: hoisted first layer -- feat_cl is Z = W_f . feat per source point (C = width of that
-// layer), the A row is relu(Z[idx] + act_wx . dxyz + act_bias) and K = C.
-static int set_group_act(MlpParams& P, const float* act_wx, const float* act_bias, int C) {
-    if (!act_wx && !act_bias) return PRCNN_OK;
-    PRCNN_REQUIRE(act_wx && act_bias && C > 0, "prcnn_mlp_group: act_wx and act_bias must both be given (C > 0)");
-    PRCNN_REQUIRE(aligned16(act_wx) && aligned16(act_bias) && C % 4 == 0,
-                  "prcnn_mlp_group: hoisted mode needs 16-byte aligned act_wx/act_bias and C %% 4 == 0 (C=%d)", C);
-    P.act = 1; P.act_wx = act_wx; P.act_bias = act_bias; P.K = C;
-    return PRCNN_OK;
-}
-
-PRCNN_API int prcnn_mlp_rows_addinterp(const float* in, int ld_in, int K, const float* wpack, const float* bias, int Nout,
-                                       int relu, const float* y_cl, int ld_y, const int32_t* idx3, const float* w3, int B,
-                                       int n, int m, float* out, int ld_out, int col_off, prcnn_stream_t stream) {
-    PRCNN_REQUIRE(in && y_cl && idx3 && w3, "prcnn_mlp_rows_addinterp: null pointer");
-    PRCNN_REQUIRE(B >= 0 && n > 0 && m > 0 && ld_in >= K && ld_y >= Nout && ld_out >= col_off + Nout,
-                  "prcnn_mlp_rows_addinterp: bad shape B=%d n=%d m=%d K=%d Nout=%d", B, n, m, K, Nout);
-    MlpParams P = {};
-    P.rows = (long)B * n; P.K = K; P.wpack = wpack; P.bias = bias; P.Nout = Nout; P.relu = relu;
-    P.out = out; P.ld_out = ld_out; P.col_off = col_off; P.pool_ns = 0;
-    P.in = in; P.ld_in = ld_in;
-    P.vec_a = aligned16(in) && (ld_in % 4 == 0);
-    P.addY = y_cl; P.ldY = ld_y; P.idx3 = idx3; P.w3 = w3; P.n = n; P.m = m;
-    P.addy_phase = (int)sw_num(SW_ADDY_PHASE, 2);      // A/B switch: 0 = all in the epilogue
-    return launch_mlp(MODE_PLAIN, P, (hipStream_t)stream);
-}
-
-PRCNN_API int prcnn_mlp_group(const float* xyz, const float* new_xyz, const int32_t* idx, const float* feat_cl,
-                              int ld_feat, int B, int N, int M, int nsample, int C, const float* act_wx,
-                              const float* act_bias, const float* wpack, const float* bias, int Nout, int relu,
-                              float* out, int ld_out, int col_off, int pool_ns, const int32_t* groups_dev, prcnn_stream_t stream) {
-    PRCNN_REQUIRE(xyz && idx, "prcnn_mlp_group: null pointer");
-    PRCNN_REQUIRE(C == 0 || feat_cl, "prcnn_mlp_group: C=%d but feat_cl is null", C);
-    PRCNN_REQUIRE(B >= 0 && N > 0 && M > 0 && nsample > 0 && C >= 0 && (C == 0 || ld_feat >= C),
-                  "prcnn_mlp_group: bad shape B=%d N=%d M=%d ns=%d C=%d ld=%d", B, N, M, nsample, C, ld_feat);
-    PRCNN_REQUIRE(ld_out >= col_off + Nout, "prcnn_mlp_group: ld_out=%d < col_off+Nout", ld_out);
-    MlpParams P = {};
-    P.rows = (long)B * M * nsample; P.K = C + 3; P.wpack = wpack; P.bias = bias; P.Nout = Nout; P.relu = relu;
-    P.out = out; P.ld_out = ld_out; P.col_off = col_off; P.pool_ns = pool_ns;
-    P.rows_dev = groups_dev; P.rows_unit = nsample;
-    P.xyz = xyz; P.new_xyz = new_xyz; P.idx = idx; P.feat = feat_cl; P.ld_feat = ld_feat;
-    P.N = N; P.M = M; P.ns = nsample; P.C = C;
-    P.vec_a = C > 0 && aligned16(feat_cl) && (ld_feat % 4 == 0);
-    int rc = set_group_act(P, act_wx, act_bias, C);
-    if (rc) return rc;
-    return launch_mlp(MODE_GROUP, P, (hipStream_t)stream);
-}
-
-// prcnn_mlp_group's hoisted form on the split-bf16 layer kernel (wsplit = prcnn_pack_weight_split image of the layer, terms 3 / 6; wpack:
-// the fp32 image, read only by rows that hold inf / NaN).  C a multiple of 32, 16-byte aligned feature rows; otherwise, or with
-// PRCNN_GROUP_SPLIT=0, the call runs the fp32 layer kernel exactly as prcnn_mlp_group does.
-PRCNN_API int prcnn_mlp_group_split(const float* xyz, const float* new_xyz, const int32_t* idx, const float* feat_cl,
-                                    int ld_feat, int B, int N, int M, int nsample, int C, const float* act_wx,
-                                    const float* act_bias, const float* wpack, const void* wsplit, int terms, const float* bias, int Nout,
-                                    int relu, float* out, int ld_out, int col_off, int pool_ns, const int32_t* groups_dev,
-                                    prcnn_stream_t stream) {
-    PRCNN_REQUIRE(xyz && idx && wsplit, "prcnn_mlp_group_split: null pointer");
-    PRCNN_REQUIRE(C > 0 && feat_cl, "prcnn_mlp_group_split: the hoisted form needs features (C=%d)", C);
-    PRCNN_REQUIRE(B >= 0 && N > 0 && M > 0 && nsample > 0 && ld_feat >= C,
-                  "prcnn_mlp_group_split: bad shape B=%d N=%d M=%d ns=%d C=%d ld=%d", B, N, M, nsample, C, ld_feat);
-    PRCNN_REQUIRE(terms == 3 || terms == 6, "prcnn_mlp_group_split: terms=%d (3 or 6)", terms);
-    PRCNN_REQUIRE(ld_out >= col_off + Nout, "prcnn_mlp_group_split: ld_out=%d < col_off+Nout", ld_out);
-    MlpParams P = {};
-    P.rows = (long)B * M * nsample; P.K = C + 3; P.wpack = wpack; P.bias = bias; P.Nout = Nout; P.relu = relu;
-    P.out = out; P.ld_out = ld_out; P.col_off = col_off; P.pool_ns = pool_ns;
-    P.rows_dev = groups_dev; P.rows_unit = nsample;
-    P.xyz = xyz; P.new_xyz = new_xyz; P.idx = idx; P.feat = feat_cl; P.ld_feat = ld_feat;
-    P.N = N; P.M = M; P.ns = nsample; P.C = C;
-    P.vec_a = C > 0 && aligned16(feat_cl) && (ld_feat % 4 == 0);
-    int rc = set_group_act(P, act_wx, act_bias, C);
-    if (rc) return rc;
-    P.wsplit = wsplit; P.split_terms = terms;
-    return launch_mlp(MODE_GROUP, P, (hipStream_t)stream);
-}
-
-// act_bias non-null (requires C1 == 0): hoisted first layer -- known_cl is Y = W . known per known point, the A row
-// is relu(interp(Y) + act_bias).
-static int set_interp_act(MlpParams& P, const float* act_bias, int C2, int C1) {
-    if (!act_bias) return PRCNN_OK;
-    PRCNN_REQUIRE(C1 == 0 && aligned16(act_bias) && C2 % 4 == 0,
-                  "prcnn_mlp_interp: hoisted mode needs C1 == 0, aligned act_bias and C2 %% 4 == 0 (C2=%d C1=%d)", C2, C1);
-    P.act = 2; P.act_bias = act_bias;
-    return PRCNN_OK;
-}
-
-PRCNN_API int prcnn_mlp_interp(const float* known_cl, int ld_known, const int32_t* idx3, const float* w3,
-                               const float* skip_cl, int ld_skip, int B, int n, int m, int C2, int C1,
-                               const float* act_bias, const float* wpack, const float* bias, int Nout, int relu,
-                               float* out, int ld_out, int col_off, prcnn_stream_t stream) {
-    PRCNN_REQUIRE(known_cl && idx3 && w3, "prcnn_mlp_interp: null pointer");
-    PRCNN_REQUIRE(C1 == 0 || skip_cl, "prcnn_mlp_interp: C1=%d but skip_cl is null", C1);
-    PRCNN_REQUIRE(B >= 0 && n > 0 && m > 0 && C2 > 0 && C1 >= 0 && ld_known >= C2 && (C1 == 0 || ld_skip >= C1),
-                  "prcnn_mlp_interp: bad shape B=%d n=%d m=%d C2=%d C1=%d", B, n, m, C2, C1);
-    PRCNN_REQUIRE(ld_out >= col_off + Nout, "prcnn_mlp_interp: ld_out=%d < col_off+Nout", ld_out);
-    MlpParams P = {};
-    P.rows = (long)B * n; P.K = C2 + C1; P.wpack = wpack; P.bias = bias; P.Nout = Nout; P.relu = relu;
-    P.out = out; P.ld_out = ld_out; P.col_off = col_off; P.pool_ns = 0;
-    P.known = known_cl; P.idx3 = idx3; P.w3 = w3; P.skip = skip_cl; P.ld_known = ld_known; P.ld_skip = ld_skip;
-    P.n = n; P.m = m; P.C2 = C2; P.C1 = C1;
-    P.vec_a = aligned16(known_cl) && (ld_known % 4 == 0);
-    P.vec_b = C1 > 0 && aligned16(skip_cl) && (ld_skip % 4 == 0) && (C2 % 4 == 0);
-    int rc = set_interp_act(P, act_bias, C2, C1);
-    if (rc) return rc;
-    return launch_mlp(MODE_INTERP, P, (hipStream_t)stream);
-}
-
-PRCNN_API int prcnn_maxpool_rows(const float* in, int ld_in, int64_t rows_out, int ns, int C, float* out, int ld_out,
-                                 int col_off, prcnn_stream_t stream) {
-    PRCNN_REQUIRE(in && out, "prcnn_maxpool_rows: null pointer");
-    PRCNN_REQUIRE(rows_out >= 0 && ns > 0 && C > 0 && ld_in >= C && ld_out >= col_off + C, "prcnn_maxpool_rows: bad shape");
-    if (rows_out == 0) return PRCNN_OK;
-    hipLaunchKernelGGL(maxpool_rows_kernel, dim3(prcnn_divup(rows_out * C, 256)), dim3(256), 0, (hipStream_t)stream, in,
-                       ld_in, (long)rows_out, ns, C, out, ld_out, col_off);
-    PRCNN_LAUNCH_CHECK("prcnn_maxpool_rows");
-    return PRCNN_OK;
-}
-
-// ---- chain launcher -----------------------------------------------------------------------------
-template <int MODE, int NB0, int NB1, int NB2>
-static void launch_chain(const ChainParams& C, hipStream_t s) {
-    dim3 grid(prcnn_divup(C.a.rows, 128));
-    hipLaunchKernelGGL((mlp_chain_kernel<MODE, NB0, NB1, NB2>), grid, dim3(256), 0, s, C);
-}
-template <int MODE, int NB0, int NB1, int NB2>
-static void launch_chain_fast(const ChainParams& C, hipStream_t s) {
-    dim3 grid(prcnn_divup(C.a.rows, 128));
-    hipLaunchKernelGGL((mlp_chain_fast_kernel<MODE, NB0, NB1, NB2>), grid, dim3(256), 0, s, C);
-}
-
-// the straight-line variant applies when nothing in the layer-0 loop needs a bounds check (see mlp_chain_fast_kernel)
-static bool chain_fast_ok(int mode, const ChainParams& C, int n0, int n1, int n2) {
-    const MlpParams& P = C.a;
-    if (P.K % 8 != 0 || P.K > FAST_MAX_K || P.K < 16 || !P.vec_a || P.addY) return false;
-    const int G0 = n0 == 3 ? 4 : CH_STAGE_TILES / n0;
-    if ((P.K / 8) % G0 != 0) return false;
-    if (n1 > 0 && P.Nout != n0 * 32) return false;                 // KB of layer 1 == 4 * NB0
-    if (n2 > 0 && C.N1 != n1 * 32) return false;
-    if (n1 > 0 && (n0 * 4) % (n1 == 3 ? 4 : CH_STAGE_TILES / n1) != 0) return false;
-    if (n2 > 0 && (n1 * 4) % (n2 == 3 ? 4 : CH_STAGE_TILES / n2) != 0) return false;
-    if (mode == MODE_GROUP) return P.act == 1 && P.K == P.C && P.act_wx && P.act_bias;
-    if (mode == MODE_INTERP) return P.act == 2 && P.C1 == 0 && P.K == P.C2 && P.act_bias;
-    return mode == MODE_PLAIN;
-}
-
-static int nb32(int n) { return (n + 31) / 32; }
 
 // =====================================================================================================
 // Two-layer STACK for short row lists (round 2): the wide SA levels (SA3 / SA4: 128 -> 196 -> 256, 256 -> 256|384 -> 512) run
@@ -3331,260 +2935,8 @@ __global__ __launch_bounds__(256, 1) void mlp_rows32_kernel(const MlpParams Pin,
     }
 }
 
-static bool rows32_ok(int mode, const MlpParams& P) {
-    return !sw_present(SW_NO_ROWS32) && mode == MODE_PLAIN && !P.addY && P.pool_ns == 0 && !P.seg_cnt && P.vec_a && P.K % 8 == 0 && P.K >= 256 &&
-           P.K <= R32_MAX_K && P.Nout >= 128 && P.rows <= 4096;
-}
-
-static int launch_rows32(MlpParams& P, hipStream_t s) {
-    static PrcnnLdsLimit attr;
-    if (!attr.raise((const void*)mlp_rows32_kernel, 144 * 1024))
-        return prcnn_fail(PRCNN_EHIP, "prcnn_mlp(rows32): cannot raise the dynamic LDS limit");
-    const int split_max = prcnn_divup(P.NB, 4);
-    const size_t lds = (size_t)ST_ROWS * (P.K + 4) * sizeof(float);
-    hipLaunchKernelGGL(mlp_rows32_kernel, dim3((unsigned)min((long)prcnn_divup(P.rows, ST_ROWS) * split_max, 2048L)), dim3(256), lds, s,
-                       P, split_max);
-    PRCNN_LAUNCH_CHECK("prcnn_mlp(rows32)");
-    return PRCNN_OK;
-}
-
-// shapes the stack kernel takes (hoisted grouped form on flat row lists, no pooling)
-static bool stack2_ok(int mode, const ChainParams& C) {
-    const MlpParams& P = C.a;
-    return mode == MODE_GROUP && C.nlayers == 2 && P.act == 1 && P.pool_ns == 0 && P.ns == 1 && P.C == P.K && P.K % 8 == 0 &&
-           P.K <= ST_MAX_K0 && P.vec_a && (P.Nout > 128 || C.N1 > 128) && nb32(P.Nout) <= ST_MAX_NB0 && nb32(C.N1) <= 16;
-}
-
-template <int NBW0>
-static void launch_stack2(const ChainParams& C, hipStream_t s) {
-    const size_t lds = (size_t)ST_ROWS * ((C.a.K + 4) + (nb32(C.a.Nout) * 32 + 4)) * sizeof(float);
-    hipLaunchKernelGGL((mlp_stack2_kernel<NBW0>), dim3((unsigned)min((long)prcnn_divup(C.a.rows, ST_ROWS) * C.stack_split, 2048L)), dim3(256), lds, s, C);
-}
-
-static bool chain_instance_exists(int mode, int n0, int n1, int n2) {
-    struct { int m, a, b, c; } T[] = {{MODE_GROUP, 1, 1, 1}, {MODE_GROUP, 1, 1, 2}, {MODE_GROUP, 2, 2, 4}, {MODE_GROUP, 2, 3, 4},
-                                      {MODE_GROUP, 2, 4, 0}, {MODE_GROUP, 3, 4, 0},          // hoisted SA2 stacks
-                                      {MODE_INTERP, 4, 4, 0}, {MODE_INTERP, 4, 0, 0},        // FP0 / hoisted FP0
-                                      {MODE_PLAIN, 4, 4, 0}, {MODE_PLAIN, 4, 1, 0}, {MODE_PLAIN, 4, 3, 0}};
-    for (auto& t : T)
-        if (t.m == mode && t.a == n0 && t.b == n1 && t.c == n2) return true;
-    return false;
-}
-
-PRCNN_API int prcnn_mlp_chain_supported(int mode, int nlayers, const int* nout, int pool_ns) {
-    if (!nout || nlayers < 1 || nlayers > 3) return 0;
-    if (!(pool_ns == 0 || pool_ns == 16 || pool_ns == 32)) return 0;
-    // two wide layers on an un-pooled grouped list: the stack kernel (hoisted form, nsample 1 -- checked again at dispatch)
-    if (mode == MODE_GROUP && nlayers == 2 && pool_ns == 0 && nout[0] > 0 && nout[1] > 0 && (nout[0] > 128 || nout[1] > 128) &&
-        nb32(nout[0]) <= ST_MAX_NB0 && nb32(nout[1]) <= 16 && !sw_present(SW_NO_STACK))
-        return 1;
-    for (int l = 0; l < nlayers; l++)
-        if (nout[l] <= 0 || nout[l] > 128) return 0;
-    return chain_instance_exists(mode, nb32(nout[0]), nlayers > 1 ? nb32(nout[1]) : 0, nlayers > 2 ? nb32(nout[2]) : 0) ? 1 : 0;
-}
-
-// returns PRCNN_EUNSUPPORTED when no instance matches
-static int dispatch_chain(int mode, ChainParams& C, hipStream_t s) {
-    MlpParams& P = C.a;
-    P.KB = (P.K + 7) / 8;
-    P.NB = nb32(P.Nout);
-    const int n0 = nb32(P.Nout), n1 = C.nlayers > 1 ? nb32(C.N1) : 0, n2 = C.nlayers > 2 ? nb32(C.N2) : 0;
-    if (C.nlayers > 1) C.KB1 = (P.Nout + 7) / 8;
-    if (C.nlayers > 2) C.KB2 = (C.N1 + 7) / 8;
-    if (P.rows == 0) return PRCNN_OK;
-    if (stack2_ok(mode, C)) {
-        // stack_split = the most workgroups a row tile's layer-B column groups may be dealt to; the kernel picks the split
-        // from the device-side row count
-        const int nbw0 = prcnn_divup(n0, 4);
-        C.stack_split = prcnn_divup(n1, 4);
-        static PrcnnLdsLimit attr[3];
-#define STACK_CASE(A)                                                                                                    \
-        if (nbw0 == A) {                                                                                                 \
-            if (!attr[A - 1].raise((const void*)mlp_stack2_kernel<A>, 96 * 1024))                                        \
-                return prcnn_fail(PRCNN_EHIP, "prcnn_mlp_chain(stack): cannot raise the dynamic LDS limit");             \
-            launch_stack2<A>(C, s);                                                                                      \
-            PRCNN_LAUNCH_CHECK("prcnn_mlp_chain(stack)");                                                                \
-            return PRCNN_OK;                                                                                             \
-        }
-        STACK_CASE(1) STACK_CASE(2) STACK_CASE(3)
-#undef STACK_CASE
-    }
-    // SA level 0: xyz-only rows, three narrow layers, pooled -- persistent register-weight kernel
-    // (pooled groups, or -- nsample 1, no pooling -- the flat row list of the padding-free path: the same kernel writes rows)
-    if (mode == MODE_GROUP && P.C == 0 && !P.act && P.K == 3 && C.nlayers == 3 && P.new_xyz &&
-        (P.pool_ns == P.ns || (P.pool_ns == 0 && P.ns == 1)) && C.N2 % 4 == 0 &&
-        !sw_present(SW_NO_SA0)) {              // (A/B switch; the generic chain kernel gives the same bits)
-        // persistent: one resident workgroup per occupancy slot (256 CUs x 3 or 2 workgroups at 115 / 243 registers)
-#define SA0_CASE(W0, W1, NBL, NSV)                                                                                        \
-        if (P.Nout == W0 && C.N1 == W1 && n2 == NBL && P.ns == NSV) {                                                   \
-            const int grid = (int)min((long)(NBL == 1 ? 768 : 512), (long)prcnn_divup(P.rows, 128));                     \
-            hipLaunchKernelGGL((sa_xyz_chain_kernel<W0 / 8, W1 / 8, NBL, NSV>), dim3(grid), dim3(256), 0, s, C);          \
-            PRCNN_LAUNCH_CHECK("prcnn_mlp_chain(sa0)");                                                                  \
-            return PRCNN_OK;                                                                                             \
-        }
-        SA0_CASE(16, 16, 1, 16)
-        SA0_CASE(32, 32, 2, 32)
-        SA0_CASE(16, 16, 1, 1)
-        SA0_CASE(32, 32, 2, 1)
-#undef SA0_CASE
-    }
-    // Opt-in (PRCNN_PERSISTENT_CHAIN=1): 6-12 % faster per launch with ONE batch in flight, but a persistent workgroup
-    // holds its CU's LDS for the whole kernel, which starves the other in-flight batches' kernels (FPS sort, layer tiles):
-    // measured -6 % RPN throughput at 3 batches in flight, so the default keeps the per-tile workgroups.
-    if (chain_fast_ok(mode, C, n0, n1, n2) && !P.seg_cnt && sw_present(SW_PERSISTENT_CHAIN)) {
-        // persistent form: weights of the whole stack resident in LDS, one 8-wave workgroup per CU
-#define PERS_CASE(M, KB0V, A, B, CC)                                                                                         \
-        if (mode == M && P.KB == KB0V && n0 == A && n1 == B && n2 == CC) {                                                    \
-            constexpr size_t lds = pers_lds_bytes<M, KB0V, A, B, CC>();                                                       \
-            static PrcnnLdsLimit attr;                                                                                       \
-            if (!attr.raise((const void*)mlp_chain_pers_kernel<M, KB0V, A, B, CC>, (int)lds))                                \
-                return prcnn_fail(PRCNN_EHIP, "prcnn_mlp_chain: cannot raise the dynamic LDS limit");                        \
-            const int grid = (int)min((long)256, (long)prcnn_divup(P.rows, 32 * PERS_WAVES));                                \
-            hipLaunchKernelGGL((mlp_chain_pers_kernel<M, KB0V, A, B, CC>), dim3(grid), dim3(PERS_WAVES * 64), lds, s, C);     \
-            PRCNN_LAUNCH_CHECK("prcnn_mlp_chain(persistent)");                                                               \
-            return PRCNN_OK;                                                                                                 \
-        }
-        PERS_CASE(MODE_GROUP, 8, 2, 4, 0)
-        PERS_CASE(MODE_GROUP, 8, 3, 4, 0)
-        PERS_CASE(MODE_INTERP, 16, 4, 0, 0)
-        PERS_CASE(MODE_PLAIN, 16, 4, 1, 0)
-        PERS_CASE(MODE_PLAIN, 16, 4, 3, 0)
-#undef PERS_CASE
-    }
-    if (chain_fast_ok(mode, C, n0, n1, n2) && !sw_present(SW_NO_FAST_CHAIN)) {      // (A/B switch, same bits)
-#define FAST_CASE(M, A, B, CC) if (mode == M && n0 == A && n1 == B && n2 == CC) { launch_chain_fast<M, A, B, CC>(C, s); PRCNN_LAUNCH_CHECK("prcnn_mlp_chain(fast)"); return PRCNN_OK; }
-        FAST_CASE(MODE_GROUP, 2, 4, 0)
-        FAST_CASE(MODE_GROUP, 3, 4, 0)
-        FAST_CASE(MODE_INTERP, 4, 0, 0)
-        FAST_CASE(MODE_PLAIN, 4, 1, 0)
-        FAST_CASE(MODE_PLAIN, 4, 3, 0)
-        FAST_CASE(MODE_PLAIN, 4, 4, 0)
-#undef FAST_CASE
-    }
-#define CHAIN_CASE(M, A, B, CC) if (mode == M && n0 == A && n1 == B && n2 == CC) { launch_chain<M, A, B, CC>(C, s); PRCNN_LAUNCH_CHECK("prcnn_mlp_chain"); return PRCNN_OK; }
-    CHAIN_CASE(MODE_GROUP, 1, 1, 1)
-    CHAIN_CASE(MODE_GROUP, 1, 1, 2)
-    CHAIN_CASE(MODE_GROUP, 2, 2, 4)
-    CHAIN_CASE(MODE_GROUP, 2, 3, 4)
-    CHAIN_CASE(MODE_GROUP, 2, 4, 0)
-    CHAIN_CASE(MODE_GROUP, 3, 4, 0)
-    CHAIN_CASE(MODE_INTERP, 4, 4, 0)
-    CHAIN_CASE(MODE_INTERP, 4, 0, 0)
-    CHAIN_CASE(MODE_PLAIN, 4, 4, 0)
-    CHAIN_CASE(MODE_PLAIN, 4, 1, 0)
-    CHAIN_CASE(MODE_PLAIN, 4, 3, 0)
-#undef CHAIN_CASE
-    return prcnn_fail(PRCNN_EUNSUPPORTED, "prcnn_mlp_chain: no register-chain instance for mode %d widths (%d,%d,%d)/32", mode, n0, n1, n2);
-}
-
-static int fill_chain(ChainParams& C, int nlayers, const float* const* wpack, const float* const* bias, const int* nout,
-                      const int* relu, float* out, int ld_out, int col_off, int pool_ns) {
-    PRCNN_REQUIRE(nlayers >= 1 && nlayers <= 3, "prcnn_mlp_chain: nlayers=%d (1..3)", nlayers);
-    PRCNN_REQUIRE(wpack && bias && nout && relu && out, "prcnn_mlp_chain: null pointer");
-    for (int l = 0; l < nlayers; l++) {
-        PRCNN_REQUIRE(wpack[l] && aligned16(wpack[l]), "prcnn_mlp_chain: layer %d wpack null/unaligned", l);
-        PRCNN_REQUIRE(bias[l] == nullptr || aligned16(bias[l]), "prcnn_mlp_chain: layer %d bias must be 16-byte aligned and padded to a multiple of 32", l);
-        PRCNN_REQUIRE(nout[l] > 0 && nout[l] <= 512, "prcnn_mlp_chain: layer %d width %d (1..512)", l, nout[l]);
-    }
-    PRCNN_REQUIRE(pool_ns == 0 || pool_ns == 16 || pool_ns == 32, "prcnn_mlp_chain: pool_ns=%d (0/16/32)", pool_ns);
-    PRCNN_REQUIRE(ld_out >= col_off + nout[nlayers - 1], "prcnn_mlp_chain: ld_out too small");
-    C.nlayers = nlayers;
-    C.a.wpack = wpack[0]; C.a.bias = bias[0]; C.a.Nout = nout[0]; C.a.relu = relu[0];
-    if (nlayers > 1) { C.wpack1 = wpack[1]; C.bias1 = bias[1]; C.N1 = nout[1]; C.relu1 = relu[1]; }
-    if (nlayers > 2) { C.wpack2 = wpack[2]; C.bias2 = bias[2]; C.N2 = nout[2]; C.relu2 = relu[2]; }
-    C.a.out = out; C.a.ld_out = ld_out; C.a.col_off = col_off; C.a.pool_ns = pool_ns;
-    return PRCNN_OK;
-}
-
-PRCNN_API int prcnn_mlp_chain_rows(const float* in, int ld_in, int64_t rows, int K, int nlayers,
-                                   const float* const* wpack, const float* const* bias, const int* nout,
-                                   const int* relu, float* out, int ld_out, int col_off, int pool_ns,
-                                   const int32_t* seg_cnt, int seg_rows, prcnn_stream_t stream) {
-    PRCNN_REQUIRE(in && ld_in >= K && K > 0 && rows >= 0, "prcnn_mlp_chain_rows: bad input");
-    PRCNN_REQUIRE(!seg_cnt || (seg_rows > 0 && seg_rows % 128 == 0 && rows % seg_rows == 0 && pool_ns == 0),
-                  "prcnn_mlp_chain_rows: seg_rows=%d must be a multiple of 128 dividing rows (and no pooling)", seg_rows);
-    ChainParams C = {};
-    int rc = fill_chain(C, nlayers, wpack, bias, nout, relu, out, ld_out, col_off, pool_ns);
-    if (rc) return rc;
-    PRCNN_REQUIRE(pool_ns == 0 || rows % pool_ns == 0, "prcnn_mlp_chain_rows: rows not a multiple of pool_ns");
-    C.a.rows = rows; C.a.K = K; C.a.in = in; C.a.ld_in = ld_in;
-    C.a.vec_a = aligned16(in) && (ld_in % 4 == 0);
-    C.a.seg_cnt = seg_cnt; C.a.seg_rows = seg_rows;
-    return dispatch_chain(MODE_PLAIN, C, (hipStream_t)stream);
-}
-
-PRCNN_API int prcnn_mlp_chain_group(const float* xyz, const float* new_xyz, const int32_t* idx, const float* feat_cl,
-                                    int ld_feat, int B, int N, int M, int nsample, int C_, const float* act_wx,
-                                    const float* act_bias, int nlayers,
-                                    const float* const* wpack, const float* const* bias, const int* nout,
-                                    const int* relu, float* out, int ld_out, int col_off, int pool_ns,
-                                    const int32_t* groups_dev, prcnn_stream_t stream) {
-    PRCNN_REQUIRE(xyz && idx && (C_ == 0 || feat_cl), "prcnn_mlp_chain_group: null pointer");
-    PRCNN_REQUIRE(B >= 0 && N > 0 && M > 0 && nsample > 0 && C_ >= 0 && (C_ == 0 || ld_feat >= C_), "prcnn_mlp_chain_group: bad shape");
-    ChainParams C = {};
-    int rc = fill_chain(C, nlayers, wpack, bias, nout, relu, out, ld_out, col_off, pool_ns);
-    if (rc) return rc;
-    PRCNN_REQUIRE(pool_ns == 0 || pool_ns == nsample, "prcnn_mlp_chain_group: pool_ns must equal nsample");
-    C.a.rows = (long)B * M * nsample; C.a.K = C_ + 3;
-    C.a.rows_dev = groups_dev; C.a.rows_unit = nsample;
-    C.a.xyz = xyz; C.a.new_xyz = new_xyz; C.a.idx = idx; C.a.feat = feat_cl; C.a.ld_feat = ld_feat;
-    C.a.N = N; C.a.M = M; C.a.ns = nsample; C.a.C = C_;
-    C.a.vec_a = C_ > 0 && aligned16(feat_cl) && (ld_feat % 4 == 0);
-    rc = set_group_act(C.a, act_wx, act_bias, C_);
-    if (rc) return rc;
-    return dispatch_chain(MODE_GROUP, C, (hipStream_t)stream);
-}
-
-PRCNN_API int prcnn_mlp_chain_interp(const float* known_cl, int ld_known, const int32_t* idx3, const float* w3,
-                                     const float* skip_cl, int ld_skip, int B, int n, int m, int C2, int C1,
-                                     const float* act_bias, int nlayers, const float* const* wpack, const float* const* bias,
-                                     const int* nout, const int* relu, float* out, int ld_out, int col_off,
-                                     prcnn_stream_t stream) {
-    PRCNN_REQUIRE(known_cl && idx3 && w3 && (C1 == 0 || skip_cl), "prcnn_mlp_chain_interp: null pointer");
-    PRCNN_REQUIRE(B >= 0 && n > 0 && m > 0 && C2 > 0 && C1 >= 0 && ld_known >= C2 && (C1 == 0 || ld_skip >= C1), "prcnn_mlp_chain_interp: bad shape");
-    ChainParams C = {};
-    int rc = fill_chain(C, nlayers, wpack, bias, nout, relu, out, ld_out, col_off, 0);
-    if (rc) return rc;
-    C.a.rows = (long)B * n; C.a.K = C2 + C1;
-    C.a.known = known_cl; C.a.idx3 = idx3; C.a.w3 = w3; C.a.skip = skip_cl; C.a.ld_known = ld_known; C.a.ld_skip = ld_skip;
-    C.a.n = n; C.a.m = m; C.a.C2 = C2; C.a.C1 = C1;
-    C.a.vec_a = aligned16(known_cl) && (ld_known % 4 == 0);
-    C.a.vec_b = C1 > 0 && aligned16(skip_cl) && (ld_skip % 4 == 0) && (C2 % 4 == 0);
-    rc = set_interp_act(C.a, act_bias, C2, C1);
-    if (rc) return rc;
-    if (B % 8 == 0 && n % 128 == 0 && !sw_present(SW_NO_XCD_ORDER)) C.a.xcd_tpf = n / 128;
-    return dispatch_chain(MODE_INTERP, C, (hipStream_t)stream);
-}
-
-// Hoisted FP0 on the split chain kernel: rows relu(interp(known_cl) + act_bias) (C2 = 128, no skip features) through ONE
-// 128 -> 128 layer.  wchain: prcnn_pack_weight_split(chain = 1).  PRCNN_EUNSUPPORTED for other shapes (issue prcnn_mlp_chain_interp).
-PRCNN_API int prcnn_mlp_chain_interp_split(const float* known_cl, int ld_known, const int32_t* idx3, const float* w3, int B, int n,
-                                           int m, int C2, const float* act_bias, const void* wchain, const float* wpack, const float* bias,
-                                           int Nout, int relu, int terms, float* out, int ld_out, int col_off, prcnn_stream_t stream) {
-    PRCNN_REQUIRE(known_cl && idx3 && w3 && act_bias && wchain && wpack && aligned16(wpack) && out, "prcnn_mlp_chain_interp_split: null / misaligned pointer");
-    PRCNN_REQUIRE(terms == 3 || terms == 6, "prcnn_mlp_chain_interp_split: terms=%d (3 or 6)", terms);
-    PRCNN_REQUIRE(B >= 0 && n > 0 && m > 0 && ld_known >= C2 && ld_out >= col_off + Nout, "prcnn_mlp_chain_interp_split: bad shape");
-    if (!(C2 == 128 && Nout == 128 && aligned16(known_cl) && ld_known % 4 == 0 && aligned16(act_bias))) return PRCNN_EUNSUPPORTED;
-    if (B == 0) return PRCNN_OK;
-    ChainParams C = {};
-    MlpParams& P = C.a;
-    P.rows = (long)B * n; P.K = C2; P.bias = bias; P.Nout = Nout; P.relu = relu;
-    P.out = out; P.ld_out = ld_out; P.col_off = col_off; P.rows_unit = 1;
-    P.known = known_cl; P.idx3 = idx3; P.w3 = w3; P.ld_known = ld_known; P.n = n; P.m = m; P.C2 = C2; P.C1 = 0;
-    P.vec_a = 1; P.act = 2; P.act_bias = act_bias;
-    P.wsplit = wchain; P.split_terms = terms; P.wpack = wpack;
-    C.nlayers = 1;
-    if (B % 8 == 0 && n % 128 == 0 && !sw_present(SW_NO_XCD_ORDER)) P.xcd_tpf = n / 128;
-    const dim3 grid(prcnn_divup(P.rows, 128));
-    if (terms == 6 && chain_coop_on() && chain_persist_on() && (long)B * m * ld_known < (1L << 30)) {
-        const int rc = launch_chain_p<MODE_INTERP, 0>(C, (hipStream_t)stream);
-        if (rc) return rc;
-    } else if (terms == 6 && chain_coop_on()) hipLaunchKernelGGL((mlp_chain_c_kernel<MODE_INTERP, 0, 6>), grid, dim3(256), 0, (hipStream_t)stream, C);
-    else if (terms == 6) hipLaunchKernelGGL((mlp_chain_s_kernel<MODE_INTERP, 0, 6>), grid, dim3(256), 0, (hipStream_t)stream, C);
-    else hipLaunchKernelGGL((mlp_chain_s_kernel<MODE_INTERP, 0, 3>), grid, dim3(256), 0, (hipStream_t)stream, C);
-    PRCNN_LAUNCH_CHECK("prcnn_mlp_chain_interp_split");
-    return PRCNN_OK;
-}
+// parameter fills, launch decisions, the launch site and the exports (host code only)
+#include "mlp_host.h"
 
 // training-mode SharedMLP (forward with batch statistics, dgrad, wgrad): shares the row fetchers and weight image above
 #include "mlp_train.h"

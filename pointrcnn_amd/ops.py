@@ -353,15 +353,52 @@ def _chain_args(layers):
     return hit[1]
 
 
-def mlp_chain_rows(x, layers, out=None, pool_ns=0, seg=None):
-    """whole stack on channels-last rows in one kernel (see mlp_rows for the layout contract; seg as there)"""
+def _row_stride(x):
+    """row stride (in elements) of a channels-last rows view (..., K): the stride of the innermost leading dim of
+    size > 1 (size-1 dims carry arbitrary strides); the caller guarantees uniform striding (pt_utils._rows_view)."""
+    for size, stride in zip(reversed(x.shape[:-1]), reversed(x.stride()[:-1])):
+        if size != 1:
+            return stride
+    return x.shape[-1]
+
+
+def _out_buf(out, rows, nout, device):
+    """-> buffer, ld_out, col_off: a fresh (rows, nout) buffer, or out = (buffer, col_off) of a wider channels-last one"""
+    if out is None:
+        return torch.empty((rows, nout), dtype=_F32, device=device), nout, 0
+    buf, col_off = out
+    return buf, _row_stride(buf), col_off
+
+
+# what a layer wrapper and its chain twin share: shapes read off the operands, the output buffer (last: the layer that writes it)
+def _rows_prelude(name, x, last, out, pool_ns):
     if x.stride(-1) != 1:
-        raise RuntimeError("mlp_chain_rows: last dim must be contiguous")
+        raise RuntimeError("%s: last dim must be contiguous" % name)
     K = x.shape[-1]
     rows = x.numel() // K
-    ld_in = _row_stride(x)
-    rows_out = rows // pool_ns if pool_ns else rows
-    buf, ld_out, col_off = _out_buf(out, rows_out, layers[-1], x.device)
+    return (K, rows, _row_stride(x)) + _out_buf(out, rows // pool_ns if pool_ns else rows, last.nout, x.device)
+
+
+def _group_prelude(xyz, idx, feat_cl, last, out, pool_ns, act):
+    B, N, _ = xyz.shape
+    _, M, ns = idx.shape
+    C = 0 if feat_cl is None else feat_cl.shape[-1]
+    ld_feat = 0 if feat_cl is None else _row_stride(feat_cl)
+    rows = B * M * ns
+    return (B, N, M, ns, C, ld_feat) + ((None, None) if act is None else tuple(act)) + _out_buf(out, rows // pool_ns if pool_ns else rows, last.nout, xyz.device)
+
+
+def _interp_prelude(known_cl, idx3, skip_cl, last, out):
+    B, m, C2 = known_cl.shape
+    n = idx3.shape[1]
+    C1 = 0 if skip_cl is None else skip_cl.shape[-1]
+    ld_skip = 0 if skip_cl is None else _row_stride(skip_cl)
+    return (B, n, m, C2, C1, ld_skip) + _out_buf(out, B * n, last.nout, known_cl.device)
+
+
+def mlp_chain_rows(x, layers, out=None, pool_ns=0, seg=None):
+    """whole stack on channels-last rows in one kernel (see mlp_rows for the layout contract; seg as there)"""
+    K, rows, ld_in, buf, ld_out, col_off = _rows_prelude("mlp_chain_rows", x, layers[-1], out, pool_ns)
     a = _chain_args(layers)
     seg_cnt, seg_rows = (None, 0) if seg is None else (seg[0], int(seg[1]))
     if (MLP_SPLIT_TERMS and not pool_ns and seg is None and a.n == 2 and K == 128 and layers[0].nout == 128
@@ -379,15 +416,8 @@ def mlp_chain_rows(x, layers, out=None, pool_ns=0, seg=None):
 
 
 def mlp_chain_group(xyz, new_xyz, idx, feat_cl, layers, out=None, pool_ns=0, act=None, groups_dev=None):
-    B, N, _ = xyz.shape
-    _, M, ns = idx.shape
-    C = 0 if feat_cl is None else feat_cl.shape[-1]
-    ld_feat = 0 if feat_cl is None else _row_stride(feat_cl)
-    rows = B * M * ns
-    rows_out = rows // pool_ns if pool_ns else rows
-    buf, ld_out, col_off = _out_buf(out, rows_out, layers[-1], xyz.device)
+    B, N, M, ns, C, ld_feat, awx, ab, buf, ld_out, col_off = _group_prelude(xyz, idx, feat_cl, layers[-1], out, pool_ns, act)
     a = _chain_args(layers)
-    awx, ab = (None, None) if act is None else act
     _cabi.check(_cabi.lib().prcnn_mlp_chain_group(_p(xyz), _p(new_xyz), _p(idx), _p(feat_cl), ld_feat, B, N, M, ns, C, _p(awx), _p(ab), a.n,
                                                   a.wpack, a.bias, a.nout, a.relu, _p(buf), ld_out, col_off, pool_ns,
                                                   _p(groups_dev), _stream()), "prcnn_mlp_chain_group")
@@ -395,11 +425,7 @@ def mlp_chain_group(xyz, new_xyz, idx, feat_cl, layers, out=None, pool_ns=0, act
 
 
 def mlp_chain_interp(known_cl, idx3, w3, skip_cl, layers, out=None, act_bias=None):
-    B, m, C2 = known_cl.shape
-    n = idx3.shape[1]
-    C1 = 0 if skip_cl is None else skip_cl.shape[-1]
-    ld_skip = 0 if skip_cl is None else _row_stride(skip_cl)
-    buf, ld_out, col_off = _out_buf(out, B * n, layers[-1], known_cl.device)
+    B, n, m, C2, C1, ld_skip, buf, ld_out, col_off = _interp_prelude(known_cl, idx3, skip_cl, layers[-1], out)
     a = _chain_args(layers)
     if (MLP_SPLIT_TERMS and skip_cl is None and act_bias is not None and a.n == 1 and C2 == 128 and layers[0].nout == 128
             and layers[0].wsplit(1) is not None):
@@ -416,35 +442,13 @@ def mlp_chain_interp(known_cl, idx3, w3, skip_cl, layers, out=None, act_bias=Non
     return buf
 
 
-def _row_stride(x):
-    """row stride (in elements) of a channels-last rows view (..., K): the stride of the innermost leading dim of
-    size > 1 (size-1 dims carry arbitrary strides); the caller guarantees uniform striding (pt_utils._rows_view)."""
-    for size, stride in zip(reversed(x.shape[:-1]), reversed(x.stride()[:-1])):
-        if size != 1:
-            return stride
-    return x.shape[-1]
-
-
-def _out_buf(out, rows, lin, device):
-    if out is None:
-        return torch.empty((rows, lin.nout), dtype=_F32, device=device), lin.nout, 0
-    buf, col_off = out
-    return buf, _row_stride(buf), col_off
-
-
 def mlp_rows(x, lin, out=None, pool_ns=0, rows_dev=None, rows_unit=1, seg=None):
     """x (..., K) channels-last rows (last dim contiguous, uniform row stride) -> (rows[/pool_ns], Nout).
     out = (buffer, col_off) writes into a wider channels-last buffer instead of allocating.
     rows_dev (1,) int32 device tensor: only the first rows_dev * rows_unit rows are processed (device-side count).
     seg = (seg_cnt (nseg,) int32 device tensor, seg_rows): segment-prefix live rows -- of every run of seg_rows rows only the
     first seg_cnt[s] are live (roipool3d wrap-copies); tiles in a segment's dead tail are skipped, their outputs unwritten."""
-    if x.stride(-1) != 1:
-        raise RuntimeError("mlp_rows: last dim must be contiguous")
-    K = x.shape[-1]
-    rows = x.numel() // K
-    ld_in = _row_stride(x)
-    rows_out = rows // pool_ns if pool_ns else rows
-    buf, ld_out, col_off = _out_buf(out, rows_out, lin, x.device)
+    K, rows, ld_in, buf, ld_out, col_off = _rows_prelude("mlp_rows", x, lin, out, pool_ns)
     if MLP_SPLIT_TERMS and ld_in % 4 == 0 and (seg is None or (rows_dev is None and not pool_ns)) and lin.wsplit() is not None:
         _cabi.check(_cabi.lib().prcnn_mlp_rows_split(_p(x), ld_in, rows, K, _p(lin.wpack), _p(lin.wsplit()), MLP_SPLIT_TERMS,
                                                      _p(lin.bias), lin.nout, int(lin.relu), _p(buf), ld_out, col_off, int(pool_ns), _p(rows_dev),
@@ -462,14 +466,7 @@ def mlp_group(xyz, new_xyz, idx, feat_cl, lin, out=None, pool_ns=0, act=None, gr
     idx (B,M,ns) i32, feat_cl (B,N,C) channels-last or None -> (B*M*ns[/pool_ns], Nout).
     act = (act_wx (C,3), act_bias (C)) selects the HOISTED form: feat_cl is Z = W_f.feat per source point and `lin` is
     the SECOND layer (see include/prcnn_pointops.h)."""
-    B, N, _ = xyz.shape
-    _, M, ns = idx.shape
-    C = 0 if feat_cl is None else feat_cl.shape[-1]
-    ld_feat = 0 if feat_cl is None else _row_stride(feat_cl)
-    rows = B * M * ns
-    rows_out = rows // pool_ns if pool_ns else rows
-    buf, ld_out, col_off = _out_buf(out, rows_out, lin, xyz.device)
-    awx, ab = (None, None) if act is None else act
+    B, N, M, ns, C, ld_feat, awx, ab, buf, ld_out, col_off = _group_prelude(xyz, idx, feat_cl, lin, out, pool_ns, act)
     if MLP_SPLIT_TERMS and act is not None and C % 32 == 0 and ld_feat % 4 == 0 and lin.wsplit() is not None:
         # the hoisted grouped layer on the split-bf16 kernel (round 5; PRCNN_GROUP_SPLIT=0 inside the library is the A/B switch)
         _cabi.check(_cabi.lib().prcnn_mlp_group_split(_p(xyz), _p(new_xyz), _p(idx), _p(feat_cl), ld_feat, B, N, M, ns, C, _p(awx), _p(ab),
@@ -486,11 +483,7 @@ def mlp_interp(known_cl, idx3, w3, skip_cl, lin, out=None, act_bias=None):
     """First FP layer fused with three_interpolate + skip concat.  known_cl (B,m,C2), idx3/w3 (B,n,3),
     skip_cl (B,n,C1) or None -> (B*n, Nout).  act_bias (C2) selects the HOISTED form (skip_cl must be None): known_cl
     is Y = W.known per known point, the row is relu(interp(Y) + act_bias) and `lin` is the second layer."""
-    B, m, C2 = known_cl.shape
-    n = idx3.shape[1]
-    C1 = 0 if skip_cl is None else skip_cl.shape[-1]
-    ld_skip = 0 if skip_cl is None else _row_stride(skip_cl)
-    buf, ld_out, col_off = _out_buf(out, B * n, lin, known_cl.device)
+    B, n, m, C2, C1, ld_skip, buf, ld_out, col_off = _interp_prelude(known_cl, idx3, skip_cl, lin, out)
     _cabi.check(_cabi.lib().prcnn_mlp_interp(_p(known_cl), _row_stride(known_cl), _p(idx3), _p(w3), _p(skip_cl), ld_skip,
                                              B, n, m, C2, C1, _p(act_bias), _p(lin.wpack), _p(lin.bias), lin.nout,
                                              int(lin.relu), _p(buf), ld_out, col_off, _stream()), "prcnn_mlp_interp")
@@ -502,7 +495,7 @@ def mlp_rows_addinterp(skip_cl, lin_b, y_cl, idx3, w3, out=None):
     y_cl (B,m,Nout) = W_a.known, idx3/w3 (B,n,3) -> (B*n, Nout)."""
     B, n, C1 = skip_cl.shape
     m = y_cl.shape[1]
-    buf, ld_out, col_off = _out_buf(out, B * n, lin_b, skip_cl.device)
+    buf, ld_out, col_off = _out_buf(out, B * n, lin_b.nout, skip_cl.device)
     if MLP_SPLIT_TERMS and _row_stride(skip_cl) % 4 == 0 and lin_b.wsplit() is not None:
         _cabi.check(_cabi.lib().prcnn_mlp_rows_addinterp_split(_p(skip_cl), _row_stride(skip_cl), C1, _p(lin_b.wpack), _p(lin_b.wsplit()),
                                                                MLP_SPLIT_TERMS, _p(lin_b.bias), lin_b.nout, int(lin_b.relu), _p(y_cl),
@@ -520,11 +513,7 @@ def maxpool_rows(x, ns, out=None):
     """x (rows, C) -> (rows/ns, C): max over every ns consecutive rows (generic nsample fallback)."""
     rows, C = x.shape
     rows_out = rows // ns
-    if out is None:
-        buf, ld_out, col_off = torch.empty((rows_out, C), dtype=_F32, device=x.device), C, 0
-    else:
-        buf, col_off = out
-        ld_out = buf.stride(-2)
+    buf, ld_out, col_off = _out_buf(out, rows_out, C, x.device)
     _cabi.check(_cabi.lib().prcnn_maxpool_rows(_p(x), x.stride(0), rows_out, ns, C, _p(buf), ld_out, col_off, _stream()),
                 "prcnn_maxpool_rows")
     return buf
