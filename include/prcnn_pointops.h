@@ -60,6 +60,8 @@ typedef void* prcnn_stream_t; /* hipStream_t */
 int prcnn_abi_version(void);   /* 12: + prcnn_switches_reload, prcnn_switch_get (the PRCNN_* kernel switches are read once, through one table);
                                  * still 12 (additive, no caller breaks): + prcnn_gt_database_workspace_bytes, prcnn_gt_database_count,
                                  * prcnn_gt_database_fill (the GT-augmentation database built on the device);
+                                 * still 12 (additive): + prcnn_rpn_loss_workspace_bytes, prcnn_rpn_loss_counts, prcnn_rpn_loss_forward,
+                                 * prcnn_rpn_loss_backward (the RPN training loss and its gradient in device passes);
                                  * 11: + prcnn_train_scene_workspace_bytes, prcnn_train_scene_prepare (the RPN training batch on the device);
                                  * 10: + prcnn_corner_iou3d, prcnn_gt_aug_sample (GT-augmentation sampling loop on the device);
                                  * 9: + prcnn_fps_mode, prcnn_ball_query_arith, prcnn_three_nn_arith (comparison mode: the squared distance as nvcc contracts the
@@ -769,6 +771,43 @@ int prcnn_proposal_target_sample(const float* roi_boxes3d, const float* gt_boxes
                                  const double* cfg6, int aug_times, int aug_method, uint32_t seed, float* rois, float* gt_of_rois,
                                  float* roi_iou, int32_t* src, float* max_overlaps, int32_t* gt_assignment, int32_t* counts,
                                  int32_t* status, prcnn_stream_t stream);
+
+/* ======================================================================================================
+ * RPN training loss and its gradient in one device pass (csrc/rpn_loss.hip, arithmetic: csrc/rpn_loss_math.h) --
+ * train_functions.get_rpn_loss for LOSS_CLS = SigmoidFocalLoss with the bin-based box regression of get_reg_loss
+ * (get_y_by_bin = get_ry_fine = False; LOC_XZ_FINE either way: C = (4 or 2) * nb + 1 + 2 * num_head_bin + 3 channels per row).
+ * Anything else is PRCNN_EUNSUPPORTED: the caller keeps its composed path for it.
+ *   rpn_cls: row r's logit at rpn_cls[r * ld_cls]; rpn_reg: row r's C predictions at rpn_reg + r * ld_reg (16-byte units when
+ *   the pointer and ld_reg allow it); cls_label (npts) i32 or i64 (label_is_i64), > 0 foreground, 0 background, < 0 ignored;
+ *   reg_label (npts, 7) [dx dy dz h w l ry].  A row that is not foreground never has its rpn_reg row read.
+ *   prcnn_rpn_loss_counts  -> counts (4) i32 {pos, valid, fg = pos, 0} of THIS process and norm (2) f32 = {1 / max(pos, 1), 1}.
+ *                             Data-parallel callers all-reduce the counts and overwrite norm with
+ *                             {world / max(pos_global, 1), world * fg_local / max(fg_global, 1)}; counts stay local.
+ *   prcnn_rpn_loss_forward -> terms (9) f32: loss, loss_cls, loss_reg, loss_loc, loss_angle, loss_size (3 x the mean, as the
+ *                             reference), cls_pos, cls_neg, fg_sum.  Per-workgroup partial sums are doubles, added in a fixed order.
+ *   prcnn_rpn_loss_backward-> dcls (npts) and dreg (npts, C) contiguous = grad_out[0] * d loss / d input, every entry written
+ *                             exactly once (zeros for the rows that carry no term); grad_out is a device scalar.
+ * work: >= prcnn_rpn_loss_workspace_bytes(npts) device bytes, 8-byte aligned.  Results depend on the flat row order only.
+ * ====================================================================================================== */
+typedef struct prcnn_rpn_loss_cfg {
+    double loc_scope, loc_bin_size; /* RPN.LOC_SCOPE, LOC_BIN_SIZE: nb = int(scope / bin_size) * 2 */
+    double mean_size[3];            /* CLS_MEAN_SIZE h w l */
+    double gamma, alpha;            /* focal loss; has_alpha 0: alpha is None */
+    double loss_weight[2];          /* RPN.LOSS_WEIGHT */
+    int num_head_bin, xz_fine, y_by_bin, ry_fine;
+    int loss_cls;                   /* 0 SigmoidFocalLoss; the others have no kernel */
+    int has_alpha;
+} prcnn_rpn_loss_cfg_t;
+size_t prcnn_rpn_loss_workspace_bytes(int64_t npts);
+int prcnn_rpn_loss_counts(const void* cls_label, int label_is_i64, int64_t npts, int32_t* counts, float* norm, void* work,
+                          size_t work_bytes, prcnn_stream_t stream);
+int prcnn_rpn_loss_forward(const float* rpn_cls, int64_t ld_cls, const float* rpn_reg, int64_t ld_reg, const void* cls_label,
+                           int label_is_i64, const float* reg_label, int64_t npts, int C, const prcnn_rpn_loss_cfg_t* cfg,
+                           const int32_t* counts, const float* norm, float* terms, void* work, size_t work_bytes, prcnn_stream_t stream);
+int prcnn_rpn_loss_backward(const float* rpn_cls, int64_t ld_cls, const float* rpn_reg, int64_t ld_reg, const void* cls_label,
+                            int label_is_i64, const float* reg_label, int64_t npts, int C, const prcnn_rpn_loss_cfg_t* cfg,
+                            const int32_t* counts, const float* norm, const float* grad_out, float* dcls, float* dreg,
+                            prcnn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -37,6 +37,12 @@ class TrainLayer(ctypes.Structure):
                 ("dW", _P), ("dgamma", _P), ("dbeta", _P)]
 
 
+class RpnLossCfg(ctypes.Structure):
+    """prcnn_rpn_loss_cfg_t (include/prcnn_pointops.h)"""
+    _fields_ = [("loc_scope", _D), ("loc_bin_size", _D), ("mean_size", _D * 3), ("gamma", _D), ("alpha", _D), ("loss_weight", _D * 2),
+                ("num_head_bin", _I), ("xz_fine", _I), ("y_by_bin", _I), ("ry_fine", _I), ("loss_cls", _I), ("has_alpha", _I)]
+
+
 REQUIRED_ABI = 12                # prcnn_abi_version() the signatures below describe
 
 # name -> (restype, argtypes); mirrors include/prcnn_pointops.h one for one
@@ -134,6 +140,10 @@ SIGNATURES = {
     "prcnn_interp_rows_grad": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P]),
     "prcnn_interp_rows_grad_work_bytes": (_Z, [_I, _I, _I]),
     "prcnn_interp_rows_grad_ws": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P, _Z, _P]),
+    "prcnn_rpn_loss_workspace_bytes": (_Z, [_L]),
+    "prcnn_rpn_loss_counts": (_I, [_P, _I, _L, _P, _P, _P, _Z, _P]),
+    "prcnn_rpn_loss_forward": (_I, [_P, _L, _P, _L, _P, _I, _P, _L, _I, ctypes.POINTER(RpnLossCfg), _P, _P, _P, _P, _Z, _P]),
+    "prcnn_rpn_loss_backward": (_I, [_P, _L, _P, _L, _P, _I, _P, _L, _I, ctypes.POINTER(RpnLossCfg), _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

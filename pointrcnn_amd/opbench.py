@@ -133,6 +133,37 @@ def gt_database_row(dev, B=8, n_raw=120000, nbox=8):
          bytes=2 * raw.numel() * 4 + P * 20 + B * nbox * 4, kernels=[("gtdb_kernel", 0), ("gtdb_scan_kernel", 0)])
 
 
+def rpn_loss_rows(dev, B=16, N=16384, rounds=5):
+    """`rpn_loss fwd+bwd`: train_functions.get_rpn_loss + backward at the training step's shape (bs16 x 16 384 points, C = 76, about
+    3 % foreground and 10 % ignored), composed torch against the fused device passes, alternated in one process; per route the median
+    and the minimum over `rounds` windows of 20 calls.  Traffic floor of the fused route: labels + foreground rows read in forward and
+    again in backward + both gradients written once."""
+    from . import train_functions as tf
+    g = torch.Generator().manual_seed(7)
+    u = torch.rand(B, N, generator=g)
+    lab = torch.where(u < 0.03, 1, torch.where(u < 0.13, -1, 0)).to(dev)
+    reg_lab = (torch.rand(B, N, 7, generator=g) * torch.tensor([6., 2., 6., 1., 1., 2., 6.28]) + torch.tensor([-3., -1., -3., 1., 1., 3., -3.14])).to(dev)
+    cls = torch.randn(B, N, 1, generator=g).to(dev).requires_grad_(True)
+    reg = torch.randn(B, N, 76, generator=g).to(dev).requires_grad_(True)
+
+    def step(fused):
+        cls.grad = reg.grad = None
+        tf.get_rpn_loss(cls, reg, lab, reg_lab, fused=fused).backward()
+    times = {False: [], True: []}
+    for _ in range(rounds):
+        for fused in (False, True):
+            times[fused].append(timeit(lambda: step(fused)))
+    n_fg, npts = int((lab > 0).sum()), B * N
+    floor = 2 * (npts * (8 + 28 + 4) + n_fg * 76 * 4) + npts * 77 * 4
+    for fused in (False, True):
+        t = sorted(times[fused])
+        d = {"op": "rpn_loss fwd+bwd (%s)" % ("fused" if fused else "composed"), "shape": "B%d N%d C76, %d foreground rows" % (B, N, n_fg),
+             "median_us": round(t[len(t) // 2] * 1e6, 1), "min_us": round(t[0] * 1e6, 1), "max_us": round(t[-1] * 1e6, 1)}
+        if fused:
+            d.update(traffic_floor_MB=round(floor / 1e6, 1), floor_GBps_at_median=round(floor / t[len(t) // 2] / 1e9, 1))
+        print(json.dumps(d), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
@@ -237,6 +268,9 @@ def main():
 
     # ---- the GT-augmentation database from raw scans and labels (kitti_input.GTDatabase.from_kitti)
     gt_database_row(dev)
+
+    # ---- the RPN training loss and its gradient: composed torch against the one-pass kernels (csrc/rpn_loss.hip)
+    rpn_loss_rows(dev)
 
     # ---- NMS (default RPN path: normal, 6300 boxes, thr 0.8) and rotated
     c = torch.rand(6300, 2, generator=g) * torch.tensor([80.0, 70.0])

@@ -606,6 +606,119 @@ def rpn_labels(pts, gt_boxes3d, num_gt=None, extra_width=0.2):
     return cls, reg
 
 
+# what csrc/rpn_loss.hip holds per row: RL_MAX_BINS (csrc/rpn_loss_math.h) bins per head and RL_MAX_C (csrc/rpn_loss.hip) channels, a
+# multiple of 4.  train_functions routes a configuration beyond them to the composed loss; the exports answer PRCNN_EUNSUPPORTED.
+RPN_LOSS_MAX_BINS = 16
+RPN_LOSS_MAX_C = 96
+
+
+def rpn_loss_cfg(cfg):
+    """an RPNLossConfig-like object -> prcnn_rpn_loss_cfg_t (what csrc/rpn_loss.hip accepts of it is decided there)"""
+    kinds = {"SigmoidFocalLoss": 0, "DiceLoss": 1, "BinaryCrossEntropy": 2}
+    alpha = cfg.FOCAL_ALPHA[0]
+    return _cabi.RpnLossCfg(loc_scope=float(cfg.LOC_SCOPE), loc_bin_size=float(cfg.LOC_BIN_SIZE),
+                            mean_size=(ctypes.c_double * 3)(*[float(v) for v in cfg.MEAN_SIZE]), gamma=float(cfg.FOCAL_GAMMA),
+                            alpha=0.0 if alpha is None else float(alpha),
+                            loss_weight=(ctypes.c_double * 2)(float(cfg.LOSS_WEIGHT[0]), float(cfg.LOSS_WEIGHT[1])),
+                            num_head_bin=int(cfg.NUM_HEAD_BIN), xz_fine=int(bool(cfg.LOC_XZ_FINE)), y_by_bin=0, ry_fine=0,
+                            loss_cls=kinds.get(cfg.LOSS_CLS, -1), has_alpha=int(alpha is not None))
+
+
+def rpn_loss_channels(cfg):
+    """channels of an rpn_reg row under cfg: (4 or 2) * nb + 1 + 2 * NUM_HEAD_BIN + 3"""
+    nb = int(cfg.LOC_SCOPE / cfg.LOC_BIN_SIZE) * 2
+    return (4 if cfg.LOC_XZ_FINE else 2) * nb + 1 + 2 * int(cfg.NUM_HEAD_BIN) + 3
+
+
+def _uniform_rows(x):
+    """x (..., K) -> (x or a contiguous copy, row stride): the rows of x in flat order sit at one stride (what the heads hand over:
+    contiguous, or a channels-last view of a wider buffer); any other layout is copied"""
+    K = x.shape[-1]
+    if K == 1 or x.stride(-1) == 1:
+        ld, expect, ok = _row_stride(x), None, True
+        for size, stride in zip(reversed(x.shape[:-1]), reversed(x.stride()[:-1])):
+            if size != 1:
+                expect = stride if expect is None else expect
+                ok = ok and stride == expect
+                expect = expect * size
+        if ok and ld >= K:
+            return x, ld
+    x = x.contiguous()
+    return x, K
+
+
+def _rpn_loss_work(npts, device):
+    return torch.empty((_cabi.lib().prcnn_rpn_loss_workspace_bytes(npts) + 7) // 8, dtype=torch.int64, device=device)
+
+
+def _rpn_loss_label(cls_label):
+    if cls_label.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError("rpn_loss: rpn_cls_label must be int32 or int64, got %s" % cls_label.dtype)
+    if not cls_label.is_cuda:
+        raise RuntimeError("rpn_loss: rpn_cls_label must be a CUDA(HIP) tensor")
+    return cls_label.contiguous(), int(cls_label.dtype == torch.int64)
+
+
+def rpn_loss_counts(cls_label):
+    """cls_label (...) i32 / i64 -> counts (4) i32 = this process's {#(label > 0), #(label >= 0), #foreground, 0} and
+    norm (2) f32 = {1 / max(pos, 1), 1}, the single-process normalisers (a data-parallel caller overwrites them, see
+    train_functions.get_rpn_loss).  Nothing is read back."""
+    label, is64 = _rpn_loss_label(cls_label)
+    npts = label.numel()
+    counts = torch.empty((4,), dtype=_INT, device=label.device)
+    norm = torch.empty((2,), dtype=_F32, device=label.device)
+    work = _rpn_loss_work(npts, label.device)
+    _cabi.check(_cabi.lib().prcnn_rpn_loss_counts(_p(label), is64, npts, _p(counts), _p(norm), _p(work), work.numel() * 8, _stream()),
+                "prcnn_rpn_loss_counts")
+    return counts, norm
+
+
+def _rpn_loss_prelude(rpn_cls, rpn_reg, cls_label, reg_label, counts, norm):
+    for name, t in (("rpn_cls", rpn_cls), ("rpn_reg", rpn_reg)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == _F32):
+            raise RuntimeError("rpn_loss: %s must be a float32 CUDA(HIP) tensor" % name)
+    C = rpn_reg.shape[-1]
+    npts = rpn_reg.numel() // C
+    if rpn_cls.numel() != npts or cls_label.numel() != npts:
+        raise ValueError("rpn_loss: rpn_cls / rpn_cls_label must have %d rows" % npts)
+    _chk(reg_label, "rpn_reg_label")
+    if reg_label.numel() != npts * 7 or reg_label.shape[-1] != 7:
+        raise ValueError("rpn_loss: rpn_reg_label must be (..., 7) with %d rows" % npts)
+    _chk(counts, "counts", _INT, 1); _chk(norm, "norm", _F32, 1)
+    label, is64 = _rpn_loss_label(cls_label)
+    cls_rows, ld_cls = _uniform_rows(rpn_cls.reshape(rpn_cls.shape + (1,)) if rpn_cls.dim() == 1 else rpn_cls)
+    reg_rows, ld_reg = _uniform_rows(rpn_reg)
+    return (_p(cls_rows), ld_cls, _p(reg_rows), ld_reg, _p(label), is64, _p(reg_label), npts, C), (cls_rows, reg_rows, label)
+
+
+def rpn_loss_forward(rpn_cls, rpn_reg, cls_label, reg_label, cfg, counts, norm):
+    """rpn_cls (B,N,1), rpn_reg (B,N,C) f32 (views whose rows sit at ONE stride -- contiguous, or channels-last columns of a wider
+    buffer, what the heads hand over -- are read in place; any other layout costs a contiguous copy, a second pass over the
+    tensor, see _uniform_rows), cls_label (B,N) i32 / i64, reg_label (B,N,7),
+    cfg (rpn_loss_cfg), counts / norm (rpn_loss_counts) -> terms (9) f32: loss, loss_cls, loss_reg, loss_loc, loss_angle,
+    loss_size, cls_pos, cls_neg, fg_sum.  Two launches, nothing read back."""
+    args, keep = _rpn_loss_prelude(rpn_cls, rpn_reg, cls_label, reg_label, counts, norm)
+    terms = torch.empty((9,), dtype=_F32, device=rpn_reg.device)
+    work = _rpn_loss_work(args[7], rpn_reg.device)
+    _cabi.check(_cabi.lib().prcnn_rpn_loss_forward(*args, ctypes.byref(cfg), _p(counts), _p(norm), _p(terms), _p(work), work.numel() * 8,
+                                                   _stream()), "prcnn_rpn_loss_forward")
+    return terms
+
+
+def rpn_loss_backward(rpn_cls, rpn_reg, cls_label, reg_label, cfg, counts, norm, grad_out):
+    """the inputs of rpn_loss_forward + grad_out (a float32 device scalar) -> grad_out * d loss / d rpn_cls, d loss / d rpn_reg,
+    contiguous, in the inputs' shapes; one launch that writes every entry once"""
+    args, keep = _rpn_loss_prelude(rpn_cls, rpn_reg, cls_label, reg_label, counts, norm)
+    _chk(grad_out, "grad_out")
+    if grad_out.numel() != 1:
+        raise ValueError("rpn_loss_backward: grad_out must be a scalar")
+    dcls = torch.empty(rpn_cls.shape, dtype=_F32, device=rpn_cls.device)
+    dreg = torch.empty(rpn_reg.shape, dtype=_F32, device=rpn_reg.device)
+    _cabi.check(_cabi.lib().prcnn_rpn_loss_backward(*args, ctypes.byref(cfg), _p(counts), _p(norm), _p(grad_out), _p(dcls), _p(dreg),
+                                                    _stream()), "prcnn_rpn_loss_backward")
+    return dcls, dreg
+
+
 def gt_aug_edit(pts, intensity, boxes3d, new_pts, new_intensity, num_pts=None, num_boxes=None, num_new=None, extra_h=2.0,
                 want_removed=False):
     """The point work of KittiRCNNDataset.apply_gt_aug_to_one_scene (kitti_rcnn_dataset.py:484-507) for a batch of scenes.
