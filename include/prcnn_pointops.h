@@ -62,6 +62,8 @@ int prcnn_abi_version(void);   /* 12: + prcnn_switches_reload, prcnn_switch_get 
                                  * prcnn_gt_database_fill (the GT-augmentation database built on the device);
                                  * still 12 (additive): + prcnn_rpn_loss_workspace_bytes, prcnn_rpn_loss_counts, prcnn_rpn_loss_forward,
                                  * prcnn_rpn_loss_backward (the RPN training loss and its gradient in device passes);
+                                 * still 12 (additive): + prcnn_rcnn_loss_workspace_bytes, prcnn_rcnn_loss_forward, prcnn_rcnn_loss_finalize,
+                                 * prcnn_rcnn_loss_backward (the RCNN training loss and its gradient in device passes);
                                  * 11: + prcnn_train_scene_workspace_bytes, prcnn_train_scene_prepare (the RPN training batch on the device);
                                  * 10: + prcnn_corner_iou3d, prcnn_gt_aug_sample (GT-augmentation sampling loop on the device);
                                  * 9: + prcnn_fps_mode, prcnn_ball_query_arith, prcnn_three_nn_arith (comparison mode: the squared distance as nvcc contracts the
@@ -808,6 +810,51 @@ int prcnn_rpn_loss_backward(const float* rpn_cls, int64_t ld_cls, const float* r
                             int label_is_i64, const float* reg_label, int64_t npts, int C, const prcnn_rpn_loss_cfg_t* cfg,
                             const int32_t* counts, const float* norm, const float* grad_out, float* dcls, float* dreg,
                             prcnn_stream_t stream);
+
+/* ======================================================================================================
+ * RCNN training loss and its gradient in device passes (csrc/rcnn_loss.hip, arithmetic: csrc/rcnn_loss_math.h) --
+ * train_functions.get_rcnn_loss for LOSS_CLS = BinaryCrossEntropy or SigmoidFocalLoss with get_reg_loss(get_xz_fine = True,
+ * get_ry_fine = True), LOC_Y_BY_BIN and SIZE_RES_ON_ROI either way: C = 4 * nb + (2 * nby | 1) + 2 * num_head_bin + 3 channels per
+ * row, any C up to 56 (no alignment of the rows is assumed), 1 <= npts <= 2^24.  Anything else is PRCNN_EUNSUPPORTED: the caller keeps
+ * its composed path for it.
+ *   rcnn_cls: row r's logit at rcnn_cls[r * ld_cls]; rcnn_reg: row r's C predictions at rcnn_reg + r * ld_reg; cls_label (npts) i32 or
+ *   i64, > 0 positive, 0 negative, < 0 ignored (its logit is not read); reg_valid_mask (npts) i32 or i64 in {0, 1}, 1: the row is regressed --
+ *   independent of the label; a row whose mask is <= 0 never has its rcnn_reg row or its targets read; roi_boxes3d (npts, 7): columns
+ *   3..5 are the size anchor under size_res_on_roi (else unused, may be null); gt_of_rois (npts, 7) [dx dy dz h w l ry].
+ *   prcnn_rcnn_loss_forward -> counts (4) i32 {#(label > 0), #(label >= 0), #(mask > 0), sum of mask (32-bit)} of THIS process, and the
+ *                              per-workgroup unnormalised sums (doubles, fixed order) in work.  finalize != 0: also terms, with the
+ *                              single-process normalisers (one launch up to 256 rows, two beyond).
+ *   prcnn_rcnn_loss_finalize-> terms from work and counts; norm null: single process; else (2) f32 device
+ *                              {classification scale, regression scale}: data-parallel callers run the forward with finalize = 0,
+ *                              all-reduce the counts and pass {world / max(pos_global | valid_global, 1), world * fg / max(fg_global, 1)}.
+ *   terms (23) f32: loss, loss_cls, loss_reg, loss_loc, loss_angle, loss_size (3 x the mean; these three carry the regression scale),
+ *                   cls_pos, cls_neg (focal), the eight per-head means x_bin z_bin x_res z_res y_offset|y_bin y_res ry_bin ry_res,
+ *                   unscaled loc, angle and size mean, then the four counts.
+ *   prcnn_rcnn_loss_backward-> dcls (npts) and dreg (npts, C) contiguous = grad_out[0] * d loss / d input, one launch, every entry
+ *                              written exactly once (zeros where no term is carried); grad_out is a device scalar; counts as the
+ *                              forward wrote them, norm as given to finalize (or null).
+ * work: >= prcnn_rcnn_loss_workspace_bytes(npts) device bytes, 8-byte aligned.  Results depend on the flat row order only.
+ * ====================================================================================================== */
+typedef struct prcnn_rcnn_loss_cfg {
+    double loc_scope, loc_bin_size;     /* RCNN.LOC_SCOPE, LOC_BIN_SIZE: nb = int(scope / bin_size) * 2 */
+    double loc_y_scope, loc_y_bin_size; /* RCNN.LOC_Y_SCOPE, LOC_Y_BIN_SIZE (read under y_by_bin) */
+    double mean_size[3];                /* CLS_MEAN_SIZE h w l (the anchor without size_res_on_roi) */
+    double gamma, alpha;                /* focal loss; has_alpha 0: alpha is None */
+    int num_head_bin, y_by_bin, size_res_on_roi;
+    int loss_cls;                       /* 0 SigmoidFocalLoss, 2 BinaryCrossEntropy (ops.rpn_loss_cfg's numbering) */
+    int has_alpha;
+} prcnn_rcnn_loss_cfg_t;
+size_t prcnn_rcnn_loss_workspace_bytes(int64_t npts);
+int prcnn_rcnn_loss_forward(const float* rcnn_cls, int64_t ld_cls, const float* rcnn_reg, int64_t ld_reg, const void* cls_label,
+                            int label_is_i64, const void* reg_valid_mask, int mask_is_i64, const float* roi_boxes3d,
+                            const float* gt_of_rois, int64_t npts, int C, const prcnn_rcnn_loss_cfg_t* cfg, int finalize,
+                            int32_t* counts, float* terms, void* work, size_t work_bytes, prcnn_stream_t stream);
+int prcnn_rcnn_loss_finalize(int64_t npts, int C, const prcnn_rcnn_loss_cfg_t* cfg, const int32_t* counts, const float* norm,
+                             float* terms, const void* work, size_t work_bytes, prcnn_stream_t stream);
+int prcnn_rcnn_loss_backward(const float* rcnn_cls, int64_t ld_cls, const float* rcnn_reg, int64_t ld_reg, const void* cls_label,
+                             int label_is_i64, const void* reg_valid_mask, int mask_is_i64, const float* roi_boxes3d,
+                             const float* gt_of_rois, int64_t npts, int C, const prcnn_rcnn_loss_cfg_t* cfg, const int32_t* counts,
+                             const float* norm, const float* grad_out, float* dcls, float* dreg, prcnn_stream_t stream);
 
 #ifdef __cplusplus
 }

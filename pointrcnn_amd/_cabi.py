@@ -43,6 +43,12 @@ class RpnLossCfg(ctypes.Structure):
                 ("num_head_bin", _I), ("xz_fine", _I), ("y_by_bin", _I), ("ry_fine", _I), ("loss_cls", _I), ("has_alpha", _I)]
 
 
+class RcnnLossCfg(ctypes.Structure):
+    """prcnn_rcnn_loss_cfg_t (include/prcnn_pointops.h)"""
+    _fields_ = [("loc_scope", _D), ("loc_bin_size", _D), ("loc_y_scope", _D), ("loc_y_bin_size", _D), ("mean_size", _D * 3), ("gamma", _D),
+                ("alpha", _D), ("num_head_bin", _I), ("y_by_bin", _I), ("size_res_on_roi", _I), ("loss_cls", _I), ("has_alpha", _I)]
+
+
 REQUIRED_ABI = 12                # prcnn_abi_version() the signatures below describe
 
 # name -> (restype, argtypes); mirrors include/prcnn_pointops.h one for one
@@ -144,6 +150,10 @@ SIGNATURES = {
     "prcnn_rpn_loss_counts": (_I, [_P, _I, _L, _P, _P, _P, _Z, _P]),
     "prcnn_rpn_loss_forward": (_I, [_P, _L, _P, _L, _P, _I, _P, _L, _I, ctypes.POINTER(RpnLossCfg), _P, _P, _P, _P, _Z, _P]),
     "prcnn_rpn_loss_backward": (_I, [_P, _L, _P, _L, _P, _I, _P, _L, _I, ctypes.POINTER(RpnLossCfg), _P, _P, _P, _P, _P, _P]),
+    "prcnn_rcnn_loss_workspace_bytes": (_Z, [_L]),
+    "prcnn_rcnn_loss_forward": (_I, [_P, _L, _P, _L, _P, _I, _P, _I, _P, _P, _L, _I, ctypes.POINTER(RcnnLossCfg), _I, _P, _P, _P, _Z, _P]),
+    "prcnn_rcnn_loss_finalize": (_I, [_L, _I, ctypes.POINTER(RcnnLossCfg), _P, _P, _P, _P, _Z, _P]),
+    "prcnn_rcnn_loss_backward": (_I, [_P, _L, _P, _L, _P, _I, _P, _I, _P, _P, _L, _I, ctypes.POINTER(RcnnLossCfg), _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

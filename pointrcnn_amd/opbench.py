@@ -164,6 +164,40 @@ def rpn_loss_rows(dev, B=16, N=16384, rounds=5):
         print(json.dumps(d), flush=True)
 
 
+def rcnn_loss_rows(dev, R=256, rounds=5):
+    """`rcnn_loss fwd+bwd`: train_functions.get_rcnn_loss + backward at the RCNN training step's shape (bs4 x 64 RoIs, C = 46, default
+    BinaryCrossEntropy; about a third of the rows regressed, 15 % ignored), composed torch against the fused device passes, alternated
+    in one process; per route the median and the minimum over `rounds` windows of 20 calls.  256 rows are launch latency, not traffic:
+    no floor is printed."""
+    from . import train_functions as tf
+    from .rcnn import RCNNConfig
+    g = torch.Generator().manual_seed(9)
+    u = torch.rand(R, generator=g)
+    mean = torch.tensor(tf.RPNLossConfig.MEAN_SIZE)
+    roi, gt = torch.zeros(R, 7), torch.zeros(R, 7)
+    roi[:, 3:6] = (torch.rand(R, 3, generator=g) * 0.4 + 0.8) * mean
+    gt[:, 0:3] = (torch.rand(R, 3, generator=g) * 2.8 - 1.4) * torch.tensor([1.0, 0.3, 1.0])
+    gt[:, 3:6] = (torch.rand(R, 3, generator=g) * 0.4 + 0.8) * mean
+    gt[:, 6] = torch.rand(R, generator=g) * 2.0 - 1.0
+    ret = {"rcnn_cls": (torch.randn(R, 1, generator=g) * 2).to(dev).requires_grad_(True),
+           "rcnn_reg": torch.randn(R, 46, generator=g).to(dev).requires_grad_(True),
+           "cls_label": torch.where(u < 0.3, 1, torch.where(u < 0.45, -1, 0)).to(dev),
+           "reg_valid_mask": (torch.rand(R, generator=g) < 0.35).long().to(dev), "roi_boxes3d": roi.to(dev), "gt_of_rois": gt.to(dev)}
+
+    def step(fused):
+        ret["rcnn_cls"].grad = ret["rcnn_reg"].grad = None
+        tf.get_rcnn_loss(ret, RCNNConfig, fused=fused).backward()
+    times = {False: [], True: []}
+    for _ in range(rounds):
+        for fused in (False, True):
+            times[fused].append(timeit(lambda: step(fused)))
+    for fused in (False, True):
+        t = sorted(times[fused])
+        print(json.dumps({"op": "rcnn_loss fwd+bwd (%s)" % ("fused" if fused else "composed"),
+                          "shape": "R%d C46, %d regressed rows" % (R, int(ret["reg_valid_mask"].sum())),
+                          "median_us": round(t[len(t) // 2] * 1e6, 1), "min_us": round(t[0] * 1e6, 1), "max_us": round(t[-1] * 1e6, 1)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
@@ -271,6 +305,8 @@ def main():
 
     # ---- the RPN training loss and its gradient: composed torch against the one-pass kernels (csrc/rpn_loss.hip)
     rpn_loss_rows(dev)
+    # ---- the RCNN training loss and its gradient: composed torch against the device passes (csrc/rcnn_loss.hip)
+    rcnn_loss_rows(dev)
 
     # ---- NMS (default RPN path: normal, 6300 boxes, thr 0.8) and rotated
     c = torch.rand(6300, 2, generator=g) * torch.tensor([80.0, 70.0])

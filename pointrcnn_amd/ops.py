@@ -719,6 +719,108 @@ def rpn_loss_backward(rpn_cls, rpn_reg, cls_label, reg_label, cfg, counts, norm,
     return dcls, dreg
 
 
+# what csrc/rcnn_loss.hip takes: RC_MAX_C channels per row (any count up to it), RC_MAX_ROWS rows, RL_MAX_BINS bins per head.
+# train_functions routes a configuration beyond them to the composed loss; the exports answer PRCNN_EUNSUPPORTED.
+RCNN_LOSS_MAX_C = 56
+RCNN_LOSS_MAX_ROWS = 1 << 24
+RCNN_LOSS_TERMS = 23
+
+
+def rcnn_loss_cfg(cfg, mean_size):
+    """an RCNNConfig-like object + CLS_MEAN_SIZE -> prcnn_rcnn_loss_cfg_t (loss kinds numbered as rpn_loss_cfg; what
+    csrc/rcnn_loss.hip accepts is decided there)"""
+    kinds = {"SigmoidFocalLoss": 0, "DiceLoss": 1, "BinaryCrossEntropy": 2}
+    alpha = cfg.FOCAL_ALPHA[0]
+    return _cabi.RcnnLossCfg(loc_scope=float(cfg.LOC_SCOPE), loc_bin_size=float(cfg.LOC_BIN_SIZE), loc_y_scope=float(cfg.LOC_Y_SCOPE),
+                             loc_y_bin_size=float(cfg.LOC_Y_BIN_SIZE), mean_size=(ctypes.c_double * 3)(*[float(v) for v in mean_size]),
+                             gamma=float(cfg.FOCAL_GAMMA), alpha=0.0 if alpha is None else float(alpha),
+                             num_head_bin=int(cfg.NUM_HEAD_BIN), y_by_bin=int(bool(cfg.LOC_Y_BY_BIN)),
+                             size_res_on_roi=int(bool(cfg.SIZE_RES_ON_ROI)), loss_cls=kinds.get(cfg.LOSS_CLS, -1),
+                             has_alpha=int(alpha is not None))
+
+
+def rcnn_loss_channels(cfg):
+    """channels of an rcnn_reg row under cfg: 4 * nb + (2 * nby or 1) + 2 * NUM_HEAD_BIN + 3"""
+    nb = int(cfg.LOC_SCOPE / cfg.LOC_BIN_SIZE) * 2
+    nby = int(cfg.LOC_Y_SCOPE / cfg.LOC_Y_BIN_SIZE) * 2
+    return 4 * nb + (2 * nby if cfg.LOC_Y_BY_BIN else 1) + 2 * int(cfg.NUM_HEAD_BIN) + 3
+
+
+def _rcnn_loss_ints(t, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in (torch.int32, torch.int64)):
+        raise RuntimeError("rcnn_loss: %s must be an int32 or int64 CUDA(HIP) tensor" % name)
+    return t.contiguous(), int(t.dtype == torch.int64)
+
+
+def _rcnn_loss_work(R, device):
+    return torch.empty((_cabi.lib().prcnn_rcnn_loss_workspace_bytes(R) + 7) // 8, dtype=torch.int64, device=device)
+
+
+def _rcnn_loss_prelude(rcnn_cls, rcnn_reg, cls_label, reg_valid_mask, roi_boxes3d, gt_of_rois):
+    for name, t in (("rcnn_cls", rcnn_cls), ("rcnn_reg", rcnn_reg)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == _F32):
+            raise RuntimeError("rcnn_loss: %s must be a float32 CUDA(HIP) tensor" % name)
+    C = rcnn_reg.shape[-1]
+    R = rcnn_reg.numel() // C
+    if rcnn_cls.numel() != R or cls_label.numel() != R or reg_valid_mask.numel() != R:
+        raise ValueError("rcnn_loss: rcnn_cls / cls_label / reg_valid_mask must have %d rows" % R)
+    _chk(roi_boxes3d, "roi_boxes3d"); _chk(gt_of_rois, "gt_of_rois")
+    for name, t in (("roi_boxes3d", roi_boxes3d), ("gt_of_rois", gt_of_rois)):
+        if t.numel() != R * 7 or t.shape[-1] != 7:
+            raise ValueError("rcnn_loss: %s must be (..., 7) with %d rows" % (name, R))
+    label, label64 = _rcnn_loss_ints(cls_label, "cls_label")
+    mask, mask64 = _rcnn_loss_ints(reg_valid_mask, "reg_valid_mask")
+    cls_rows, ld_cls = _uniform_rows(rcnn_cls.reshape(rcnn_cls.shape + (1,)) if rcnn_cls.dim() == 1 else rcnn_cls)
+    reg_rows, ld_reg = _uniform_rows(rcnn_reg)
+    args = (_p(cls_rows), ld_cls, _p(reg_rows), ld_reg, _p(label), label64, _p(mask), mask64, _p(roi_boxes3d), _p(gt_of_rois), R, C)
+    return args, (cls_rows, reg_rows, label, mask)
+
+
+def rcnn_loss_forward(rcnn_cls, rcnn_reg, cls_label, reg_valid_mask, roi_boxes3d, gt_of_rois, cfg, finalize=True):
+    """rcnn_cls (R,1), rcnn_reg (R,C) f32 (views whose rows sit at ONE stride are read in place, see _uniform_rows; C is any count
+    up to RCNN_LOSS_MAX_C), cls_label (R) and reg_valid_mask (R) i32 / i64, roi_boxes3d (R,7), gt_of_rois (R,7), cfg (rcnn_loss_cfg)
+    -> counts (4) i32 {#(label > 0), #(label >= 0), #(mask > 0), sum of mask}, terms (RCNN_LOSS_TERMS) f32 or None, work.
+    finalize=True: the single-process loss, one launch up to 256 rows and two beyond.  finalize=False (data-parallel callers): the
+    counts and the unnormalised sums in work only, one launch; rcnn_loss_finalize follows.  Nothing is read back."""
+    args, keep = _rcnn_loss_prelude(rcnn_cls, rcnn_reg, cls_label, reg_valid_mask, roi_boxes3d, gt_of_rois)
+    dev = rcnn_reg.device
+    counts = torch.empty((4,), dtype=_INT, device=dev)
+    terms = torch.empty((RCNN_LOSS_TERMS,), dtype=_F32, device=dev) if finalize else None
+    work = _rcnn_loss_work(args[10], dev)
+    _cabi.check(_cabi.lib().prcnn_rcnn_loss_forward(*args, ctypes.byref(cfg), int(bool(finalize)), _p(counts), _p(terms), _p(work),
+                                                    work.numel() * 8, _stream()), "prcnn_rcnn_loss_forward")
+    return counts, terms, work
+
+
+def rcnn_loss_finalize(R, C, cfg, counts, norm, work):
+    """the sums rcnn_loss_forward(finalize=False) left in work + counts + norm (2) f32 {classification scale, regression scale} (or
+    None: the single-process normalisers) -> terms (RCNN_LOSS_TERMS) f32; one launch"""
+    _chk(counts, "counts", _INT, 1)
+    if norm is not None:
+        _chk(norm, "norm", _F32, 1)
+    terms = torch.empty((RCNN_LOSS_TERMS,), dtype=_F32, device=counts.device)
+    _cabi.check(_cabi.lib().prcnn_rcnn_loss_finalize(R, C, ctypes.byref(cfg), _p(counts), _p(norm), _p(terms), _p(work), work.numel() * 8,
+                                                     _stream()), "prcnn_rcnn_loss_finalize")
+    return terms
+
+
+def rcnn_loss_backward(rcnn_cls, rcnn_reg, cls_label, reg_valid_mask, roi_boxes3d, gt_of_rois, cfg, counts, norm, grad_out):
+    """the inputs of rcnn_loss_forward + its counts, the norm given to rcnn_loss_finalize (or None) and grad_out (a float32 device
+    scalar) -> grad_out * d loss / d rcnn_cls, d loss / d rcnn_reg, contiguous, in the inputs' shapes; one launch that writes every
+    entry once"""
+    args, keep = _rcnn_loss_prelude(rcnn_cls, rcnn_reg, cls_label, reg_valid_mask, roi_boxes3d, gt_of_rois)
+    _chk(counts, "counts", _INT, 1); _chk(grad_out, "grad_out")
+    if norm is not None:
+        _chk(norm, "norm", _F32, 1)
+    if grad_out.numel() != 1:
+        raise ValueError("rcnn_loss_backward: grad_out must be a scalar")
+    dcls = torch.empty(rcnn_cls.shape, dtype=_F32, device=rcnn_cls.device)
+    dreg = torch.empty(rcnn_reg.shape, dtype=_F32, device=rcnn_reg.device)
+    _cabi.check(_cabi.lib().prcnn_rcnn_loss_backward(*args, ctypes.byref(cfg), _p(counts), _p(norm), _p(grad_out), _p(dcls), _p(dreg),
+                                                     _stream()), "prcnn_rcnn_loss_backward")
+    return dcls, dreg
+
+
 def gt_aug_edit(pts, intensity, boxes3d, new_pts, new_intensity, num_pts=None, num_boxes=None, num_new=None, extra_h=2.0,
                 want_removed=False):
     """The point work of KittiRCNNDataset.apply_gt_aug_to_one_scene (kitti_rcnn_dataset.py:484-507) for a batch of scenes.
