@@ -58,6 +58,7 @@ typedef void* prcnn_stream_t; /* hipStream_t */
 #define PRCNN_EUNSUPPORTED (-3) /* valid request this build has no kernel for */
 
 int prcnn_abi_version(void);   /* 12: + prcnn_switches_reload, prcnn_switch_get (the PRCNN_* kernel switches are read once, through one table);
+                                 * still 12 (additive): + prcnn_fps_nested (a nested FPS level answered from the parent's sample order);
                                  * still 12 (additive, no caller breaks): + prcnn_gt_database_workspace_bytes, prcnn_gt_database_count,
                                  * prcnn_gt_database_fill (the GT-augmentation database built on the device);
                                  * still 12 (additive): + prcnn_rpn_loss_workspace_bytes, prcnn_rpn_loss_counts, prcnn_rpn_loss_forward,
@@ -104,6 +105,16 @@ int prcnn_switch_get(const char* name, int* set, long* num);
  * and the indices returned for it are unspecified (always within [0, N)).  Callers with unvalidated input filter first
  * (prcnn_scene_prepare drops non-finite raw points). */
 int prcnn_fps(const float* xyz, int B, int N, int npoint, float* tmp, int32_t* idx, prcnn_stream_t stream);
+
+/* prcnn_fps for a NESTED level: xyz (B,N,3) must be gather(parent cloud, prev_idx), where prev_idx (B,N) i32 is what prcnn_fps
+ * returned for the parent cloud with npoint = N (canonical tie order).  FPS is greedy, so the first npoint samples of such a cloud
+ * are positions 0, 1, 2, ... unless the parent ran out of distinct points or a coordinate is non-finite / huge.  A device pass
+ * decides that per frame (every |coordinate| < 1e4 and prev_idx[b][1 .. npoint-1] != 0; csrc/fps.hip states why that suffices):
+ * a frame that passes gets idx[b][j] = j and skip[b] = 1, every other frame gets skip[b] = 0 and runs the kernels of prcnn_fps.
+ * Same indices as prcnn_fps(xyz, ...) bit for bit, no host synchronisation (safe inside a graph capture).
+ * Requires npoint <= N <= 16384; `tmp` as for prcnn_fps; skip (B) i32 is written, not read, by the caller. */
+int prcnn_fps_nested(const float* xyz, const int32_t* prev_idx, int B, int N, int npoint, float* tmp, int32_t* idx, int32_t* skip,
+                     prcnn_stream_t stream);
 
 /* N > 16384 runs one frame on several cooperating workgroups whose wait for each other is bounded (a hang would take the
  * GPU down); a workgroup that gave up fills the rest of its frame's output with -1 and marks a host-visible word.

@@ -59,6 +59,7 @@ SIGNATURES = {
     "prcnn_switches_reload": (_I, []),
     "prcnn_switch_get": (_I, [ctypes.c_char_p, ctypes.POINTER(_I), ctypes.POINTER(ctypes.c_long)]),
     "prcnn_fps": (_I, [_P, _I, _I, _I, _P, _P, _P]),
+    "prcnn_fps_nested": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "prcnn_fps_status": (_I, []),
     "prcnn_fps_order": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "prcnn_fps_mode": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),

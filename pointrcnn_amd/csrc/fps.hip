@@ -177,7 +177,8 @@ template <class V> __device__ __forceinline__ int wave_max_eq2_16(const V& pt, f
 
 template <int BLOCK, int PPT>
 __global__ __launch_bounds__(BLOCK) void fps_reg_kernel(const float* __restrict__ xyz, int N, int npoint,
-                                                        int32_t* __restrict__ idx_out) {
+                                                        int32_t* __restrict__ idx_out, const int32_t* __restrict__ skip) {
+    if (skip && skip[blockIdx.x]) return;          // fps_prefix_kernel answered this frame (workgroup-uniform, ahead of any barrier)
     constexpr int NW = BLOCK / 64;
     typedef typename fvec_t<PPT>::type fvec;
     __shared__ float slot[2][NW][8];   // val(bits), idx(bits), x, y, z, pad...
@@ -308,7 +309,9 @@ __device__ __forceinline__ unsigned morton_spread6(unsigned v) {       // 6 bits
 // the key is half the time (95 -> ~50 us per 16 384-point frame set) and half the LDS (136 -> 68 KB, which kept every other
 // workgroup off the CU).  The order only decides how compact a slot's 64 points are, never a result (ties go to the ORIGINAL index
 // inside the FPS kernels): 64 cells per axis leave ~1 point per occupied cell at 16 384 points.
-__global__ __launch_bounds__(1024) void fps_sort_kernel(const float* __restrict__ xyz, int N, int NP, int32_t* __restrict__ perm) {
+__global__ __launch_bounds__(1024) void fps_sort_kernel(const float* __restrict__ xyz, int N, int NP, int32_t* __restrict__ perm,
+                                                        const int32_t* __restrict__ skip) {
+    if (skip && skip[blockIdx.x]) return;          // fps_prefix_kernel answered this frame: nobody reads its permutation
     extern __shared__ unsigned keys[];
     __shared__ float red[6][16];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
@@ -443,7 +446,8 @@ PRCNN_API int prcnn_fps_timing_read(unsigned long long* host_out) {
 
 template <int PPT>
 __global__ __launch_bounds__(1024) void fps_pruned_kernel(const float* __restrict__ xyz, const int32_t* __restrict__ perm,
-                                                          int N, int npoint, int32_t* __restrict__ idx_out) {
+                                                          int N, int npoint, int32_t* __restrict__ idx_out, const int32_t* __restrict__ skip) {
+    if (skip && skip[blockIdx.x]) return;          // fps_prefix_kernel answered this frame (workgroup-uniform, ahead of any barrier)
     constexpr int BLOCK = 1024, NW = 16;
     typedef typename fvec_t<PPT>::type fvec;
     FPS_XT_DECL;
@@ -619,7 +623,8 @@ __global__ __launch_bounds__(1024) void fps_pruned_kernel(const float* __restric
 // =====================================================================================================
 template <int PPT, int NW>
 __global__ __launch_bounds__(NW * 64) void fps_slot_kernel(const float* __restrict__ xyz, const int32_t* __restrict__ perm,
-                                                          int N, int npoint, int32_t* __restrict__ idx_out) {
+                                                          int N, int npoint, int32_t* __restrict__ idx_out, const int32_t* __restrict__ skip) {
+    if (skip && skip[blockIdx.x]) return;          // fps_prefix_kernel answered this frame (workgroup-uniform, ahead of any barrier)
     constexpr int BLOCK = NW * 64;          // NW waves x 64 lanes x PPT points (16 x 16 for 16 384 points; the 4 096-point level on 8 x 8: 716, on 4 x 16: 748 vs 653 us for 16 waves x 4 points -- not used)
     typedef typename fvec_t<PPT>::type fvec;
     FPS_XT_DECL;
@@ -882,7 +887,8 @@ __device__ __forceinline__ void fps_bcand_set(fps_bcand_t& c, int wave, float cx
 
 template <int PPT, int NW>
 __global__ __launch_bounds__(NW * 64) void fps_batch_kernel(const float* __restrict__ xyz, const int32_t* __restrict__ perm,
-                                                           int N, int npoint, int32_t* __restrict__ idx_out) {
+                                                           int N, int npoint, int32_t* __restrict__ idx_out, const int32_t* __restrict__ skip) {
+    if (skip && skip[blockIdx.x]) return;          // fps_prefix_kernel answered this frame (workgroup-uniform, ahead of any barrier)
     static_assert(NW == 16 && PPT == 16, "rows of 16 lanes = the 16 waves; 8 pair boxes");
     constexpr int BLOCK = NW * 64;
     typedef typename fvec_t<PPT>::type fvec;
@@ -1276,8 +1282,8 @@ __global__ __launch_bounds__(1024) void fps_mem_kernel(const float* __restrict__
 }
 
 template <int BLOCK, int PPT>
-static void launch_fps(const float* xyz, int B, int N, int npoint, int32_t* idx, hipStream_t s) {
-    hipLaunchKernelGGL((fps_reg_kernel<BLOCK, PPT>), dim3(B), dim3(BLOCK), 0, s, xyz, N, npoint, idx);
+static void launch_fps(const float* xyz, int B, int N, int npoint, int32_t* idx, const int32_t* skip, hipStream_t s) {
+    hipLaunchKernelGGL((fps_reg_kernel<BLOCK, PPT>), dim3(B), dim3(BLOCK), 0, s, xyz, N, npoint, idx, skip);
 }
 
 // The multi-slice kernel's poll is bounded; a slice that gave up marks this pinned host word (device-mapped, written with a
@@ -1301,12 +1307,40 @@ PRCNN_API int prcnn_fps_status(void) {
     return PRCNN_OK;
 }
 
-PRCNN_API int prcnn_fps(const float* xyz, int B, int N, int npoint, float* tmp, int32_t* idx, prcnn_stream_t stream) {
-    PRCNN_REQUIRE(B >= 0 && N > 0 && npoint >= 0, "prcnn_fps: bad shape B=%d N=%d npoint=%d", B, N, npoint);
-    PRCNN_REQUIRE(npoint <= N, "prcnn_fps: npoint %d > N %d", npoint, N);
-    if (B == 0 || npoint == 0) return PRCNN_OK;          // empty problem: pointers may legitimately be null
-    PRCNN_REQUIRE(xyz && idx, "prcnn_fps: null pointer");
-    hipStream_t s = (hipStream_t)stream;
+// =====================================================================================================
+// Nested levels (prcnn_fps_nested).  FPS is greedy: if p0, p1, ... is the FPS order of a set S, FPS run on S' = [p0 .. p(N-1)] IN THAT
+// ORDER returns positions 0, 1, 2, ...  The running min-distance of a point of S' to the chosen points is the same number in both runs
+// (the same sqdist3 of the same coordinates, the same minimum), p_j was the maximum over all of S and therefore over S', and under the
+// canonical tie rule (lowest index) it sits at position j, the lowest position not yet selected (the selected ones hold 0 < maximum).
+// The property fails when (a) the selected maximum reached 0 -- fewer distinct points than samples; the oracle's `best = -1, besti = 0`
+// scan then returns index 0 again, and ONLY then: index 0 holds distance 0 from the first step on -- or (b) a distance cannot fall
+// below the 1e10 start value (a NaN / inf / huge coordinate): such a point keeps 1e10 and is selected again.  Both are recognised per
+// frame from what the nested level reads anyway; frame b is answered with iota when
+//   every coordinate c of S' satisfies fabsf(c) < 1e4f   (false for NaN and inf), and
+//   prev_idx[b][j] != 0 for all 1 <= j < npoint          (prev_idx = the indices the parent FPS returned, S' = gather(S, prev_idx)).
+// Why that suffices: a point of S whose distance to p0 is not below 1e10 holds the largest possible running distance, so one of them is
+// the parent's second sample and a bad point of S shows up in S'; with all of S' inside 1e4 every squared distance among its points is
+// at most 3 * (2e4)^2 = 1.2e9 < 1e10, so case (b) is excluded for S'; and "index 0 appears again among the first npoint parent samples"
+// is exactly case (a) for the steps the nested level takes.  A frame that fails either test keeps skip[b] = 0 and runs the kernels
+// below as before (same bits).  The upstream tie order breaks the position argument on lattices, so only the canonical entry uses this.
+// =====================================================================================================
+__global__ __launch_bounds__(256) void fps_prefix_kernel(const float* __restrict__ xyz, const int32_t* __restrict__ prev_idx, int N, int npoint,
+                                                         int32_t* __restrict__ idx_out, int32_t* __restrict__ skip) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* __restrict__ p = xyz + (size_t)b * N * 3;
+    const int32_t* __restrict__ pi = prev_idx + (size_t)b * N;
+    int32_t* __restrict__ out = idx_out + (size_t)b * npoint;
+    bool ok = true;
+    for (int k = tid; k < 3 * N; k += 256) ok &= fabsf(p[k]) < 1e4f;          // NaN, inf: the comparison is false
+    for (int j = 1 + tid; j < npoint; j += 256) ok &= pi[j] != 0;
+    const int pass = __syncthreads_and(ok) ? 1 : 0;
+    if (pass)
+        for (int j = tid; j < npoint; j += 256) out[j] = j;
+    if (tid == 0) skip[b] = pass;
+}
+
+// The size ladder of prcnn_fps / prcnn_fps_nested; `skip` (null, or one word per frame written by fps_prefix_kernel) only for N <= 16384.
+static int fps_dispatch(const float* xyz, int B, int N, int npoint, float* tmp, int32_t* idx, const int32_t* skip, hipStream_t s) {
     if (tmp && N > 2048 && N <= 16384) {
         // spatially pruned path: tmp (B,N) 4-byte entries holds the Morton-order permutation
         int NP = 1;
@@ -1316,7 +1350,7 @@ PRCNN_API int prcnn_fps(const float* xyz, int B, int N, int npoint, float* tmp, 
         if (!sort_attr.raise((const void*)fps_sort_kernel, 80 * 1024))
             return prcnn_fail(PRCNN_EHIP, "prcnn_fps: cannot raise the dynamic LDS limit of the sort kernel");
         const int sort_threads = NP / 16 < 64 ? 64 : NP / 16;
-        hipLaunchKernelGGL(fps_sort_kernel, dim3(B), dim3(sort_threads), lds_sort_bytes(NP, sizeof(unsigned)), s, xyz, N, NP, perm);
+        hipLaunchKernelGGL(fps_sort_kernel, dim3(B), dim3(sort_threads), lds_sort_bytes(NP, sizeof(unsigned)), s, xyz, N, NP, perm, skip);
         PRCNN_LAUNCH_CHECK("prcnn_fps(sort)");
         static PrcnnLdsLimit pruned_attr;
         if (!pruned_attr.raise((const void*)fps_pruned_kernel<16>, 16 * 4096))
@@ -1333,24 +1367,25 @@ PRCNN_API int prcnn_fps(const float* xyz, int B, int N, int npoint, float* tmp, 
         static PrcnnLdsLimit batch_attr;
         if (slots && batch && N > 8192 && !batch_attr.raise((const void*)fps_batch_kernel<16, 16>, 16 * 4096))
             return prcnn_fail(PRCNN_EHIP, "prcnn_fps: cannot raise the dynamic LDS limit of the batch kernel");
-        if (slots && batch && N > 8192) hipLaunchKernelGGL((fps_batch_kernel<16, 16>), dim3(B), dim3(1024), 16 * 4096, s, xyz, perm, N, npoint, idx);
-        else if (slots && N > 8192) hipLaunchKernelGGL((fps_slot_kernel<16, 16>), dim3(B), dim3(1024), 16 * 4096, s, xyz, perm, N, npoint, idx);
+        if (slots && batch && N > 8192) hipLaunchKernelGGL((fps_batch_kernel<16, 16>), dim3(B), dim3(1024), 16 * 4096, s, xyz, perm, N, npoint, idx, skip);
+        else if (slots && N > 8192) hipLaunchKernelGGL((fps_slot_kernel<16, 16>), dim3(B), dim3(1024), 16 * 4096, s, xyz, perm, N, npoint, idx, skip);
         // (4 096 -> 1 024 with the sort, round 6: 16 waves x 4 points per lane 578 us; the same kernel on 8 waves x 8: 629, on 4 waves x 16: 757)
-        else if (N <= 4096) hipLaunchKernelGGL((fps_pruned_kernel<4>), dim3(B), dim3(1024), 4 * 4096, s, xyz, perm, N, npoint, idx);
-        else if (N <= 8192) hipLaunchKernelGGL((fps_pruned_kernel<8>), dim3(B), dim3(1024), 8 * 4096, s, xyz, perm, N, npoint, idx);
-        else hipLaunchKernelGGL((fps_pruned_kernel<16>), dim3(B), dim3(1024), 16 * 4096, s, xyz, perm, N, npoint, idx);
+        else if (N <= 4096) hipLaunchKernelGGL((fps_pruned_kernel<4>), dim3(B), dim3(1024), 4 * 4096, s, xyz, perm, N, npoint, idx, skip);
+        else if (N <= 8192) hipLaunchKernelGGL((fps_pruned_kernel<8>), dim3(B), dim3(1024), 8 * 4096, s, xyz, perm, N, npoint, idx, skip);
+        else hipLaunchKernelGGL((fps_pruned_kernel<16>), dim3(B), dim3(1024), 16 * 4096, s, xyz, perm, N, npoint, idx, skip);
     }
-    else if (N <= 64) launch_fps<64, 1>(xyz, B, N, npoint, idx, s);
-    else if (N <= 128) launch_fps<64, 2>(xyz, B, N, npoint, idx, s);
-    else if (N <= 256) launch_fps<64, 4>(xyz, B, N, npoint, idx, s);
-    else if (N <= 512) launch_fps<64, 8>(xyz, B, N, npoint, idx, s);
-    else if (N <= 1024) launch_fps<64, 16>(xyz, B, N, npoint, idx, s);
-    else if (N <= 2048) launch_fps<256, 8>(xyz, B, N, npoint, idx, s);
-    else if (N <= 4096) launch_fps<256, 16>(xyz, B, N, npoint, idx, s);
-    else if (N <= 8192) launch_fps<1024, 8>(xyz, B, N, npoint, idx, s);
-    else if (N <= 16384) launch_fps<1024, 16>(xyz, B, N, npoint, idx, s);
+    else if (N <= 64) launch_fps<64, 1>(xyz, B, N, npoint, idx, skip, s);
+    else if (N <= 128) launch_fps<64, 2>(xyz, B, N, npoint, idx, skip, s);
+    else if (N <= 256) launch_fps<64, 4>(xyz, B, N, npoint, idx, skip, s);
+    else if (N <= 512) launch_fps<64, 8>(xyz, B, N, npoint, idx, skip, s);
+    else if (N <= 1024) launch_fps<64, 16>(xyz, B, N, npoint, idx, skip, s);
+    else if (N <= 2048) launch_fps<256, 8>(xyz, B, N, npoint, idx, skip, s);
+    else if (N <= 4096) launch_fps<256, 16>(xyz, B, N, npoint, idx, skip, s);
+    else if (N <= 8192) launch_fps<1024, 8>(xyz, B, N, npoint, idx, skip, s);
+    else if (N <= 16384) launch_fps<1024, 16>(xyz, B, N, npoint, idx, skip, s);
     else {
         PRCNN_REQUIRE(tmp, "prcnn_fps: N=%d > 16384 needs the (B,N) tmp buffer", N);
+        PRCNN_REQUIRE(!skip, "prcnn_fps: the multi-workgroup kernels (N=%d > 16384) take no skip words", N);
         const int S = prcnn_divup(N, FPS_MULTI_SLICE);
         // multi-workgroup register-resident kernel: the exchange slots (B * 2 * S * 5 granules of 8 bytes) live at the start
         // of tmp, which is 4 N bytes per frame >= 80 S bytes.  Needs every slice of a frame resident at once: up to 256 CUs.
@@ -1367,6 +1402,27 @@ PRCNN_API int prcnn_fps(const float* xyz, int B, int N, int npoint, float* tmp, 
     }
     PRCNN_LAUNCH_CHECK("prcnn_fps");
     return PRCNN_OK;
+}
+
+PRCNN_API int prcnn_fps(const float* xyz, int B, int N, int npoint, float* tmp, int32_t* idx, prcnn_stream_t stream) {
+    PRCNN_REQUIRE(B >= 0 && N > 0 && npoint >= 0, "prcnn_fps: bad shape B=%d N=%d npoint=%d", B, N, npoint);
+    PRCNN_REQUIRE(npoint <= N, "prcnn_fps: npoint %d > N %d", npoint, N);
+    if (B == 0 || npoint == 0) return PRCNN_OK;          // empty problem: pointers may legitimately be null
+    PRCNN_REQUIRE(xyz && idx, "prcnn_fps: null pointer");
+    return fps_dispatch(xyz, B, N, npoint, tmp, idx, nullptr, (hipStream_t)stream);
+}
+
+PRCNN_API int prcnn_fps_nested(const float* xyz, const int32_t* prev_idx, int B, int N, int npoint, float* tmp, int32_t* idx, int32_t* skip,
+                               prcnn_stream_t stream) {
+    PRCNN_REQUIRE(B >= 0 && N > 0 && npoint >= 0, "prcnn_fps_nested: bad shape B=%d N=%d npoint=%d", B, N, npoint);
+    PRCNN_REQUIRE(npoint <= N, "prcnn_fps_nested: npoint %d > N %d", npoint, N);
+    PRCNN_REQUIRE(N <= 16384, "prcnn_fps_nested: N=%d > 16384 (call prcnn_fps)", N);
+    if (B == 0 || npoint == 0) return PRCNN_OK;
+    PRCNN_REQUIRE(xyz && prev_idx && idx && skip, "prcnn_fps_nested: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(fps_prefix_kernel, dim3(B), dim3(256), 0, s, xyz, prev_idx, N, npoint, idx, skip);
+    PRCNN_LAUNCH_CHECK("prcnn_fps_nested(prefix)");
+    return fps_dispatch(xyz, B, N, npoint, tmp, idx, skip, s);
 }
 
 // =====================================================================================================

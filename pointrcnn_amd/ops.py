@@ -8,6 +8,7 @@ import ctypes
 import math
 import os
 import threading
+import weakref
 
 import torch
 
@@ -19,6 +20,10 @@ _F32 = torch.float32
 # results, ~35 % shorter serial chain.  With the neighbour searches on the grid the FPS chain is the longest dependency of
 # a batch, so it is the default (+8 % RPN throughput at 3 batches in flight); PRCNN_FPS_PRUNED=0 selects the plain kernel.
 FPS_PRUNED = os.environ.get("PRCNN_FPS_PRUNED", "1") == "1"
+# A nested FPS level (a cloud that IS the sample set of the previous level, in sample order) is answered from the parent's indices
+# by prcnn_fps_nested: positions 0, 1, 2, ... for every frame a device pass accepts, the plain kernels for the rest.  Same bits;
+# PRCNN_FPS_NESTED=0 selects plain FPS at every level (A/B).
+FPS_NESTED = os.environ.get("PRCNN_FPS_NESTED", "1") == "1"
 
 
 def _stream():
@@ -43,6 +48,17 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
+def _tensor_key(t):
+    return (t.data_ptr(), tuple(t.shape), tuple(t.stride()), t._version)
+
+
+def _hintable(*tensors):
+    """the nested-FPS hint may ride on these tensors: the switch is on and every one of them tracks a version counter.  A tensor made
+    under torch.inference_mode() does not (reading _version raises, and an in-place write leaves no trace), so it never carries a hint
+    and its FPS levels all take plain prcnn_fps."""
+    return FPS_NESTED and not any(t.is_inference() for t in tensors)
+
+
 # ------------------------------------------------------------------ PointNet++ operators
 def furthest_point_sample(xyz, npoint, order="canonical"):
     """xyz (B,N,3) f32 -> idx (B,npoint) i32   [pointnet2_utils.furthest_point_sample]
@@ -62,7 +78,22 @@ def furthest_point_sample(xyz, npoint, order="canonical"):
     # HBM-resident min-distance array (N > 16384); the small-N kernels need none
     tmp = torch.empty((B, N), dtype=_F32, device=xyz.device) if (N > 16384 or (N > 2048 and FPS_PRUNED)) else None
     L = _cabi.lib()
-    _cabi.check(L.prcnn_fps(_p(xyz), B, N, npoint, _p(tmp), _p(idx), _stream()), "prcnn_fps")
+    # the modules hand each other tensors only, so the hint rides on them: gather_rows tags the sample set it writes with the
+    # indices that made it (see there); any doubt -- another object, a view, a copy, an in-place write since -- means plain FPS
+    parent = getattr(xyz, "_prcnn_fps_parent", None) if _hintable(xyz) else None
+    if parent is not None:
+        prev_idx, prev_version, key = parent
+        if not (_hintable(prev_idx) and key == _tensor_key(xyz) and prev_idx._version == prev_version and prev_idx.device == xyz.device
+                and tuple(prev_idx.shape) == (B, N) and npoint <= N <= 16384):
+            parent = None
+    if parent is not None:
+        skip = torch.empty((B,), dtype=_INT, device=xyz.device)
+        _cabi.check(L.prcnn_fps_nested(_p(xyz), _p(prev_idx), B, N, npoint, _p(tmp), _p(idx), _p(skip), _stream()), "prcnn_fps_nested")
+    else:
+        _cabi.check(L.prcnn_fps(_p(xyz), B, N, npoint, _p(tmp), _p(idx), _stream()), "prcnn_fps")
+    # the identity (not the address: a new tensor can land where a dropped one was) and the state of the tensor these indices sample
+    if _hintable(xyz, idx):
+        idx._prcnn_fps_src = (weakref.ref(xyz), _tensor_key(xyz), idx._version)
     return idx
 
 
@@ -136,6 +167,10 @@ def gather_rows(in_cl, idx):
     out = torch.empty((B, M, C), dtype=_F32, device=in_cl.device)
     _cabi.check(_cabi.lib().prcnn_gather_rows(_p(in_cl), _row_stride(in_cl), _p(idx), B, N, M, C, _p(out), _stream()),
                 "prcnn_gather_rows")
+    src = getattr(idx, "_prcnn_fps_src", None) if (C == 3 and _hintable(in_cl, idx, out)) else None
+    if src is not None and src[0]() is in_cl and src[1] == _tensor_key(in_cl) and src[2] == idx._version:
+        # `out` is the canonical FPS sample set of in_cl in sample order: a later furthest_point_sample(out, m <= M) may answer from idx
+        out._prcnn_fps_parent = (idx, idx._version, _tensor_key(out))
     return out
 
 
