@@ -58,6 +58,7 @@ typedef void* prcnn_stream_t; /* hipStream_t */
 #define PRCNN_EUNSUPPORTED (-3) /* valid request this build has no kernel for */
 
 int prcnn_abi_version(void);   /* 12: + prcnn_switches_reload, prcnn_switch_get (the PRCNN_* kernel switches are read once, through one table);
+                                 * still 12 (additive): + prcnn_rcnn_offline_sample, prcnn_rcnn_offline_finish (RCNN offline training batches);
                                  * still 12 (additive): + prcnn_fps_nested (a nested FPS level answered from the parent's sample order);
                                  * still 12 (additive, no caller breaks): + prcnn_gt_database_workspace_bytes, prcnn_gt_database_count,
                                  * prcnn_gt_database_fill (the GT-augmentation database built on the device);
@@ -784,6 +785,41 @@ int prcnn_proposal_target_sample(const float* roi_boxes3d, const float* gt_boxes
                                  const double* cfg6, int aug_times, int aug_method, uint32_t seed, float* rois, float* gt_of_rois,
                                  float* roi_iou, int32_t* src, float* max_overlaps, int32_t* gt_assignment, int32_t* counts,
                                  int32_t* status, prcnn_stream_t stream);
+
+/* ======================================================================================================
+ * RoI sampling for RCNN offline training (csrc/rcnn_offline.hip, per-slot arithmetic: csrc/rcnn_offline_math.h) --
+ * `train_rcnn.py --train_mode rcnn_offline` with RCNN.ROI_SAMPLE_JIT False.
+ * prcnn_rcnn_offline_sample: the sampling part of KittiRCNNDataset.get_rcnn_training_sample_batch
+ * (lib/datasets/kitti_rcnn_dataset.py:890-957, sample_bg_inds :1024-1050, aug_roi_by_noise_batch :1052-1077, random_aug_box3d
+ * :747-788) for a batch in two launches, no host round trip:
+ *   roi_boxes3d (B, M, 7) with num_roi (B), gt_boxes3d (B, G, 7) with num_gt (B): both ragged and COUNTED (M <= 4096, G <= 128);
+ *   frame_ids (B) or NULL: the id of every frame in the random table (NULL: its position in the batch);
+ *   cfg6 (HOST pointer, six doubles) as for prcnn_proposal_target_sample; aug_times = the attempts on a foreground slot (the
+ *   reference's 10; a background slot gets one), aug_method 0 = 'multiple', 1 = 'single';
+ *   -> iou3d (B, M, G) kitti_utils.get_iou3d on boxes3d_to_corners3d corners (0 past the counts), rois, gt_of_rois (B, R, 7),
+ *   roi_iou (B, R) the noise loop's last IoU, src (B, R) the input RoI behind every slot, max_overlaps / gt_assignment (B, M)
+ *   (0 / -1 past num_roi), counts (B, 4) = foreground list length (threshold entries + the labels' best RoIs, duplicates kept) /
+ *   hard / easy candidates and foreground slots, status (B): 0 ok, 1 = the reference raises (foreground but no background
+ *   candidate, no candidate, no RoI), 2 = no label.  A frame with status != 0 has rois, gt_of_rois, roi_iou cleared and src -1.
+ * The random draw is the counter table of csrc/counter_rand.h, streams 40, 42, 43, 50 (see the kernel file). */
+int prcnn_rcnn_offline_sample(const float* roi_boxes3d, const int32_t* num_roi, const float* gt_boxes3d, const int32_t* num_gt,
+                              const int32_t* frame_ids, int B, int M, int G, int roi_per_image, const double* cfg6, int aug_times,
+                              int aug_method, uint32_t seed, float* iou3d, float* rois, float* gt_of_rois, float* roi_iou, int32_t* src,
+                              float* max_overlaps, int32_t* gt_assignment, int32_t* counts, int32_t* status, prcnn_stream_t stream);
+
+/* prcnn_rcnn_offline_finish: everything of that method after pooling (:976-1010) in one pass over the pooled tensor
+ * (prcnn_roipool3d on the sampled RoIs, enlarged): pooled (B * R, S, ld) with xyz in columns 0:3, REWRITTEN IN PLACE -- per RoI the
+ * rotation by the drawn angle, the scale, the flip (data_augmentation stage 2 with mustaug), the shift to the augmented RoI's centre
+ * and the rotation by ry mod 2 pi; the other columns are not touched.  rois / gt_of_rois / roi_iou / status: the sampler's outputs;
+ * pooled_empty_flag (B, R) from the pooling; cfg5 (HOST, five doubles): REG_FG_THRESH, CLS_FG_THRESH, CLS_BG_THRESH,
+ * AUG_METHOD_PROB[2], AUG_ROT_RANGE; aug_methods: mask of 'rotation' 1, 'scaling' 2, 'flip' 4 in AUG_METHOD_LIST, 0 = AUG_DATA off
+ * (only the canonical transform and the labels run).  -> out_rois, out_gt_of_rois (B, R, 7) the augmented boxes, gt_boxes3d_ct
+ * (B, R, 7), cls_label (B, R) in {-1, 0, 1}, reg_valid_mask (B, R).  A frame with status != 0: its pooled rows (every column) and boxes cleared,
+ * label -1, mask 0.  Random streams 51, 52, 53 (csrc/rcnn_offline_math.h). */
+int prcnn_rcnn_offline_finish(float* pooled, int ld, int B, int R, int S, const float* rois, const float* gt_of_rois,
+                              const float* roi_iou, const int32_t* pooled_empty_flag, const int32_t* status, const int32_t* frame_ids,
+                              const double* cfg5, int aug_methods, uint32_t seed, float* out_rois, float* out_gt_of_rois,
+                              float* gt_boxes3d_ct, int32_t* cls_label, int32_t* reg_valid_mask, prcnn_stream_t stream);
 
 /* ======================================================================================================
  * RPN training loss and its gradient in one device pass (csrc/rpn_loss.hip, arithmetic: csrc/rpn_loss_math.h) --

@@ -344,6 +344,131 @@ class GTDatabase:
                                  extra_num, rand_num, apply_prob, self.hard_ratio, scope, try_times, max_accept, seed)
 
 
+def filtrate_objects(labels, classes=("Car",), include_similar_type=True, area_scope=PC_AREA_SCOPE):
+    """KittiRCNNDataset.filtrate_objects in TRAIN mode (lib/datasets/kitti_rcnn_dataset.py:152-173) on read_label_lines' arrays:
+    keep the classes (with INCLUDE_SIMILAR_TYPE: Van with Car, Person_sitting with Pedestrian) whose float32 centre, widened to
+    double, lies inside PC_AREA_SCOPE, bounds included (area_scope None: PC_REDUCE_BY_RANGE off) -> the kept rows' indices, in file order"""
+    white = list(classes)
+    if include_similar_type:
+        white += (["Van"] if "Car" in classes else []) + (["Person_sitting"] if "Pedestrian" in classes else [])
+    keep = np.isin(labels["cls_type"], white)
+    if area_scope is not None:
+        c = labels["boxes3d"][:, 0:3].astype(np.float64)      # check_pc_range compares float32 scalars with Python floats: in double
+        for k, (lo, hi) in enumerate(area_scope):
+            keep &= (lo <= c[:, k]) & (c[:, k] <= hi)
+    return np.nonzero(keep)[0]
+
+
+def load_rcnn_offline_frame(feature_dir, roi_dir, label_lines, sample_id, classes=("Car",), include_similar_type=True,
+                            area_scope=PC_AREA_SCOPE):
+    """The file side of KittiRCNNDataset.get_rcnn_training_sample_batch (kitti_rcnn_dataset.py:876-888) for one frame of
+    `--train_mode rcnn_offline`: the five RPN dumps of kitti_output.save_rpn_features from feature_dir, the proposals
+    roi_dir/%06d.txt parsed as the reference's label parser does (get_objects_from_label + objs_to_boxes3d: every field a float32 of
+    the parsed double), and the frame's label lines through filtrate_objects.
+    -> dict sample_id, rpn_xyz (N,3), rpn_features (N,C), rpn_intensity (N), seg_mask (N), roi_boxes3d (M,7), roi_scores (M) f32,
+    gt_boxes3d (G,7) -- host arrays; ops.rcnn_offline_sample takes the boxes of a batch padded to (B,M,7) / (B,G,7) with their counts"""
+    from . import kitti_output
+    xyz, features, intensity, seg = kitti_output.get_rpn_features(feature_dir, sample_id)
+    with open(os.path.join(roi_dir, "%06d.txt" % int(sample_id))) as fh:
+        rois = read_label_lines(fh.readlines())
+    labels = read_label_lines(label_lines)
+    return {"sample_id": int(sample_id), "rpn_xyz": xyz, "rpn_features": features, "rpn_intensity": intensity, "seg_mask": seg,
+            "roi_boxes3d": rois["boxes3d"], "roi_scores": rois["score"].astype(np.float32),
+            "gt_boxes3d": labels["boxes3d"][filtrate_objects(labels, classes, include_similar_type, area_scope)]}
+
+
+class RCNNOfflinePreparer:
+    """KittiRCNNDataset.get_rcnn_training_sample_batch (kitti_rcnn_dataset.py:876-1022) for a batch of `--train_mode rcnn_offline`
+    frames with RCNN.ROI_SAMPLE_JIT False: files in (load_rcnn_offline_frame), device batch out, nothing returns to the host
+    between the sampler and the loss.  pack() pads and pins the frames; the call uploads them and runs ops.rcnn_offline_sample,
+    prcnn_roipool3d on the sampled RoIs enlarged by POOL_EXTRA_WIDTH and ops.rcnn_offline_finish.  cfg: the RCNN section
+    (pointrcnn_amd.rcnn.RCNNConfig) plus AUG_DATA / AUG_ROT_RANGE; AUG_METHOD_LIST / AUG_METHOD_PROB default to default.yaml's."""
+
+    def __init__(self, cfg=None, device="cuda", aug_method_list=("rotation", "scaling", "flip"), aug_method_prob=(1.0, 1.0, 0.5)):
+        if cfg is None:
+            from .rcnn import RCNNConfig as cfg
+        if cfg.REG_AUG_METHOD not in ("multiple", "single"):
+            raise ValueError("RCNNOfflinePreparer: REG_AUG_METHOD %r is not supported ('multiple' or 'single')" % (cfg.REG_AUG_METHOD,))
+        self.cfg, self.device = cfg, torch.device(device)
+        self.aug_methods = tuple(getattr(cfg, "AUG_METHOD_LIST", aug_method_list)) if cfg.AUG_DATA else ()
+        self.flip_prob = float(getattr(cfg, "AUG_METHOD_PROB", aug_method_prob)[2])
+
+    def pack(self, frames, pin=True):
+        """frames: load_rcnn_offline_frame's dicts, all with the same point count (the RPN's 16384) -> host batch: rpn_xyz (B,N,3),
+        rpn_features (B,N,C), rpn_intensity, seg_mask, pts_depth (B,N; norm / 70 - 0.5 of the unaugmented point), roi_boxes3d (B,M,7) + num_roi, roi_scores (B,M), gt_boxes3d (B,G,7) +
+        num_gt, frame_ids (B) = the sample ids, which key the random table"""
+        if len({f["rpn_xyz"].shape[0] for f in frames}) != 1:
+            raise ValueError("RCNNOfflinePreparer.pack: every frame must hold the same number of points")
+        B = len(frames)
+        M, G = max(max(len(f["roi_boxes3d"]) for f in frames), 1), max(max(len(f["gt_boxes3d"]) for f in frames), 1)
+        roi, gt, sc = np.zeros((B, M, 7), np.float32), np.zeros((B, G, 7), np.float32), np.zeros((B, M), np.float32)
+        for b, f in enumerate(frames):
+            roi[b, :len(f["roi_boxes3d"])], gt[b, :len(f["gt_boxes3d"])] = f["roi_boxes3d"], f["gt_boxes3d"]
+            sc[b, :len(f["roi_boxes3d"])] = f["roi_scores"]
+        stack = lambda k: np.stack([np.ascontiguousarray(f[k], np.float32) for f in frames])      # noqa: E731
+        out = {"rpn_xyz": stack("rpn_xyz"), "rpn_features": stack("rpn_features"), "rpn_intensity": stack("rpn_intensity"),
+               "seg_mask": stack("seg_mask"), "roi_boxes3d": roi,
+               # :966 / :838-839 in numpy's own float32 arithmetic, on the host where the reference forms it: the unaugmented point's depth
+               "pts_depth": np.stack([(np.linalg.norm(f["rpn_xyz"].astype(np.float32), ord=2, axis=1) / 70.0 - 0.5).astype(np.float32)
+                                      for f in frames]), "roi_scores": sc, "gt_boxes3d": gt,
+               "num_roi": np.array([len(f["roi_boxes3d"]) for f in frames], np.int32),
+               "num_gt": np.array([len(f["gt_boxes3d"]) for f in frames], np.int32),
+               "frame_ids": np.array([f["sample_id"] for f in frames], np.int32)}
+        out = {k: torch.from_numpy(v) for k, v in out.items()}
+        return {k: v.pin_memory() for k, v in out.items()} if pin else out
+
+    def _upload(self, packed):
+        return {k: v.to(self.device, non_blocking=True) for k, v in packed.items()}
+
+    def _point_features(self, d):
+        cfg = self.cfg
+        extras = ([d["rpn_intensity"].unsqueeze(2)] if cfg.USE_INTENSITY else []) + [d["seg_mask"].unsqueeze(2)]
+        if cfg.USE_DEPTH:
+            extras.append(d["pts_depth"].unsqueeze(2))
+        return len(extras), torch.cat(extras + [d["rpn_features"]], dim=2)
+
+    def __call__(self, packed, seed=0):
+        """-> the reference's sample_info on the device, flattened over (B, R): pts_input (B*R,S,3+extras), pts_features (B*R,S,C),
+        cls_label, reg_valid_mask (B*R) i32, gt_boxes3d_ct, roi_boxes3d, gt_boxes3d (B*R,7), roi_size (B*R,3), plus gt_iou (B*R) the
+        noise loop's IoU, src (B*R) i32, status (B) i32 (ops.rcnn_offline_sample: 1 / 2 = a frame the reference raises on, cleared)"""
+        from . import rcnn
+        cfg, d = self.cfg, self._upload(packed)
+        s = ops.rcnn_offline_sample(d["roi_boxes3d"], d["num_roi"], d["gt_boxes3d"], d["num_gt"], cfg.ROI_PER_IMAGE,
+                                    (cfg.REG_FG_THRESH, cfg.CLS_FG_THRESH, cfg.CLS_BG_THRESH, cfg.CLS_BG_THRESH_LO), cfg.FG_RATIO,
+                                    cfg.HARD_BG_RATIO, aug_method=cfg.REG_AUG_METHOD, seed=seed, frame_ids=d["frame_ids"])
+        E, feat = self._point_features(d)
+        pooled, empty = rcnn.roipool3d_gpu(d["rpn_xyz"], feat, s["rois"], cfg.POOL_EXTRA_WIDTH, cfg.NUM_POINTS)
+        f = ops.rcnn_offline_finish(pooled, s, empty, (cfg.REG_FG_THRESH, cfg.CLS_FG_THRESH, cfg.CLS_BG_THRESH), self.aug_methods,
+                                    self.flip_prob, cfg.AUG_ROT_RANGE, seed, d["frame_ids"])
+        rows = pooled.view((-1,) + tuple(pooled.shape[2:]))
+        return {"pts_input": rows[:, :, :3 + E], "pts_features": rows[:, :, 3 + E:], "cls_label": f["cls_label"].view(-1),
+                "reg_valid_mask": f["reg_valid_mask"].view(-1), "gt_boxes3d_ct": f["gt_boxes3d_ct"].view(-1, 7),
+                "roi_boxes3d": f["roi_boxes3d"].view(-1, 7), "roi_size": f["roi_boxes3d"].view(-1, 7)[:, 3:6],
+                "gt_boxes3d": f["gt_boxes3d"].view(-1, 7), "gt_iou": s["roi_iou"].view(-1), "src": s["src"].view(-1),
+                "status": s["status"], "pooled_empty_flag": empty.view(-1)}
+
+    def eval_batch(self, packed):
+        """The non-JIT branch of get_proposal_from_file (:832-852): every RoI of every frame pooled and moved into its canonical frame
+        by ops.roipool3d_canonical.  -> pts_input (B*M,S,3+extras), pts_features (B*M,S,C), roi_boxes3d (B*M,7), roi_scores (B*M),
+        roi_size (B*M,3), pooled_empty_flag (B*M), num_roi (B): rows past a frame's num_roi belong to zero boxes"""
+        from . import rcnn
+        cfg, d = self.cfg, self._upload(packed)
+        extras = ([d["rpn_intensity"]] if cfg.USE_INTENSITY else []) + [d["seg_mask"]]
+        if cfg.USE_DEPTH:
+            extras.append(d["pts_depth"])
+        if len(extras) > 2:
+            raise NotImplementedError("RCNNOfflinePreparer.eval_batch: USE_INTENSITY with USE_DEPTH needs three scalar channels; "
+                                      "ops.roipool3d_canonical takes two")
+        rois = d["roi_boxes3d"].contiguous()
+        B, M = rois.shape[:2]
+        pool_boxes = rcnn.enlarge_box3d(rois.view(-1, 7), cfg.POOL_EXTRA_WIDTH).view(B, M, 7)
+        pts, feat, empty = ops.roipool3d_canonical(d["rpn_xyz"].contiguous(), pool_boxes, rois, extras, d["rpn_features"].contiguous(),
+                                                   cfg.NUM_POINTS)
+        return {"pts_input": pts, "pts_features": feat.view(B * M, cfg.NUM_POINTS, -1), "roi_boxes3d": rois.view(-1, 7),
+                "roi_scores": d["roi_scores"].view(-1), "roi_size": rois.view(-1, 7)[:, 3:6], "pooled_empty_flag": empty.view(-1),
+                "num_roi": d["num_roi"]}
+
+
 def road_plane_from_lines(lines):
     """kitti_dataset.get_road_plane (lib/datasets/kitti_dataset.py:55-68) on the plane file's lines: normal facing up, unit length"""
     plane = np.asarray([float(v) for v in lines[3].split()])

@@ -58,6 +58,7 @@ def emit(name, shape, sec, **kw):
     if "flops" in kw:
         tf = kw["flops"] / sec / 1e12
         d.update(bound="mfma", achieved_TFLOPs=round(tf, 2), frac_of_peak=round(tf / MFMA_F32_PEAK_TF, 3))
+    d.update(kw.get("parts", {}))             # a composed row's own breakdown
     print(json.dumps(d), flush=True)
 
 
@@ -162,6 +163,55 @@ def rpn_loss_rows(dev, B=16, N=16384, rounds=5):
         if fused:
             d.update(traffic_floor_MB=round(floor / 1e6, 1), floor_GBps_at_median=round(floor / t[len(t) // 2] / 1e9, 1))
         print(json.dumps(d), flush=True)
+
+
+def rcnn_offline_rows(dev, B=4, M=300, G=12, R=64, N=16384, C=128, S=512):
+    """`rcnn_offline_batch`: kitti_input.RCNNOfflinePreparer's device side (`--train_mode rcnn_offline`, ROI_SAMPLE_JIT False) at the
+    workload's shape -- RoI sampling (IoU matrix + lists + picks + noise loop), pooling of the sampled RoIs (prcnn_roipool3d, mask +
+    depth + C feature channels) and the finish pass (per-RoI rotate / scale / flip, canonical transform, labels) -- the whole call and
+    the three parts.  Scene: every label has 8 RoIs near it (foreground), 8 shifted by half its length (hard background), the rest
+    scattered (easy background).  Also the sampler alone at its RoI cap (M = 4096), where one lane builds the candidate lists."""
+    import numpy as np
+    from . import kitti_input, rcnn
+    rng = np.random.default_rng(12)
+
+    def scene(M):
+        gt = (rng.random((B, G, 7)) * [60., .3, 50., .3, .3, .8, 6.28] + [-30., 1.4, 8., 1.4, 1.5, 3.5, -3.14]).astype(np.float32)
+        roi = (rng.random((B, M, 7)) * [70., .4, 60., .3, .3, 1., 6.28] + [-35., 1.3, 4., 1.4, 1.5, 3.4, -3.14]).astype(np.float32)
+        for j in range(G):
+            near = gt[:, j:j + 1] + rng.normal(0, 1, (B, 8, 7)) * [.1, .03, .1, .03, .03, .06, .03]
+            hard = gt[:, j:j + 1] + rng.normal(0, 1, (B, 8, 7)) * [.1, .03, .1, .03, .03, .06, .03]
+            hard[..., 0] += np.cos(gt[:, j:j + 1, 6]) * 0.5 * gt[:, j:j + 1, 5]
+            hard[..., 2] -= np.sin(gt[:, j:j + 1, 6]) * 0.5 * gt[:, j:j + 1, 5]
+            roi[:, 16 * j:16 * j + 8], roi[:, 16 * j + 8:16 * j + 16] = near, hard
+        return roi, gt
+    roi, gt = scene(M)
+    ctr = gt[np.arange(B)[:, None], rng.integers(0, G, (B, N))][..., :3]
+    xyz = (ctr + rng.normal(0, 1, (B, N, 3)) * [1.8, .6, 1.8] - [0, .8, 0]).astype(np.float32)
+    frames = [{"sample_id": b, "rpn_xyz": xyz[b], "rpn_features": rng.normal(0, 1, (N, C)).astype(np.float32),
+               "rpn_intensity": rng.random(N).astype(np.float32), "seg_mask": (rng.random(N) > 0.5).astype(np.float32),
+               "roi_boxes3d": roi[b], "roi_scores": np.zeros(M, np.float32), "gt_boxes3d": gt[b]} for b in range(B)]
+    cfg = type("Cfg", (rcnn.RCNNConfig,), dict(ROI_SAMPLE_JIT=False, ROI_PER_IMAGE=R, NUM_POINTS=S))
+    prep = kitti_input.RCNNOfflinePreparer(cfg, dev)
+    d = prep._upload(prep.pack(frames, pin=False))
+    out = prep(d, seed=3)
+    assert not out["status"].any() and (out["cls_label"] == 1).any() and (out["cls_label"] == 0).any()
+    thr = (cfg.REG_FG_THRESH, cfg.CLS_FG_THRESH, cfg.CLS_BG_THRESH)
+    sample = lambda: ops.rcnn_offline_sample(d["roi_boxes3d"], d["num_roi"], d["gt_boxes3d"], d["num_gt"], R, seed=3, frame_ids=d["frame_ids"])   # noqa: E731
+    s = sample()
+    _, feat = prep._point_features(d)
+    pooled, empty = rcnn.roipool3d_gpu(d["rpn_xyz"], feat, s["rois"], cfg.POOL_EXTRA_WIDTH, S)
+    t_all = timeit(lambda: prep(d, seed=3))
+    t_s = timeit(sample)
+    t_p = timeit(lambda: rcnn.roipool3d_gpu(d["rpn_xyz"], feat, s["rois"], cfg.POOL_EXTRA_WIDTH, S))
+    t_f = timeit(lambda: ops.rcnn_offline_finish(pooled, s, empty, thr, prep.aug_methods, prep.flip_prob, cfg.AUG_ROT_RANGE, 3, d["frame_ids"]))
+    emit("rcnn_offline_batch", "bs%d M%d G%d R%d N%d S%d C%d (upload excluded; includes the (B,N,%d) feature concat)" % (B, M, G, R, N, S, C, 2 + C),
+         t_all, bytes=B * R * S * (5 + C) * 4, parts={"sample_us": round(t_s * 1e6, 1), "pool_us": round(t_p * 1e6, 1), "finish_us": round(t_f * 1e6, 1)})
+    big, bgt = scene(4096)
+    T = lambda a, dt=None: torch.from_numpy(np.ascontiguousarray(a, dt)).to(dev)          # noqa: E731
+    br, bg, bn, bm = T(big), T(bgt), T(np.full(B, 4096), np.int32), T(np.full(B, G), np.int32)
+    emit("rcnn_offline_sample", "bs%d M4096 G%d R%d (the RoI cap)" % (B, G, R), timeit(lambda: ops.rcnn_offline_sample(br, bn, bg, bm, R, seed=3)),
+         pairs=B * 4096 * G)
 
 
 def rcnn_loss_rows(dev, R=256, rounds=5):
@@ -296,6 +346,9 @@ def main():
     planes = torch.tensor([[0.0, -1.0, 0.0, 1.65]] * Bs, dtype=torch.float64, device=dev)
     emit("gt_aug_sample", "B%d G12 D%d (default.yaml: 10-14 extra, 100 tries)" % (Bs, D),
          timeit(lambda: gdb.sample(sg, ngt, planes, seed=5)))
+
+    # ---- the RCNN offline training batch: sample + pool + finish (csrc/rcnn_offline.hip, kitti_input.RCNNOfflinePreparer)
+    rcnn_offline_rows(dev)
 
     # ---- the RPN training batch from raw scans (kitti_input.TrainScenePreparer) next to the separate passes
     train_scene_rows(dev, B=4 if args.quick else 16)

@@ -1021,6 +1021,77 @@ def proposal_target_sample(roi_boxes3d, gt_boxes3d, roi_per_image=64, thresholds
     return o
 
 
+def rcnn_offline_sample(roi_boxes3d, num_roi, gt_boxes3d, num_gt, roi_per_image=64, thresholds=(0.55, 0.6, 0.45, 0.05), fg_ratio=0.5,
+                        hard_bg_ratio=0.8, aug_times=10, aug_method="multiple", seed=0, frame_ids=None):
+    """The sampling part of KittiRCNNDataset.get_rcnn_training_sample_batch (lib/datasets/kitti_rcnn_dataset.py:890-957) for a batch
+    (`--train_mode rcnn_offline`, RCNN.ROI_SAMPLE_JIT False).  roi_boxes3d (B,M,7) with num_roi (B) i32, gt_boxes3d (B,G,7) with
+    num_gt (B) i32; thresholds = (REG_FG, CLS_FG, CLS_BG, CLS_BG_LO); frame_ids (B) i32 = the id of every frame in the random table
+    (default: its position in the batch).
+    -> dict: iou3d (B,M,G) corner IoU, rois, gt_of_rois (B,R,7), roi_iou (B,R) the noise loop's last IoU, src (B,R) i32,
+    max_overlaps (B,M), gt_assignment (B,M) i32, counts (B,4), status (B): 0 ok, 1 the reference raises, 2 no label
+    (include/prcnn_pointops.h)"""
+    _chk(roi_boxes3d, "roi_boxes3d", ndim=3); _chk(gt_boxes3d, "gt_boxes3d", ndim=3)
+    _chk(num_roi, "num_roi", _INT, 1); _chk(num_gt, "num_gt", _INT, 1)
+    B, M, _ = roi_boxes3d.shape
+    G = gt_boxes3d.shape[1]
+    if roi_boxes3d.shape[2] != 7 or gt_boxes3d.shape[0] != B or gt_boxes3d.shape[2] != 7 or num_roi.shape[0] != B or num_gt.shape[0] != B:
+        raise ValueError("rcnn_offline_sample: roi_boxes3d (B, M, 7), gt_boxes3d (B, G, 7), num_roi (B,), num_gt (B,) disagree")
+    if aug_method not in ("multiple", "single"):
+        raise ValueError("rcnn_offline_sample: REG_AUG_METHOD %r is not supported ('multiple' or 'single')" % (aug_method,))
+    dev = roi_boxes3d.device
+    if frame_ids is not None:
+        _chk(frame_ids, "frame_ids", _INT, 1)
+        if frame_ids.shape[0] != B:
+            raise ValueError("rcnn_offline_sample: frame_ids must be (%d,)" % B)
+    for name, t in (("num_roi", num_roi), ("gt_boxes3d", gt_boxes3d), ("num_gt", num_gt), ("frame_ids", frame_ids)):
+        if t is not None and t.device != dev:
+            raise RuntimeError("rcnn_offline_sample: %s is on %s, roi_boxes3d on %s" % (name, t.device, dev))
+    R = int(roi_per_image)
+    o = {"iou3d": torch.empty((B, M, G), dtype=_F32, device=dev),
+         "rois": torch.empty((B, R, 7), dtype=_F32, device=dev), "gt_of_rois": torch.empty((B, R, 7), dtype=_F32, device=dev),
+         "roi_iou": torch.empty((B, R), dtype=_F32, device=dev), "src": torch.empty((B, R), dtype=_INT, device=dev),
+         "max_overlaps": torch.empty((B, M), dtype=_F32, device=dev), "gt_assignment": torch.empty((B, M), dtype=_INT, device=dev),
+         "counts": torch.empty((B, 4), dtype=_INT, device=dev), "status": torch.empty((B,), dtype=_INT, device=dev)}
+    cfg6 = (ctypes.c_double * 6)(*[float(v) for v in tuple(thresholds) + (fg_ratio, hard_bg_ratio)])
+    _cabi.check(_cabi.lib().prcnn_rcnn_offline_sample(
+        _p(roi_boxes3d), _p(num_roi), _p(gt_boxes3d), _p(num_gt), _p(frame_ids), B, M, G, R, ctypes.cast(cfg6, ctypes.c_void_p),
+        int(aug_times), {"multiple": 0, "single": 1}[aug_method], int(seed) & 0xFFFFFFFF, _p(o["iou3d"]), _p(o["rois"]), _p(o["gt_of_rois"]),
+        _p(o["roi_iou"]), _p(o["src"]), _p(o["max_overlaps"]), _p(o["gt_assignment"]), _p(o["counts"]), _p(o["status"]), _stream()),
+        "prcnn_rcnn_offline_sample")
+    return o
+
+
+AUG_METHOD_BITS = {"rotation": 1, "scaling": 2, "flip": 4}
+
+
+def rcnn_offline_finish(pooled, sample, pooled_empty_flag, thresholds=(0.55, 0.6, 0.45), aug_methods=("rotation", "scaling", "flip"),
+                        flip_prob=0.5, rot_range=18, seed=0, frame_ids=None):
+    """Everything of get_rcnn_training_sample_batch after pooling (kitti_rcnn_dataset.py:976-1010), one launch.  pooled (B,R,S,W) or
+    (B*R,S,W) contiguous, xyz in its first three columns, REWRITTEN IN PLACE (per-RoI rotate / scale / flip, canonical transform);
+    sample: rcnn_offline_sample's dict; pooled_empty_flag (B,R) i32; thresholds = (REG_FG, CLS_FG, CLS_BG); aug_methods: the entries of
+    AUG_METHOD_LIST, () when AUG_DATA is off.
+    -> dict roi_boxes3d, gt_boxes3d (B,R,7) the augmented boxes, gt_boxes3d_ct (B,R,7), cls_label, reg_valid_mask (B,R) i32"""
+    _chk(pooled, "pooled"); _chk(pooled_empty_flag, "pooled_empty_flag", _INT, 2)
+    rois, gts, iou, status = sample["rois"], sample["gt_of_rois"], sample["roi_iou"], sample["status"]
+    B, R, _ = rois.shape
+    if not pooled.is_contiguous() or pooled.dim() not in (3, 4) or pooled.numel() % (B * R) or pooled.shape[-1] < 3 or \
+            pooled.numel() // (B * R) != pooled.shape[-2] * pooled.shape[-1] or tuple(pooled_empty_flag.shape) != (B, R):
+        raise ValueError("rcnn_offline_finish: pooled must be contiguous (B, R, S, W >= 3) rows for the sample's (%d, %d) slots" % (B, R))
+    S, W = pooled.shape[-2], pooled.shape[-1]
+    if frame_ids is not None:
+        _chk(frame_ids, "frame_ids", _INT, 1)
+    dev = pooled.device
+    o = {"roi_boxes3d": torch.empty((B, R, 7), dtype=_F32, device=dev), "gt_boxes3d": torch.empty((B, R, 7), dtype=_F32, device=dev),
+         "gt_boxes3d_ct": torch.empty((B, R, 7), dtype=_F32, device=dev), "cls_label": torch.empty((B, R), dtype=_INT, device=dev),
+         "reg_valid_mask": torch.empty((B, R), dtype=_INT, device=dev)}
+    cfg5 = (ctypes.c_double * 5)(*[float(v) for v in tuple(thresholds) + (flip_prob, rot_range)])
+    _cabi.check(_cabi.lib().prcnn_rcnn_offline_finish(
+        _p(pooled), W, B, R, S, _p(rois), _p(gts), _p(iou), _p(pooled_empty_flag), _p(status), _p(frame_ids),
+        ctypes.cast(cfg5, ctypes.c_void_p), sum(AUG_METHOD_BITS[m] for m in set(aug_methods)), int(seed) & 0xFFFFFFFF, _p(o["roi_boxes3d"]),
+        _p(o["gt_boxes3d"]), _p(o["gt_boxes3d_ct"]), _p(o["cls_label"]), _p(o["reg_valid_mask"]), _stream()), "prcnn_rcnn_offline_finish")
+    return o
+
+
 def nms_sorted(boxes_sorted, thresh, rotated=True, max_keep=0):
     """Greedy NMS over boxes already sorted by descending score, fully on device.
     -> keep (N) int64 (first num entries valid), num (1) int32.  No host sync.

@@ -224,9 +224,35 @@ class RCNNNet(nn.Module):
         rcnn_reg = pt_utils.fused_sequential(self.reg_layer, l_features[-1]).transpose(1, 2).contiguous().squeeze(1)
         return {"rcnn_cls": rcnn_cls, "rcnn_reg": rcnn_reg, "pooled_empty_flag": empty}
 
+    def _offline_input(self, input_data):
+        """rcnn_net.py:155-163, the ROI_SAMPLE_JIT False entry: the stage's rows come ready from the dataset side
+        (KittiRCNNDataset.get_rcnn_training_sample_batch / get_proposal_from_file).  pts_features, when given, is appended to
+        pts_input as train_functions.py:31-33 does before the model is called.  The reference's collate_batch leaves a frame axis in
+        front of the RoI axis: (B, R, S, c) and (B * R, S, c) are both taken and flattened, and so are the targets."""
+        pts_input = input_data["pts_input"]
+        if "pts_features" in input_data:
+            pts_input = torch.cat((pts_input, input_data["pts_features"]), dim=-1)
+        if pts_input.dim() not in (3, 4):
+            raise ValueError("RCNNNet: pts_input must be (R, S, c) or (B, R, S, c), got %s" % (tuple(pts_input.shape),))
+        pts_input = pts_input.reshape((-1,) + tuple(pts_input.shape[-2:]))
+        rows = pts_input.shape[0]
+        target_dict = {"pts_input": pts_input, "roi_boxes3d": input_data["roi_boxes3d"].reshape(-1, 7)}
+        if self.training:
+            target_dict["cls_label"] = input_data["cls_label"].reshape(-1)
+            target_dict["reg_valid_mask"] = input_data["reg_valid_mask"].reshape(-1)
+            target_dict["gt_of_rois"] = input_data["gt_boxes3d_ct"].reshape(-1, 7)
+        for k, v in target_dict.items():
+            if v.shape[0] != rows:
+                raise ValueError("RCNNNet: %s has %d rows, pts_input %d" % (k, v.shape[0], rows))
+        return pts_input, target_dict
+
     def forward(self, input_data):
         target_dict = None
-        if self.training and self.cfg.ROI_SAMPLE_JIT:
+        offline = not self.cfg.ROI_SAMPLE_JIT
+        if offline:
+            pts_input, target_dict = self._offline_input(input_data)
+            empty = None
+        elif self.training:
             # rcnn_net.py:120-126: RoI sampling, noise augmentation, pooling, canonical transform, labels (device sampler:
             # proposal_target_layer.py) -- no gradient; the network below trains on its (B * 64, 512, 3 + C') rows
             with torch.no_grad():
@@ -251,6 +277,11 @@ class RCNNNet(nn.Module):
             l_features.append(li_features)
         rcnn_cls = pt_utils.fused_sequential(self.cls_layer, l_features[-1]).transpose(1, 2).contiguous().squeeze(1)
         rcnn_reg = pt_utils.fused_sequential(self.reg_layer, l_features[-1]).transpose(1, 2).contiguous().squeeze(1)
+        if offline:                                                              # rcnn_net.py:186-190
+            ret = {"rcnn_cls": rcnn_cls, "rcnn_reg": rcnn_reg}
+            if self.training:
+                ret.update(target_dict)
+            return ret
         ret = {"rcnn_cls": rcnn_cls, "rcnn_reg": rcnn_reg, "pooled_empty_flag": empty, "pts_input": pts_input}
         if target_dict is not None:
             ret.update(target_dict)                                              # rcnn_net.py:186-188
