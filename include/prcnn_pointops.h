@@ -58,6 +58,8 @@ typedef void* prcnn_stream_t; /* hipStream_t */
 #define PRCNN_EUNSUPPORTED (-3) /* valid request this build has no kernel for */
 
 int prcnn_abi_version(void);   /* 12: + prcnn_switches_reload, prcnn_switch_get (the PRCNN_* kernel switches are read once, through one table);
+                                 * still 12 (additive): + prcnn_eval_gt_max_iou, prcnn_eval_stats_accumulate, prcnn_eval_stats_workspace_bytes
+                                 * (recall, segmentation IoU and RCNN accuracy of the evaluation loops counted on the device);
                                  * still 12 (additive): + prcnn_rcnn_offline_sample, prcnn_rcnn_offline_finish (RCNN offline training batches);
                                  * still 12 (additive): + prcnn_fps_nested (a nested FPS level answered from the parent's sample order);
                                  * still 12 (additive, no caller breaks): + prcnn_gt_database_workspace_bytes, prcnn_gt_database_count,
@@ -902,6 +904,44 @@ int prcnn_rcnn_loss_backward(const float* rcnn_cls, int64_t ld_cls, const float*
                              int label_is_i64, const void* reg_valid_mask, int mask_is_i64, const float* roi_boxes3d,
                              const float* gt_of_rois, int64_t npts, int C, const prcnn_rcnn_loss_cfg_t* cfg, const int32_t* counts,
                              const float* norm, const float* grad_out, float* dcls, float* dreg, prcnn_stream_t stream);
+
+/* ======================================================================================================
+ * Evaluation statistics on the device (csrc/eval_stats.hip, per-item arithmetic: csrc/eval_stats_math.h) -- what the three loops of
+ * tools/eval_rcnn.py report next to the AP: eval_one_epoch_rpn (:171-202), eval_one_epoch_rcnn (:336-364), eval_one_epoch_joint
+ * (:539-573).  Two launches per batch, nothing is read on the host, both capturable in a hipGraph as a plain chain.
+ * prcnn_eval_gt_max_iou: `iou3d_utils.boxes_iou3d_gpu(boxes[k], gt[k]).max(dim=0)` (:190-191, :339-349, :551-563) for every frame of S box
+ * sets in one launch:
+ *   boxes0, boxes1 (B, M, 7): S = 1 reads boxes0 (the RoIs), S = 2 also boxes1 (the decoded boxes); M >= 1;
+ *   gt_boxes3d (B, G, gt_cols >= 7), 1 <= G <= 128, columns 0..6 [x y z h w l ry]; trailing rows whose float32 sum over all gt_cols
+ *   columns, added in column order, is 0 are dropped, as prcnn_proposal_target_sample drops them; trim_mode 0 (:541-548, joint / rcnn):
+ *   nothing may remain; trim_mode 1 (:183-186, rpn): the loop stops at k > 0, row 0 always stays -- an all-zero row 0 is a ground-truth
+ *   box that is counted and never recalled;
+ *   -> gt_max (S, B, G): the column maximum of the IoU matrix (the arithmetic of prcnn_boxes_iou3d bit for bit, every pair through the
+ *   full clip), NaN when any IoU of the column is NaN (torch.max), -1 for rows >= num_gt[b]; num_gt (B) the live rows.
+ * prcnn_eval_stats_accumulate: adds one batch into the caller's state -- PRCNN_EVAL_STATS_STATE_BYTES device bytes, 8-byte aligned:
+ * int64 counters[16] then double sums[4]; zeroed by the caller to reset.  One workgroup in stream order is the only writer, the double
+ * sums are added in the reference's order: two runs give identical bytes.
+ *   counters [0..4] ground-truth boxes recalled by set 0 at float32(0.1, 0.3, 0.5, 0.7, 0.9): gt_max > thresh in float32, as torch casts
+ *            the Python scalar (float32(0.1) itself is not recalled at 0.1; NaN never is); [5..9] the same for set 1; [10] live
+ *            ground-truth boxes; [11] detections (det_num (B) i32 or NULL, the `num` of the NMS select); [12] frames; [13] batches.
+ *   sums [0] segmentation IoU (:198-202, :568-573): seg (B, N) f32 0 / 1 and cls_label (B, N) i32 or i64, both or neither; per frame
+ *            (seg_mode 0, rpn) or per batch (seg_mode 1, joint) correct = #(seg == label and label > 0), union = #(label > 0) +
+ *            #(seg > 0) - correct, float32(correct) / max(float32(union), 1), widened to double.  seg_mode 1 adds the batch's ratio
+ *            B times: the reference computes it inside its `for k in range(batch_size)` loop.
+ *        [1], [2] RCNN classification accuracy (:355-364): pred_class (B, R) u8 0 / 1 (sigmoid(rcnn_cls) > SCORE_THRESH, formed by the
+ *            caller) and gt_iou (B, R), both or neither; per frame label = gt_iou > cls_fg, valid = gt_iou >= cls_fg or gt_iou <= cls_bg,
+ *            acc = sum((pred == label) * valid) / max(sum(valid), 1), acc_refined = #(pred == (gt_iou >= refine_thresh)) / max(R, 1).
+ *   S = 0 or G = 0: no recall part (gt_max / num_gt may be NULL).
+ * prcnn_eval_stats_workspace_bytes: bytes of gt_max (S, B, G) f32 followed by num_gt (B) i32, rounded up to 8.
+ * ====================================================================================================== */
+#define PRCNN_EVAL_STATS_STATE_BYTES 160
+size_t prcnn_eval_stats_workspace_bytes(int S, int B, int G);
+int prcnn_eval_gt_max_iou(const float* boxes0, const float* boxes1, int S, int B, int M, const float* gt_boxes3d, int G, int gt_cols,
+                          int trim_mode, float* gt_max, int32_t* num_gt, prcnn_stream_t stream);
+int prcnn_eval_stats_accumulate(const float* gt_max, const int32_t* num_gt, int S, int B, int G, const int32_t* det_num,
+                                const float* seg, const void* cls_label, int label_is_i64, int64_t N, int seg_mode,
+                                const uint8_t* pred_class, const float* gt_iou, int R, float cls_fg, float cls_bg, float refine_thresh,
+                                void* state, prcnn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -157,6 +157,9 @@ SIGNATURES = {
     "prcnn_rcnn_loss_forward": (_I, [_P, _L, _P, _L, _P, _I, _P, _I, _P, _P, _L, _I, ctypes.POINTER(RcnnLossCfg), _I, _P, _P, _P, _Z, _P]),
     "prcnn_rcnn_loss_finalize": (_I, [_L, _I, ctypes.POINTER(RcnnLossCfg), _P, _P, _P, _P, _Z, _P]),
     "prcnn_rcnn_loss_backward": (_I, [_P, _L, _P, _L, _P, _I, _P, _I, _P, _P, _L, _I, ctypes.POINTER(RcnnLossCfg), _P, _P, _P, _P, _P, _P]),
+    "prcnn_eval_stats_workspace_bytes": (_Z, [_I, _I, _I]),
+    "prcnn_eval_gt_max_iou": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
+    "prcnn_eval_stats_accumulate": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _L, _I, _P, _P, _I, _F, _F, _F, _P, _P]),
 }
 
 _lib = None

@@ -24,7 +24,7 @@
 // tests/golden/ref_proposal_target.py answers the reference's own random calls from the same table: its output must be -- and is
 // -- reproduced bit for bit by the oracle in reference arithmetic; this kernel equals the oracle in the kernels' arithmetic
 // (box trigonometry in double rounded once, division-only vertex order: DESIGN.md section 2).
-#include "iou3d_geom.h"
+#include "iou3d_pair.h"
 
 #define PT_THREADS 256
 #define PT_MAX_GT 128
@@ -41,27 +41,7 @@ __device__ __forceinline__ int pt_below(unsigned r, int n) { return (int)(((unsi
 
 struct Box3 { float v[7]; };
 
-__device__ __forceinline__ void bev_of(const float* b, float* o) {                  // kitti_utils.py:134-147
-    o[0] = sub(b[0], b[5] / 2); o[1] = sub(b[2], b[4] / 2); o[2] = add(b[0], b[5] / 2); o[3] = add(b[2], b[4] / 2); o[4] = b[6];
-}
-
-// iou3d_utils.py:20-53 for one pair; B: the ground-truth box with its RBox already built
-__device__ float iou3d_pair(const float* a, const float* b, const RBox& rb) {
-    float abev[5];
-    bev_of(a, abev);
-    RBox ra;
-    make_rbox(abev, ra);
-    const float ov = far_apart(ra, rb) ? 0.0f : box_overlap(ra, rb);
-    const float amin = sub(a[1], a[3]), bmin = sub(b[1], b[3]);
-    const float max_of_min = amin > bmin ? amin : bmin, min_of_max = a[1] < b[1] ? a[1] : b[1];
-    float h = sub(min_of_max, max_of_min);
-    if (!(h > 0.0f)) h = 0.0f;
-    const float ov3 = mul(ov, h);
-    const float va = mul(mul(a[3], a[4]), a[5]), vb = mul(mul(b[3], b[4]), b[5]);
-    float den = sub(add(va, vb), ov3);
-    if (den < 1e-7f) den = 1e-7f;
-    return ov3 / den;
-}
+// bev_of, iou3d_pair: iou3d_pair.h (shared with eval_stats.hip)
 
 struct PtParams {
     const float* roi;        // (B, M, 7)

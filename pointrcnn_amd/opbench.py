@@ -248,11 +248,73 @@ def rcnn_loss_rows(dev, R=256, rounds=5):
                           "median_us": round(t[len(t) // 2] * 1e6, 1), "min_us": round(t[0] * 1e6, 1), "max_us": round(t[-1] * 1e6, 1)}), flush=True)
 
 
+def eval_stats_rows(dev, B=32, shapes=((100, 12), (512, 24)), N=16384, rounds=5):
+    """`eval_stats`: the per-batch statistics of eval_one_epoch_joint (tools/eval_rcnn.py:539-573) at bs32 -- recall of the ground truth
+    by the RoIs and the refined boxes at five thresholds, the segmentation IoU, the detection count.  Composed route: the reference's
+    loop as it runs on this library, per frame ops.boxes_iou3d x 2, max, compares and `.item()` reads.  Device route: EvalStats.update
+    (two launches, no host read; the window ends on one synchronisation).  Alternated in one process; per route the median, minimum and
+    maximum over `rounds` windows of 20 calls."""
+    from .eval_stats import THRESH_LIST, EvalStats
+    gq = torch.Generator().manual_seed(21)
+    span, base = torch.tensor([60., .8, 60., .3, .3, 1., 6.28]), torch.tensor([-30., 1.2, 5., 1.4, 1.5, 3.4, -3.14])
+    seg = (torch.rand(B, N, generator=gq) < 0.2).float().to(dev)
+    label = (torch.rand(B, N, generator=gq) < 0.2).long().to(dev)
+    for M, G in shapes:
+        gt = torch.rand(B, G, 7, generator=gq) * span + base
+        gt[:, G - G // 4:] = 0                                    # a quarter of the rows is padding
+        near = gt[:, torch.randint(0, G - G // 4, (M,), generator=gq)] + torch.randn(B, M, 7, generator=gq) * 0.2
+        far = torch.rand(B, M, 7, generator=gq) * span + base
+        rois = torch.where(torch.rand(B, M, 1, generator=gq) < 0.5, near, far).to(dev).contiguous()
+        pred = (rois + torch.randn(B, M, 7, generator=gq).to(dev) * 0.05).contiguous()
+        gt = gt.to(dev)
+        num = torch.randint(0, 20, (B,), generator=gq, dtype=torch.int32).to(dev)
+        stats = EvalStats("joint", dev)
+
+        def composed():
+            total = [0] * 5, [0] * 5
+            total_gt = final_total = 0
+            total_rpn_iou = 0.0
+            for k in range(B):
+                cur = gt[k]
+                n = cur.shape[0] - 1
+                while n >= 0 and cur[n].sum().item() == 0:
+                    n -= 1
+                if n >= 0:
+                    cur = cur[:n + 1].contiguous()
+                    for which, boxes in enumerate((pred[k], rois[k])):
+                        gt_max_iou, _ = ops.boxes_iou3d(boxes, cur).max(dim=0)
+                        for idx, thresh in enumerate(THRESH_LIST):
+                            total[which][idx] += (gt_max_iou > thresh).sum().item()
+                    total_gt += cur.shape[0]
+                fg_mask = label > 0
+                correct = ((seg == label) & fg_mask).sum().float()
+                union = fg_mask.sum().float() + (seg > 0).sum().float() - correct
+                total_rpn_iou += (correct / torch.clamp(union, min=1.0)).item()
+                final_total += int(num[k].item())
+            return total, total_gt, total_rpn_iou, final_total
+
+        def device():
+            stats.update(rois, gt, pred_boxes3d=pred, det_num=num, seg_result=seg, rpn_cls_label=label)
+        times = {"composed": [], "device": []}
+        for _ in range(rounds):
+            times["composed"].append(timeit(composed))
+            times["device"].append(timeit(device))
+        for route in ("composed", "device"):
+            t = sorted(times[route])
+            print(json.dumps({"op": "eval_stats (%s)" % route, "shape": "B%d M%d G%d N%d joint" % (B, M, G, N),
+                              "median_us": round(t[len(t) // 2] * 1e6, 1), "min_us": round(t[0] * 1e6, 1), "max_us": round(t[-1] * 1e6, 1),
+                              "launches_per_update": 2 if route == "device" else None}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--only", default=None, help="run one row family only: eval_stats")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
+    if args.only == "eval_stats":
+        eval_stats_rows(dev)
+        return
     B = 8 if args.quick else 32
     N = 16384
     xyz = rpn.synthetic_clouds(B, N, device=dev)
@@ -360,6 +422,8 @@ def main():
     rpn_loss_rows(dev)
     # ---- the RCNN training loss and its gradient: composed torch against the device passes (csrc/rcnn_loss.hip)
     rcnn_loss_rows(dev)
+    # ---- the evaluation statistics of a batch: the reference's per-frame loop on this library against the device passes (csrc/eval_stats.hip)
+    eval_stats_rows(dev)
 
     # ---- NMS (default RPN path: normal, 6300 boxes, thr 0.8) and rotated
     c = torch.rand(6300, 2, generator=g) * torch.tensor([80.0, 70.0])

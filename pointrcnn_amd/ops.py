@@ -1440,3 +1440,79 @@ def gt_database_build(raw, offsets, max_points_per_frame, calib, boxes3d, num_bo
     _cabi.check(L.prcnn_gt_database_fill(_p(raw), _p(offsets), B, total, mp, _p(calib), _p(boxes3d), _p(num_boxes), G, _p(off), P, _p(points),
                                          _p(inten), _p(src), _p(ws), ws.numel(), _stream()), "prcnn_gt_database_fill")
     return npts, off, points, inten, src
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Evaluation statistics (csrc/eval_stats.hip)
+# ---------------------------------------------------------------------------------------------------------
+EVAL_STATS_MAX_GT = 128
+EVAL_STATS_STATE_BYTES = 160             # PRCNN_EVAL_STATS_STATE_BYTES: int64 counters[16], double sums[4]
+EVAL_TRIM = {"joint": 0, "rcnn": 0, "rpn": 1}
+
+
+def eval_stats_workspace(S, B, G, device):
+    """-> (gt_max (S,B,G) f32, num_gt (B) i32): views of one prcnn_eval_stats_workspace_bytes buffer"""
+    ws = torch.empty((int(_cabi.lib().prcnn_eval_stats_workspace_bytes(S, B, G)),), dtype=torch.uint8, device=device)
+    n = S * B * G * 4
+    return ws[:n].view(_F32).view(S, B, G), ws[n:n + B * 4].view(_INT)
+
+
+def eval_gt_max_iou(boxes, gt_boxes3d, trim_mode=0, out=None):
+    """`boxes_iou3d_gpu(boxes[k], gt[k]).max(dim=0)` for every frame of one or two box sets in one launch [tools/eval_rcnn.py:190-191,
+    :551-563].  boxes: a (B,M,7) tensor or a sequence of one or two of them (RoIs, decoded boxes); gt_boxes3d (B,G,>=7), zero rows at the
+    end; trim_mode 0 (joint / rcnn: nothing may remain) or 1 (rpn: row 0 always stays); out: an eval_stats_workspace pair.
+    -> gt_max (S,B,G), NaN where a column holds a NaN, -1 past num_gt; num_gt (B) i32"""
+    sets = [boxes] if isinstance(boxes, torch.Tensor) else list(boxes)
+    if len(sets) not in (1, 2):
+        raise ValueError("eval_gt_max_iou: one or two box sets, got %d" % len(sets))
+    for t in sets:
+        _chk(t, "boxes", ndim=3)
+    _chk(gt_boxes3d, "gt_boxes3d", ndim=3)
+    B, M = sets[0].shape[:2]
+    G, gc = gt_boxes3d.shape[1], gt_boxes3d.shape[2]
+    if any(tuple(t.shape) != (B, M, 7) for t in sets) or gt_boxes3d.shape[0] != B:
+        raise ValueError("eval_gt_max_iou: every box set must be (%d, %d, 7) and gt_boxes3d (%d, G, >= 7)" % (B, M, B))
+    gt_max, num_gt = out if out is not None else eval_stats_workspace(len(sets), B, G, gt_boxes3d.device)
+    _cabi.check(_cabi.lib().prcnn_eval_gt_max_iou(_p(sets[0]), _p(sets[1]) if len(sets) == 2 else None, len(sets), B, M, _p(gt_boxes3d), G, gc,
+                                                  int(trim_mode), _p(gt_max), _p(num_gt), _stream()), "prcnn_eval_gt_max_iou")
+    return gt_max, num_gt
+
+
+def eval_stats_accumulate(state, gt_max, num_gt, B, det_num=None, seg=None, cls_label=None, seg_mode=0, pred_class=None, gt_iou=None,
+                          cls_fg=0.6, cls_bg=0.45, refine_thresh=0.7):
+    """add one batch into `state` (EVAL_STATS_STATE_BYTES uint8 on the device; see prcnn_eval_stats_accumulate): recall counts from
+    gt_max (S,B,G) / num_gt (both None: no recall part), det_num (B) i32, the segmentation IoU from seg (B,N) f32 and cls_label (B,N)
+    i32 | i64, the RCNN classification accuracy from pred_class (B,R) u8 and gt_iou (B,R).  One launch, one workgroup."""
+    _chk(state, "state", torch.uint8, 1)
+    if state.numel() < EVAL_STATS_STATE_BYTES:
+        raise ValueError("eval_stats_accumulate: state holds %d bytes, %d are needed" % (state.numel(), EVAL_STATS_STATE_BYTES))
+    S = G = N = R = 0
+    if gt_max is not None:
+        _chk(gt_max, "gt_max", ndim=3); _chk(num_gt, "num_gt", _INT, 1)
+        S, G = gt_max.shape[0], gt_max.shape[2]
+        if gt_max.shape[1] != B or num_gt.shape[0] != B:
+            raise ValueError("eval_stats_accumulate: gt_max must be (S, %d, G) and num_gt (%d,)" % (B, B))
+    if det_num is not None and tuple(_chk(det_num, "det_num", _INT, 1).shape) != (B,):
+        raise ValueError("eval_stats_accumulate: det_num must be (%d,)" % B)
+    is64 = 0
+    if seg is not None:
+        _chk(seg, "seg", ndim=2)
+        N = seg.shape[1]
+        if seg.shape[0] != B:
+            raise ValueError("eval_stats_accumulate: seg must be (%d, N)" % B)
+    if cls_label is not None:
+        if not (cls_label.is_cuda and cls_label.dtype in (torch.int32, torch.int64) and cls_label.is_contiguous()):
+            raise RuntimeError("eval_stats_accumulate: cls_label must be a contiguous int32 or int64 CUDA(HIP) tensor")
+        is64 = int(cls_label.dtype == torch.int64)
+        if seg is not None and tuple(cls_label.shape) != tuple(seg.shape):
+            raise ValueError("eval_stats_accumulate: cls_label must be shaped as seg")
+    if pred_class is not None:
+        _chk(pred_class, "pred_class", torch.uint8, 2)
+        R = pred_class.shape[1]
+        if pred_class.shape[0] != B:
+            raise ValueError("eval_stats_accumulate: pred_class must be (%d, R)" % B)
+    if gt_iou is not None and pred_class is not None and tuple(_chk(gt_iou, "gt_iou", ndim=2).shape) != tuple(pred_class.shape):
+        raise ValueError("eval_stats_accumulate: gt_iou must be shaped as pred_class")
+    _cabi.check(_cabi.lib().prcnn_eval_stats_accumulate(_p(gt_max), _p(num_gt), S, B, G, _p(det_num), _p(seg), _p(cls_label), is64, N,
+                                                        int(seg_mode), _p(pred_class), _p(gt_iou), R, float(cls_fg), float(cls_bg),
+                                                        float(refine_thresh), _p(state), _stream()), "prcnn_eval_stats_accumulate")
