@@ -28,24 +28,11 @@ struct EsGtMaxParams {
     int32_t* num_gt;         // (B)
 };
 
-// the ground truth of a frame without its all-zero rows at the end, as pt_live_gt (proposal_target.hip) decides them; `keep` rows always
-// stay: 0 for eval_rcnn.py:541-548 (`while tmp_idx >= 0`), 1 for :183-186 (`while k > 0`: row 0 stays even when it is all zero)
-__device__ __forceinline__ int es_live_gt(const float* gt, int G, int gt_cols, int keep) {
-    int ng = G;
-    while (ng > keep) {
-        float s = 0.f;
-        for (int c = 0; c < gt_cols; c++) s = add(s, gt[(size_t)(ng - 1) * gt_cols + c]);
-        if (s != 0.f) break;
-        ng--;
-    }
-    return ng;
-}
-
 __global__ __launch_bounds__(64) void es_gt_max_kernel(const EsGtMaxParams P) {
     __shared__ float s_clip[CLIP_LDS_FLOATS * 64];
     const int j = blockIdx.x, b = blockIdx.y, s = blockIdx.z, lane = threadIdx.x;
     const float* gt = P.gt + (size_t)b * P.G * P.gt_cols;
-    const int ng = es_live_gt(gt, P.G, P.gt_cols, P.trim_mode);
+    const int ng = live_gt(gt, P.G, P.gt_cols, P.trim_mode);      // iou3d_pair.h; trim_mode = the rows that always stay
     float* out = P.gt_max + ((size_t)s * P.B + b) * P.G + j;
     if (s == 0 && j == 0 && lane == 0) P.num_gt[b] = ng;
     if (j >= ng) {                                       // every output byte is defined

@@ -17,6 +17,7 @@
 // Randomness is re-specified (the reference draws from numpy's and torch's global streams in a data-dependent order) with the
 // counter-based generator of scene.hip, one number per (purpose, frame, position):
 //   stream 10, index = RoI            fg keys: sampling without replacement = the RoIs with the smallest (key, RoI), in that order
+//                                     (the list is in RoI order, so (key, RoI) orders it as roi_sample.h's (key, place) does)
 //   stream 11, index = slot           fg sampling with replacement (frames without a background candidate)
 //   stream 12 / 13, index = position  hard / easy background picks
 //   stream 20, index = ((slot * 16 + attempt) * 16 + q): q = 8 keep-the-original decision (u < 0.2), q = 0 range row,
@@ -25,48 +26,25 @@
 // -- reproduced bit for bit by the oracle in reference arithmetic; this kernel equals the oracle in the kernels' arithmetic
 // (box trigonometry in double rounded once, division-only vertex order: DESIGN.md section 2).
 #include "iou3d_pair.h"
+#include "roi_sample.h"
 
 #define PT_THREADS 256
 #define PT_MAX_GT 128
+constexpr unsigned PT_STREAM_FG_KEY = 10, PT_STREAM_FG_REPLACE = 11, PT_STREAM_HARD = 12, PT_STREAM_EASY = 13, PT_STREAM_NOISE = 20;
 
-__host__ __device__ __forceinline__ unsigned pt_mix(unsigned x) {
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-    return x;
-}
-__host__ __device__ __forceinline__ unsigned pt_rand(unsigned seed, unsigned stream, unsigned frame, unsigned i) {
-    return pt_mix(i ^ pt_mix(frame * 0x9E3779B9U + pt_mix(seed + stream * 0x85EBCA6BU)));
-}
-__device__ __forceinline__ float pt_u01(unsigned r) { return (float)(r >> 8) * (1.0f / 16777216.0f); }
-__device__ __forceinline__ int pt_below(unsigned r, int n) { return (int)(((unsigned long long)r * (unsigned long long)n) >> 32); }
-
-struct Box3 { float v[7]; };
-
-// bev_of, iou3d_pair: iou3d_pair.h (shared with eval_stats.hip)
+// bev_of, iou3d_pair, live_gt: iou3d_pair.h (shared with eval_stats.hip); the selection of phase 2: roi_sample.h (shared with rcnn_offline.hip)
 
 struct PtParams {
     const float* roi;        // (B, M, 7)
     const float* gt;         // (B, G, gt_cols)
     int B, M, G, gt_cols, R;
-    float reg_fg, cls_fg, cls_bg, cls_bg_lo;
-    double hard_ratio;
-    int fg_per_image, aug_times, aug_method;
+    RsCfg c;
+    int aug_times, aug_method;
     unsigned seed;
     float* rois; float* gt_of_rois; float* roi_iou; int32_t* src;      // (B,R,7) (B,R,7) (B,R) (B,R)
     float* max_overlaps; int32_t* gt_assignment;                      // (B,M)
     int32_t* counts; int32_t* status;                                 // (B,4) (B)
 };
-
-// :96-99: the ground truth of a frame without its all-zero rows at the end
-__device__ __forceinline__ int pt_live_gt(const float* gt, int G, int gt_cols) {
-    int ng = G;
-    while (ng > 0) {
-        float s = 0.f;
-        for (int c = 0; c < gt_cols; c++) s = add(s, gt[(size_t)(ng - 1) * gt_cols + c]);
-        if (s != 0.f) break;
-        ng--;
-    }
-    return ng;
-}
 
 // Phase 1 on the whole chip: max IoU and its ground-truth box for every RoI (iou3d_utils.boxes_iou3d_gpu + torch.max over dim 1,
 // :100-101).  The sampler kernel below is one workgroup per frame -- its branching is per frame -- and 512 RoIs x 12 boxes of
@@ -77,9 +55,12 @@ __global__ __launch_bounds__(64) void pt_overlaps_kernel(const PtParams P) {
     const int b = blockIdx.y, lane = threadIdx.x;
     const int i = blockIdx.x * 4 + (lane >> 4), sub = lane & 15;
     const float* gt = P.gt + (size_t)b * P.G * P.gt_cols;
-    const int ng = pt_live_gt(gt, P.G, P.gt_cols);
-    if (ng == 0) return;
+    const int ng = live_gt(gt, P.G, P.gt_cols, 0);
     const bool live = i < P.M;
+    if (ng == 0) {                                      // status 2: every output byte is defined, 0 / 0 as the oracle reports it
+        if (live && sub == 0) { P.max_overlaps[(size_t)b * P.M + i] = 0.f; P.gt_assignment[(size_t)b * P.M + i] = 0; }
+        return;
+    }
     float a[7];
     for (int c = 0; c < 7; c++) a[c] = P.roi[((size_t)b * P.M + (live ? i : 0)) * 7 + c];
     float best = -INFINITY, v0 = 0.f;
@@ -111,7 +92,9 @@ __global__ __launch_bounds__(PT_THREADS) void proposal_target_kernel(const PtPar
     extern __shared__ int lds_i[];                    // fg[M], hard[M], easy[M] candidate lists, then keys[M]
     __shared__ RBox s_gt[PT_MAX_GT];
     __shared__ float s_gtraw[PT_MAX_GT][7];
-    __shared__ int s_ng, s_n[3], s_slots[2], s_hard_slots;
+    __shared__ int s_ng;
+    __shared__ RsLists s_lists;
+    __shared__ RsPlan s_plan;
     const int b = blockIdx.x, tid = threadIdx.x;
     const float* roi = P.roi + (size_t)b * P.M * 7;
     const float* gt = P.gt + (size_t)b * P.G * P.gt_cols;
@@ -123,18 +106,15 @@ __global__ __launch_bounds__(PT_THREADS) void proposal_target_kernel(const PtPar
     float* o_gt = P.gt_of_rois + (size_t)b * P.R * 7;
     float* o_iou = P.roi_iou + (size_t)b * P.R;
     int32_t* o_src = P.src + (size_t)b * P.R;
-    const float fg_thresh = fminf(P.reg_fg, P.cls_fg);
+    const float fg_thresh = P.c.fg_thresh;
 
     if (tid == 0) {                                   // :96-99: drop the all-zero rows at the end of the ground truth
-        const int ng = pt_live_gt(gt, P.G, P.gt_cols);
+        const int ng = live_gt(gt, P.G, P.gt_cols, 0);
         s_ng = ng;
         P.status[b] = ng == 0 ? 2 : 0;
         for (int q = 0; q < 4; q++) P.counts[b * 4 + q] = 0;
     }
-    for (int t = tid; t < P.R; t += PT_THREADS) {
-        o_src[t] = -1; o_iou[t] = 0.f;
-        for (int c = 0; c < 7; c++) { o_roi[(size_t)t * 7 + c] = 0.f; o_gt[(size_t)t * 7 + c] = 0.f; }
-    }
+    rs_clear(o_roi, o_gt, o_iou, o_src, P.R, tid, PT_THREADS);
     __syncthreads();
     const int ng = s_ng;
     if (ng == 0) return;
@@ -144,55 +124,34 @@ __global__ __launch_bounds__(PT_THREADS) void proposal_target_kernel(const PtPar
         bev_of(s_gtraw[j], bev);
         make_rbox(bev, s_gt[j]);
     }
-    __syncthreads();
     // phase 1 (max_overlaps / gt_assignment): pt_overlaps_kernel, launched before this one
-    for (int i = tid; i < P.M; i += PT_THREADS) keys[i] = pt_rand(P.seed, 10, (unsigned)b, (unsigned)i);
-    __syncthreads();
-    // phase 2: candidate lists in RoI order (one thread: M <= a few thousand), then the reference's four cases
+    // phase 2: candidate lists in RoI order (one thread: M <= a few thousand), then the reference's four cases (roi_sample.h)
     if (tid == 0) {
-        int nfg = 0, nhard = 0, neasy = 0;
-        for (int i = 0; i < P.M; i++) {
-            const float mo = P.max_overlaps[(size_t)b * P.M + i];
-            if (mo >= fg_thresh) fg[nfg++] = i;
-            if (mo < P.cls_bg_lo) easy[neasy++] = i;
-            if (mo < P.cls_bg && mo >= P.cls_bg_lo) hard[nhard++] = i;
-        }
-        s_n[0] = nfg; s_n[1] = nhard; s_n[2] = neasy;
-        P.counts[b * 4] = nfg; P.counts[b * 4 + 1] = nhard; P.counts[b * 4 + 2] = neasy;
-        const int nbg = nhard + neasy;
-        int fs = 0, bs = 0;
-        if (nfg > 0 && nbg > 0) { fs = min(P.fg_per_image, nfg); bs = P.R - fs; }
-        else if (nfg > 0) fs = P.R;
-        else if (nbg > 0) bs = P.R;
-        else P.status[b] = 1;
-        s_slots[0] = fs; s_slots[1] = bs;
-        int nh = 0;
-        if (nhard > 0 && neasy > 0) nh = (int)((double)bs * P.hard_ratio);
-        else if (nhard > 0) nh = bs;
-        s_hard_slots = nh;
-        P.counts[b * 4 + 3] = fs;
+        const RsLists l = rs_lists(P.max_overlaps + (size_t)b * P.M, P.M, P.c, fg, hard, easy);
+        RsPlan p = rs_plan(l, P.R, P.c.fg_per_image, P.c.hard_ratio);
+        if (p.kind == RS_FG_ONLY) p.fs = P.R;         // no background candidate: every slot is foreground, with replacement (:137-141)
+        if (p.kind == RS_NEITHER) P.status[b] = 1;
+        s_lists = l; s_plan = p;
+        P.counts[b * 4] = l.nfg; P.counts[b * 4 + 1] = l.nhard; P.counts[b * 4 + 2] = l.neasy; P.counts[b * 4 + 3] = p.fs;
     }
     __syncthreads();
-    const int nfg = s_n[0], nhard = s_n[1], neasy = s_n[2], fs = s_slots[0], bs = s_slots[1], nh = s_hard_slots;
-    if (fs + bs == 0) return;
-    if (nfg > 0 && nhard + neasy > 0) {
-        // without replacement: candidate t goes to slot rank(t) = number of candidates with a smaller (key, RoI)
-        for (int t = tid; t < nfg; t += PT_THREADS) {
-            const unsigned k = keys[fg[t]];
-            int rank = 0;
-            for (int u = 0; u < nfg; u++) {
-                const unsigned ku = keys[fg[u]];
-                rank += (ku < k || (ku == k && fg[u] < fg[t])) ? 1 : 0;
-            }
+    const RsLists l = s_lists;
+    const RsPlan p = s_plan;
+    const int fs = p.fs;
+    if (p.kind == RS_NEITHER) return;
+    if (p.kind == RS_BOTH) {
+        for (int t = tid; t < l.nfg; t += PT_THREADS) keys[t] = scene_rand(P.seed, PT_STREAM_FG_KEY, (unsigned)b, (unsigned)fg[t]);
+        __syncthreads();                              // p.kind is the workgroup's: every lane is here
+        for (int t = tid; t < l.nfg; t += PT_THREADS) {
+            const int rank = rs_rank(keys, l.nfg, t);
             if (rank < fs) o_src[rank] = fg[t];
         }
-    } else if (nfg > 0) {
-        for (int t = tid; t < P.R; t += PT_THREADS) o_src[t] = fg[pt_below(pt_rand(P.seed, 11, (unsigned)b, (unsigned)t), nfg)];
+    } else if (p.kind == RS_FG_ONLY) {
+        for (int t = tid; t < P.R; t += PT_THREADS)
+            o_src[t] = fg[rs_below(scene_rand(P.seed, PT_STREAM_FG_REPLACE, (unsigned)b, (unsigned)t), l.nfg)];
     }
-    for (int t = tid; t < bs; t += PT_THREADS) {
-        if (t < nh) o_src[fs + t] = hard[pt_below(pt_rand(P.seed, 12, (unsigned)b, (unsigned)t), nhard)];
-        else o_src[fs + t] = easy[pt_below(pt_rand(P.seed, 13, (unsigned)b, (unsigned)(t - nh)), neasy)];
-    }
+    for (int t = tid; t < p.bs; t += PT_THREADS)
+        o_src[fs + t] = rs_bg_pick(t, p, l, hard, easy, P.seed, PT_STREAM_HARD, PT_STREAM_EASY, (unsigned)b);
     __syncthreads();
     // phase 3: aug_roi_by_noise_torch
     for (int t = tid; t < P.R; t += PT_THREADS) {
@@ -207,23 +166,20 @@ __global__ __launch_bounds__(PT_THREADS) void proposal_target_kernel(const PtPar
         bool keep = true;
         while (temp_iou < fg_thresh && cnt < times) {
             const unsigned base = (unsigned)((t * 16 + cnt) * 16);
-            if (pt_u01(pt_rand(P.seed, 20, (unsigned)b, base + 8)) < 0.2f) {
+            if (scene_u01f(scene_rand(P.seed, PT_STREAM_NOISE, (unsigned)b, base + 8)) < 0.2f) {
                 for (int c = 0; c < 7; c++) aug[c] = box[c];
                 keep = true;
             } else {
                 float ps[3], hs[3], ar;
                 if (P.aug_method == 0) {                     // 'multiple' (:262-277)
-                    const double rc[5][3] = { {0.2, 0.1, 3.14159265358979323846 / 12}, {0.3, 0.15, 3.14159265358979323846 / 12},
-                                              {0.5, 0.15, 3.14159265358979323846 / 9}, {0.8, 0.15, 3.14159265358979323846 / 6},
-                                              {1.0, 0.15, 3.14159265358979323846 / 3} };
-                    const int idx = pt_below(pt_rand(P.seed, 20, (unsigned)b, base), 5);
-                    for (int c = 0; c < 3; c++) ps[c] = mul(sub(pt_u01(pt_rand(P.seed, 20, (unsigned)b, base + 1 + c)), 0.5f) / 0.5f, (float)rc[idx][0]);
-                    for (int c = 0; c < 3; c++) hs[c] = add(mul(sub(pt_u01(pt_rand(P.seed, 20, (unsigned)b, base + 4 + c)), 0.5f) / 0.5f, (float)rc[idx][1]), 1.0f);
-                    ar = mul(sub(pt_u01(pt_rand(P.seed, 20, (unsigned)b, base + 7)), 0.5f) / 0.5f, (float)rc[idx][2]);
+                    const RsNoiseRange rg = rs_noise_range(rs_below(scene_rand(P.seed, PT_STREAM_NOISE, (unsigned)b, base), 5));
+                    for (int c = 0; c < 3; c++) ps[c] = mul(sub(scene_u01f(scene_rand(P.seed, PT_STREAM_NOISE, (unsigned)b, base + 1 + c)), 0.5f) / 0.5f, (float)rg.pos);
+                    for (int c = 0; c < 3; c++) hs[c] = add(mul(sub(scene_u01f(scene_rand(P.seed, PT_STREAM_NOISE, (unsigned)b, base + 4 + c)), 0.5f) / 0.5f, (float)rg.hwl), 1.0f);
+                    ar = mul(sub(scene_u01f(scene_rand(P.seed, PT_STREAM_NOISE, (unsigned)b, base + 7)), 0.5f) / 0.5f, (float)rg.ang);
                 } else {                                     // 'single' (:254-260)
-                    for (int c = 0; c < 3; c++) ps[c] = sub(pt_u01(pt_rand(P.seed, 20, (unsigned)b, base + 1 + c)), 0.5f);
-                    for (int c = 0; c < 3; c++) hs[c] = add(sub(pt_u01(pt_rand(P.seed, 20, (unsigned)b, base + 4 + c)), 0.5f) / (float)(0.5 / 0.15), 1.0f);
-                    ar = sub(pt_u01(pt_rand(P.seed, 20, (unsigned)b, base + 7)), 0.5f) / (float)(0.5 / (3.14159265358979323846 / 12));
+                    for (int c = 0; c < 3; c++) ps[c] = sub(scene_u01f(scene_rand(P.seed, PT_STREAM_NOISE, (unsigned)b, base + 1 + c)), 0.5f);
+                    for (int c = 0; c < 3; c++) hs[c] = add(sub(scene_u01f(scene_rand(P.seed, PT_STREAM_NOISE, (unsigned)b, base + 4 + c)), 0.5f) / (float)(0.5 / 0.15), 1.0f);
+                    ar = sub(scene_u01f(scene_rand(P.seed, PT_STREAM_NOISE, (unsigned)b, base + 7)), 0.5f) / (float)(0.5 / (3.14159265358979323846 / 12));
                 }
                 for (int c = 0; c < 3; c++) { aug[c] = add(box[c], ps[c]); aug[3 + c] = mul(box[3 + c], hs[c]); }
                 aug[6] = add(box[6], ar);
@@ -251,10 +207,7 @@ PRCNN_API int prcnn_proposal_target_sample(const float* roi_boxes3d, const float
                   "prcnn_proposal_target_sample: null pointer");
     PtParams P;
     P.roi = roi_boxes3d; P.gt = gt_boxes3d; P.B = B; P.M = M; P.G = G; P.gt_cols = gt_cols; P.R = roi_per_image;
-    // thresholds meet float32 overlaps (torch casts the Python scalar to the tensor's dtype); the two ratios stay DOUBLE: the reference
-    // computes np.round(FG_RATIO * ROI_PER_IMAGE) and int(bg_rois_per_this_image * HARD_BG_RATIO) in Python doubles (0.7f * 10 -> 6, 0.7 * 10 -> 7)
-    P.reg_fg = (float)cfg6[0]; P.cls_fg = (float)cfg6[1]; P.cls_bg = (float)cfg6[2]; P.cls_bg_lo = (float)cfg6[3]; P.hard_ratio = cfg6[5];
-    P.fg_per_image = (int)nearbyint(cfg6[4] * (double)roi_per_image);                 // np.round
+    P.c = rs_cfg(cfg6, roi_per_image);
     P.aug_times = aug_times; P.aug_method = aug_method; P.seed = seed;
     P.rois = rois; P.gt_of_rois = gt_of_rois; P.roi_iou = roi_iou; P.src = src; P.max_overlaps = max_overlaps;
     P.gt_assignment = gt_assignment; P.counts = counts; P.status = status;

@@ -9,7 +9,7 @@
 //   ro_sample_kernel  one workgroup per frame:
 //     1  row maximum and its label for every RoI (one lane per RoI, numpy's first maximum); column maximum and its RoI for every
 //        label (one wave per label, lanes over the RoIs, combined to the first maximum)
-//     2  the candidate lists in RoI order: foreground (row maximum >= min(REG_FG, CLS_FG)) FOLLOWED BY the best RoI of every label
+//     2  (roi_sample.h, shared with the online sampler) the candidate lists in RoI order: foreground (row maximum >= min(REG_FG, CLS_FG)) FOLLOWED BY the best RoI of every label
 //        whose column maximum is > 0, in label order -- an RoI can stand in that list several times (:894-901); hard and easy
 //        background; the reference's cases; the picks
 //     3  one lane per output slot: the noise loop (ten attempts on a foreground slot, one on a background slot, whose IoU is
@@ -18,7 +18,8 @@
 // Differences from the online sampler (proposal_target.hip): the IoU is the corner clip in double, not boxes_iou3d_gpu; the ground
 // truth is counted (num_gt), not padded with zero rows; the foreground list holds the labels' best RoIs; the noisy box is float64;
 // a frame with foreground but no background candidate makes the reference raise (:923, type_as on a numpy array) and is reported
-// through status with its sampled outputs cleared.
+// through status with its sampled outputs cleared.  Everything else of phase 2 -- lists, slot plan, ranks, picks, the decoding of cfg6,
+// the noise range rows -- is roi_sample.h, one statement for both.
 //
 // Randomness (counter_rand.h; scene.hip's header lists every stream id), r(stream, frame, position):
 //   stream 40, position = place t in the foreground list   np.random.permutation (:913): the slots go to the places with the
@@ -43,9 +44,8 @@ struct RoParams {
     const int32_t* num_gt;       // (B)
     const int32_t* frame_ids;    // (B) or NULL
     int B, M, G, R;
-    float fg_thresh, cls_bg, cls_bg_lo;
-    double pos_thresh, hard_ratio;
-    int fg_per_image, aug_times, aug_method;
+    RsCfg c;
+    int aug_times, aug_method;
     unsigned seed;
     float* iou;                  // (B, M, G)
     float* rois; float* gt_of_rois; float* roi_iou; int32_t* src;      // (B,R,7) (B,R,7) (B,R) (B,R)
@@ -74,7 +74,8 @@ __global__ __launch_bounds__(RO_THREADS) void ro_iou_kernel(const RoParams P) {
 __global__ __launch_bounds__(RO_THREADS) void ro_sample_kernel(const RoParams P) {
     extern __shared__ int lds_i[];                    // mo[M] (float), fg[M + G], hard[M], easy[M], keys[M + G]
     __shared__ int s_col[RO_MAX_GT];                  // the best RoI of every label, -1 when its column maximum is not > 0
-    __shared__ int s_n[3], s_slots[2], s_hard_slots;
+    __shared__ RsLists s_lists;
+    __shared__ RsPlan s_plan;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const unsigned frame = P.frame_ids ? (unsigned)P.frame_ids[b] : (unsigned)b;
     const float* roi = P.roi + (size_t)b * P.M * 7;
@@ -91,10 +92,7 @@ __global__ __launch_bounds__(RO_THREADS) void ro_sample_kernel(const RoParams P)
     int32_t* o_src = P.src + (size_t)b * P.R;
     const int nr = ro_count(P.num_roi, b, P.M), ng = ro_count(P.num_gt, b, P.G);
 
-    for (int t = tid; t < P.R; t += RO_THREADS) {
-        o_src[t] = -1; o_iou[t] = 0.f;
-        for (int c = 0; c < 7; c++) { o_roi[(size_t)t * 7 + c] = 0.f; o_gt[(size_t)t * 7 + c] = 0.f; }
-    }
+    rs_clear(o_roi, o_gt, o_iou, o_src, P.R, tid, RO_THREADS);
     // phase 1: iou3d.max(axis=1) / argmax(axis=1), rows past num_roi cleared
     for (int i = tid; i < P.M; i += RO_THREADS) {
         float best = 0.f;
@@ -137,43 +135,25 @@ __global__ __launch_bounds__(RO_THREADS) void ro_sample_kernel(const RoParams P)
     // by the LDS latency an estimated 1 - 2 us at the workload's M = 300 and 20 - 30 us at the cap of 4096 (not timed on its own; the
     // whole call measures 181 us at M = 300 and 643 us at the cap).  A prefix scan would buy back that part only.
     if (tid == 0) {
-        int nfg = 0, nhard = 0, neasy = 0;
-        for (int i = 0; i < nr; i++) {
-            const float v = mo[i];
-            if (v >= P.fg_thresh) fg[nfg++] = i;
-            if (v < P.cls_bg_lo) easy[neasy++] = i;
-            if (v < P.cls_bg && v >= P.cls_bg_lo) hard[nhard++] = i;
-        }
+        RsLists l = rs_lists(mo, nr, P.c, fg, hard, easy);
         for (int j = 0; j < ng; j++)
-            if (s_col[j] >= 0) fg[nfg++] = s_col[j];
-        s_n[0] = nfg; s_n[1] = nhard; s_n[2] = neasy;
-        P.counts[b * 4] = nfg; P.counts[b * 4 + 1] = nhard; P.counts[b * 4 + 2] = neasy;
-        const int nbg = nhard + neasy;
-        int fs = 0, bs = 0;
-        if (nfg > 0 && nbg > 0) { fs = min(P.fg_per_image, nfg); bs = P.R - fs; }
-        else if (nbg > 0) bs = P.R;
-        else P.status[b] = 1;                        // foreground only (:923 raises), or no candidate at all (:932-935)
-        s_slots[0] = fs; s_slots[1] = bs;
-        int nh = 0;
-        if (nhard > 0 && neasy > 0) nh = (int)((double)bs * P.hard_ratio);
-        else if (nhard > 0) nh = bs;
-        s_hard_slots = nh;
-        P.counts[b * 4 + 3] = fs;
+            if (s_col[j] >= 0) fg[l.nfg++] = s_col[j];
+        const RsPlan p = rs_plan(l, P.R, P.c.fg_per_image, P.c.hard_ratio);
+        if (p.kind == RS_FG_ONLY || p.kind == RS_NEITHER) P.status[b] = 1;      // foreground only (:923 raises), or no candidate at all (:932-935)
+        s_lists = l; s_plan = p;
+        P.counts[b * 4] = l.nfg; P.counts[b * 4 + 1] = l.nhard; P.counts[b * 4 + 2] = l.neasy; P.counts[b * 4 + 3] = p.fs;
     }
     __syncthreads();
-    const int nfg = s_n[0], nhard = s_n[1], neasy = s_n[2], fs = s_slots[0], bs = s_slots[1], nh = s_hard_slots;
-    if (fs + bs == 0) return;
-    // without replacement: place t goes to slot rank(t) = the number of places with a smaller (key, place)
-    for (int t = tid; t < nfg && fs > 0; t += RO_THREADS) {
-        const unsigned k = keys[t];
-        int rank = 0;
-        for (int u = 0; u < nfg; u++) rank += (keys[u] < k || (keys[u] == k && u < t)) ? 1 : 0;
+    const RsLists l = s_lists;
+    const RsPlan p = s_plan;
+    const int fs = p.fs;
+    if (fs + p.bs == 0) return;
+    for (int t = tid; t < l.nfg && fs > 0; t += RO_THREADS) {
+        const int rank = rs_rank(keys, l.nfg, t);
         if (rank < fs) o_src[rank] = fg[t];
     }
-    for (int t = tid; t < bs; t += RO_THREADS) {
-        if (t < nh) o_src[fs + t] = hard[ro_below(scene_rand(P.seed, RO_STREAM_HARD, frame, (unsigned)t), nhard)];
-        else o_src[fs + t] = easy[ro_below(scene_rand(P.seed, RO_STREAM_EASY, frame, (unsigned)(t - nh)), neasy)];
-    }
+    for (int t = tid; t < p.bs; t += RO_THREADS)
+        o_src[fs + t] = rs_bg_pick(t, p, l, hard, easy, P.seed, RO_STREAM_HARD, RO_STREAM_EASY, frame);
     __syncthreads();
     // phase 3: aug_roi_by_noise_batch
     for (int t = tid; t < P.R; t += RO_THREADS) {
@@ -182,7 +162,7 @@ __global__ __launch_bounds__(RO_THREADS) void ro_sample_kernel(const RoParams P)
         float box[7], g[7], gc[24], out[7], v;
         for (int c = 0; c < 7; c++) { box[c] = roi[(size_t)i * 7 + c]; g[c] = gt[(size_t)ga * 7 + c]; }
         ro_corners_f32(g, gc, true);
-        ro_noise_slot(box, gc, t < fs ? P.aug_times : min(P.aug_times, 1), P.pos_thresh, P.seed, frame, (unsigned)t, P.aug_method, out, &v);
+        ro_noise_slot(box, gc, t < fs ? P.aug_times : min(P.aug_times, 1), P.c.pos_thresh, P.seed, frame, (unsigned)t, P.aug_method, out, &v);
         for (int c = 0; c < 7; c++) { o_roi[(size_t)t * 7 + c] = out[c]; o_gt[(size_t)t * 7 + c] = g[c]; }
         o_iou[t] = v;
     }
@@ -204,11 +184,7 @@ PRCNN_API int prcnn_rcnn_offline_sample(const float* roi_boxes3d, const int32_t*
     RoParams P;
     P.roi = roi_boxes3d; P.num_roi = num_roi; P.gt = gt_boxes3d; P.num_gt = num_gt; P.frame_ids = frame_ids;
     P.B = B; P.M = M; P.G = G; P.R = roi_per_image;
-    // numpy compares the float32 overlap ARRAY with a Python float in float32, the float32 SCALAR of the noise loop in double; the two
-    // ratios stay double as in prcnn_proposal_target_sample: np.round(FG_RATIO * ROI_PER_IMAGE), int(bg_rois * HARD_BG_RATIO)
-    P.pos_thresh = cfg6[0] < cfg6[1] ? cfg6[0] : cfg6[1];
-    P.fg_thresh = (float)P.pos_thresh; P.cls_bg = (float)cfg6[2]; P.cls_bg_lo = (float)cfg6[3]; P.hard_ratio = cfg6[5];
-    P.fg_per_image = (int)nearbyint(cfg6[4] * (double)roi_per_image);
+    P.c = rs_cfg(cfg6, roi_per_image);
     P.aug_times = aug_times; P.aug_method = aug_method; P.seed = seed;
     P.iou = iou3d; P.rois = rois; P.gt_of_rois = gt_of_rois; P.roi_iou = roi_iou; P.src = src; P.max_overlaps = max_overlaps;
     P.gt_assignment = gt_assignment; P.counts = counts; P.status = status;

@@ -19,12 +19,12 @@
 //       train_input.hip) proves that the exact clip is empty: the overlap is then exactly 0 and so is the quotient, the same
 //       +0.0f the clip returns, so the test changes no result and only saves the clip;
 //   `temp_iou < pos_thresh` compares a numpy float32 scalar with a Python float: in double.
-// Randomness: counter_rand.h, stream RO_STREAM_NOISE, position ((slot * 16 + attempt) * 16 + q) -- q = 8 the keep-the-original
+// Randomness: counter_rand.h (through roi_sample.h, whose below() and range rows the online sampler shares), stream RO_STREAM_NOISE, position ((slot * 16 + attempt) * 16 + q) -- q = 8 the keep-the-original
 // draw (u < 0.2), q = 0 the range row (below(r, 5)), q = 1..3 position, q = 4..6 size, q = 7 heading.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "quad_clip.h"
-#include "counter_rand.h"
+#include "roi_sample.h"
 #include "ref_trig.h"
 
 constexpr unsigned RO_STREAM_FG_KEY = 40;     // position = place in the foreground list: the draw without replacement
@@ -32,8 +32,6 @@ constexpr unsigned RO_STREAM_HARD = 42;       // position = hard-background slot
 constexpr unsigned RO_STREAM_EASY = 43;       // position = easy-background slot
 constexpr unsigned RO_STREAM_NOISE = 50;
 constexpr int RO_MAX_AUG_TIMES = 16;          // the attempt field of the noise position is four bits wide
-
-__host__ __device__ __forceinline__ int ro_below(unsigned r, int n) { return (int)(((unsigned long long)r * (unsigned long long)n) >> 32); }
 
 // boxes3d_to_corners3d of a float32 box -> (8,3) float32; fused: the one-box form
 __host__ __device__ inline void ro_corners_f32(const float* bx, float* c, bool fused) {
@@ -107,23 +105,17 @@ __host__ __device__ inline float ro_pair_iou(const float* ca, const float* cb) {
 // random_aug_box3d: method 0 'multiple' (:760-774), 1 'single' (:752-759); base = the attempt's first position
 __host__ __device__ inline void ro_noise_box(const float* box, unsigned seed, unsigned frame, unsigned base, int method, double* aug) {
     const double pi = 3.14159265358979323846;
-    double pos_r = 0.0, hwl_r = 0.0, ang_r = 0.0;
-    if (method == 0) {
-        const int idx = ro_below(scene_rand(seed, RO_STREAM_NOISE, frame, base), 5);      // selects: an indexed local table is scratch memory
-        pos_r = idx == 0 ? 0.2 : idx == 1 ? 0.3 : idx == 2 ? 0.5 : idx == 3 ? 0.8 : 1.0;
-        hwl_r = idx == 0 ? 0.1 : 0.15;
-        ang_r = idx < 2 ? pi / 12 : idx == 2 ? pi / 9 : idx == 3 ? pi / 6 : pi / 3;
-    }
+    const RsNoiseRange rg = rs_noise_range(method == 0 ? rs_below(scene_rand(seed, RO_STREAM_NOISE, frame, base), 5) : 0);      // roi_sample.h
     for (int c = 0; c < 3; ++c) {
         const double up = scene_u01(scene_rand(seed, RO_STREAM_NOISE, frame, base + 1 + c)) - 0.5;
         const double uh = scene_u01(scene_rand(seed, RO_STREAM_NOISE, frame, base + 4 + c)) - 0.5;
-        const double ps = method == 0 ? (up / 0.5) * pos_r : up;
-        const double hs = method == 0 ? (uh / 0.5) * hwl_r + 1.0 : uh / (0.5 / 0.15) + 1.0;
+        const double ps = method == 0 ? (up / 0.5) * rg.pos : up;
+        const double hs = method == 0 ? (uh / 0.5) * rg.hwl + 1.0 : uh / (0.5 / 0.15) + 1.0;
         aug[c] = (double)box[c] + ps;
         aug[3 + c] = (double)box[3 + c] * hs;
     }
     const double ua = scene_u01(scene_rand(seed, RO_STREAM_NOISE, frame, base + 7)) - 0.5;
-    aug[6] = (double)box[6] + (method == 0 ? (ua / 0.5) * ang_r : ua / (0.5 / (pi / 12)));
+    aug[6] = (double)box[6] + (method == 0 ? (ua / 0.5) * rg.ang : ua / (0.5 / (pi / 12)));
 }
 
 // aug_roi_by_noise_batch for one slot: box = the sampled RoI, gtc = its label's corners (one-box form), times = 10 (foreground) / 1 (background).

@@ -999,6 +999,20 @@ def boxes_iou3d(boxes_a, boxes_b):
     return out
 
 
+# the eight outputs both RoI samplers share
+def _roi_sample_outputs(B, M, R, dev):
+    return {"rois": torch.empty((B, R, 7), dtype=_F32, device=dev), "gt_of_rois": torch.empty((B, R, 7), dtype=_F32, device=dev),
+            "roi_iou": torch.empty((B, R), dtype=_F32, device=dev), "src": torch.empty((B, R), dtype=_INT, device=dev),
+            "max_overlaps": torch.empty((B, M), dtype=_F32, device=dev), "gt_assignment": torch.empty((B, M), dtype=_INT, device=dev),
+            "counts": torch.empty((B, 4), dtype=_INT, device=dev), "status": torch.empty((B,), dtype=_INT, device=dev)}
+
+
+# -> cfg6 (doubles: the ratios must arrive as Python computes with them) as a pointer, aug_method as the C ABI's number
+def _roi_sample_cfg(thresholds, fg_ratio, hard_bg_ratio, aug_method):
+    cfg6 = (ctypes.c_double * 6)(*[float(v) for v in tuple(thresholds) + (fg_ratio, hard_bg_ratio)])
+    return ctypes.cast(cfg6, ctypes.c_void_p), {"multiple": 0, "single": 1}[aug_method]
+
+
 def proposal_target_sample(roi_boxes3d, gt_boxes3d, roi_per_image=64, thresholds=(0.55, 0.6, 0.45, 0.05), fg_ratio=0.5, hard_bg_ratio=0.8,
                            aug_times=10, aug_method="multiple", seed=0):
     """ProposalTargetLayer.sample_rois_for_rcnn for the whole batch in one launch (lib/rpn/proposal_target_layer.py:75-250).
@@ -1008,13 +1022,10 @@ def proposal_target_sample(roi_boxes3d, gt_boxes3d, roi_per_image=64, thresholds
     B, M, _ = roi_boxes3d.shape
     G, gc = gt_boxes3d.shape[1], gt_boxes3d.shape[2]
     R, dev = int(roi_per_image), roi_boxes3d.device
-    o = {"rois": torch.empty((B, R, 7), dtype=_F32, device=dev), "gt_of_rois": torch.empty((B, R, 7), dtype=_F32, device=dev),
-         "roi_iou": torch.empty((B, R), dtype=_F32, device=dev), "src": torch.empty((B, R), dtype=_INT, device=dev),
-         "max_overlaps": torch.empty((B, M), dtype=_F32, device=dev), "gt_assignment": torch.empty((B, M), dtype=_INT, device=dev),
-         "counts": torch.empty((B, 4), dtype=_INT, device=dev), "status": torch.empty((B,), dtype=_INT, device=dev)}
-    cfg6 = (ctypes.c_double * 6)(*[float(v) for v in tuple(thresholds) + (fg_ratio, hard_bg_ratio)])
-    _cabi.check(_cabi.lib().prcnn_proposal_target_sample(_p(roi_boxes3d), _p(gt_boxes3d), B, M, G, gc, R, ctypes.cast(cfg6, ctypes.c_void_p),
-                                                         int(aug_times), {"multiple": 0, "single": 1}[aug_method], seed & 0xFFFFFFFF,
+    o = _roi_sample_outputs(B, M, R, dev)
+    cfg6, method = _roi_sample_cfg(thresholds, fg_ratio, hard_bg_ratio, aug_method)
+    _cabi.check(_cabi.lib().prcnn_proposal_target_sample(_p(roi_boxes3d), _p(gt_boxes3d), B, M, G, gc, R, cfg6,
+                                                         int(aug_times), method, seed & 0xFFFFFFFF,
                                                          _p(o["rois"]), _p(o["gt_of_rois"]), _p(o["roi_iou"]), _p(o["src"]),
                                                          _p(o["max_overlaps"]), _p(o["gt_assignment"]), _p(o["counts"]), _p(o["status"]),
                                                          _stream()), "prcnn_proposal_target_sample")
@@ -1047,15 +1058,11 @@ def rcnn_offline_sample(roi_boxes3d, num_roi, gt_boxes3d, num_gt, roi_per_image=
         if t is not None and t.device != dev:
             raise RuntimeError("rcnn_offline_sample: %s is on %s, roi_boxes3d on %s" % (name, t.device, dev))
     R = int(roi_per_image)
-    o = {"iou3d": torch.empty((B, M, G), dtype=_F32, device=dev),
-         "rois": torch.empty((B, R, 7), dtype=_F32, device=dev), "gt_of_rois": torch.empty((B, R, 7), dtype=_F32, device=dev),
-         "roi_iou": torch.empty((B, R), dtype=_F32, device=dev), "src": torch.empty((B, R), dtype=_INT, device=dev),
-         "max_overlaps": torch.empty((B, M), dtype=_F32, device=dev), "gt_assignment": torch.empty((B, M), dtype=_INT, device=dev),
-         "counts": torch.empty((B, 4), dtype=_INT, device=dev), "status": torch.empty((B,), dtype=_INT, device=dev)}
-    cfg6 = (ctypes.c_double * 6)(*[float(v) for v in tuple(thresholds) + (fg_ratio, hard_bg_ratio)])
+    o = dict(iou3d=torch.empty((B, M, G), dtype=_F32, device=dev), **_roi_sample_outputs(B, M, R, dev))
+    cfg6, method = _roi_sample_cfg(thresholds, fg_ratio, hard_bg_ratio, aug_method)
     _cabi.check(_cabi.lib().prcnn_rcnn_offline_sample(
-        _p(roi_boxes3d), _p(num_roi), _p(gt_boxes3d), _p(num_gt), _p(frame_ids), B, M, G, R, ctypes.cast(cfg6, ctypes.c_void_p),
-        int(aug_times), {"multiple": 0, "single": 1}[aug_method], int(seed) & 0xFFFFFFFF, _p(o["iou3d"]), _p(o["rois"]), _p(o["gt_of_rois"]),
+        _p(roi_boxes3d), _p(num_roi), _p(gt_boxes3d), _p(num_gt), _p(frame_ids), B, M, G, R, cfg6,
+        int(aug_times), method, int(seed) & 0xFFFFFFFF, _p(o["iou3d"]), _p(o["rois"]), _p(o["gt_of_rois"]),
         _p(o["roi_iou"]), _p(o["src"]), _p(o["max_overlaps"]), _p(o["gt_assignment"]), _p(o["counts"]), _p(o["status"]), _stream()),
         "prcnn_rcnn_offline_sample")
     return o

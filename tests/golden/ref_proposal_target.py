@@ -203,6 +203,28 @@ def scenes(seed, B=3, M=512, G=12):
     return np.stack(rois), np.stack(gts)
 
 
+# what small_frames() is built to be: per frame counts [nfg, nhard, neasy, fs] and status at roi_per_image 8 (the tests hold the oracle
+# to this table before they use the frames)
+SMALL_COUNTS = ([16, 0, 0, 8], [0, 0, 0, 0], [0, 16, 0, 0], [0, 0, 16, 0], [0, 0, 0, 0], [8, 8, 0, 4], [8, 0, 8, 4])
+SMALL_STATUS = (0, 1, 0, 0, 2, 0, 0)
+
+
+def small_frames():
+    """seven frames (M 16, G 2) for the cases scenes() never produces: one car of scenes(7) tiled 16 times and shifted along x by s
+    (IoU 1 at s = 0, ~0.52 at 0.51: in neither candidate set, ~0.29 at 0.93: hard background, 0 at 30: easy background), z of RoI i
+    raised by i mm so that the RoIs are distinct; ground truth = [the car, a zero row], all zero in frame 4.
+    0 foreground only (with replacement), 1 no candidate (status 1), 2 hard only, 3 easy only, 4 no ground truth (status 2),
+    5 foreground + hard, 6 foreground + easy"""
+    car = scenes(7)[1][0, :1]
+    shifts = [[0] * 16, [0.51] * 16, [0.93] * 16, [30] * 16, [0.93] * 16, [0] * 8 + [0.93] * 8, [0] * 8 + [30] * 8]
+    roi = np.tile(car, (7, 16, 1))
+    roi[:, :, 0] += np.array(shifts, np.float32)
+    roi[:, :, 2] += (np.arange(16) * 1e-3).astype(np.float32)
+    gt = np.tile(np.concatenate([car, np.zeros((1, 7), np.float32)]), (7, 1, 1))
+    gt[4] = 0
+    return roi, gt
+
+
 def aug_inputs(seed=3, B=2, R=16, S=32):
     """seeded inputs for the data_augmentation fixture (shared with the tests)"""
     g = torch.Generator().manual_seed(seed)

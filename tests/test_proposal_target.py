@@ -121,6 +121,13 @@ def test_hip_sampler_equals_oracle_and_reference_fixture(g, cpu, dev):
         assert np.array_equal(got[k].cpu().numpy(), want[k]), k
     k = 6
     assert np.array_equal(ops.boxes_iou3d(t(roi[0]), t(gt[0, :k])).cpu().numpy(), cpu.boxes_iou3d(roi[0], gt[0, :k]))
+    # the cases scenes() never produces: no candidate (status 1), no ground truth (status 2), hard-only / easy-only background
+    roi, gt = rpt.small_frames()
+    got = ops.proposal_target_sample(t(roi), t(gt), roi_per_image=8, seed=1)
+    want = cpu.proposal_target_sample(roi, gt, roi_per_image=8, seed=1)
+    assert want["counts"].tolist() == [list(c) for c in rpt.SMALL_COUNTS] and want["status"].tolist() == list(rpt.SMALL_STATUS)
+    for k in want:
+        assert np.array_equal(got[k].cpu().numpy(), want[k]), k
 
 
 @pytest.mark.gpu
