@@ -58,6 +58,8 @@ typedef void* prcnn_stream_t; /* hipStream_t */
 #define PRCNN_EUNSUPPORTED (-3) /* valid request this build has no kernel for */
 
 int prcnn_abi_version(void);   /* 12: + prcnn_switches_reload, prcnn_switch_get (the PRCNN_* kernel switches are read once, through one table);
+                                 * still 12 (additive): + prcnn_optim_chunk_elems, prcnn_optim_grad_norm, prcnn_optim_step (the adam_onecycle
+                                 * parameter update: clip, decay and Adam over all tensors in two launches);
                                  * still 12 (additive): + prcnn_eval_gt_max_iou, prcnn_eval_stats_accumulate, prcnn_eval_stats_workspace_bytes
                                  * (recall, segmentation IoU and RCNN accuracy of the evaluation loops counted on the device);
                                  * still 12 (additive): + prcnn_rcnn_offline_sample, prcnn_rcnn_offline_finish (RCNN offline training batches);
@@ -942,6 +944,41 @@ int prcnn_eval_stats_accumulate(const float* gt_max, const int32_t* num_gt, int 
                                 const float* seg, const void* cls_label, int label_is_i64, int64_t N, int seg_mode,
                                 const uint8_t* pred_class, const float* gt_iou, int R, float cls_fg, float cls_bg, float refine_thresh,
                                 void* state, prcnn_stream_t stream);
+
+/* ======================================================================================================
+ * adam_onecycle parameter update (csrc/optim.hip, per-element arithmetic: csrc/optim_math.h) -- gradient-norm clip, decoupled
+ * weight decay and the Adam step over ALL parameter tensors in two launches (pointrcnn_amd/optim.py OneCycleAdam).
+ * Both calls walk two DEVICE-resident tables the caller builds and keeps: `tensors`, one row per parameter tensor (float32,
+ * contiguous; grad null: the tensor receives the decay alone, its moments are not touched and it adds nothing to the norm),
+ * and `chunks`, one row per run of at most PRCNN_OPTIM_CHUNK consecutive elements of one tensor (first a multiple of
+ * PRCNN_OPTIM_CHUNK, first < numel), covering every element of every tensor exactly once.  One workgroup per chunk.
+ *   prcnn_optim_grad_norm -> partial (num_chunks) f64: the sum of grad^2 over each chunk, added in a fixed order; every slot
+ *                            is written, no atomics: the same state gives the same bytes.
+ *   prcnn_optim_step      -> coef null: every workgroup adds the partials in a fixed order, norm = float(sqrt(sum)),
+ *                            coef = min(max_norm / (norm + 1e-6), 1) in float32, {norm, coef} written to state (2) f32;
+ *                            coef given (a device float): it is used as it is, partial / state / max_norm are not read.
+ *                            Then per element, each operation rounded to float32: g = grad * coef; param *= decay;
+ *                            exp_avg += one_minus_beta1 * (g - exp_avg); exp_avg_sq = exp_avg_sq * beta2 + one_minus_beta2 * (g * g);
+ *                            param += neg_step * (exp_avg / (sqrt(exp_avg_sq) / bias2_sqrt + eps)).  grad is never written.
+ * The scalars are the caller's (double arithmetic rounded to float once; optim.py adam_scalars).  Nothing is read back.
+ * ====================================================================================================== */
+#define PRCNN_OPTIM_CHUNK 4096
+typedef struct prcnn_optim_tensor {
+    float* param;
+    const float* grad;          /* null: decay only */
+    float* exp_avg;
+    float* exp_avg_sq;
+    int64_t numel;
+} prcnn_optim_tensor_t;
+typedef struct prcnn_optim_chunk {
+    int64_t tensor, first;      /* row of `tensors`, first element of the chunk */
+} prcnn_optim_chunk_t;
+size_t prcnn_optim_chunk_elems(void);
+int prcnn_optim_grad_norm(const prcnn_optim_tensor_t* tensors, const prcnn_optim_chunk_t* chunks, int64_t num_chunks, double* partial,
+                          prcnn_stream_t stream);
+int prcnn_optim_step(const prcnn_optim_tensor_t* tensors, const prcnn_optim_chunk_t* chunks, int64_t num_chunks, const double* partial,
+                     float max_norm, const float* coef, float* state, float decay, float one_minus_beta1, float beta2,
+                     float one_minus_beta2, float bias2_sqrt, float eps, float neg_step, prcnn_stream_t stream);
 
 #ifdef __cplusplus
 }

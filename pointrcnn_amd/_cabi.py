@@ -160,6 +160,9 @@ SIGNATURES = {
     "prcnn_eval_stats_workspace_bytes": (_Z, [_I, _I, _I]),
     "prcnn_eval_gt_max_iou": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
     "prcnn_eval_stats_accumulate": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _L, _I, _P, _P, _I, _F, _F, _F, _P, _P]),
+    "prcnn_optim_chunk_elems": (_Z, []),
+    "prcnn_optim_grad_norm": (_I, [_P, _P, _L, _P, _P]),
+    "prcnn_optim_step": (_I, [_P, _P, _L, _P, _F, _P, _P, _F, _F, _F, _F, _F, _F, _F, _P]),
 }
 
 _lib = None

@@ -165,6 +165,38 @@ def rpn_loss_rows(dev, B=16, N=16384, rounds=5):
         print(json.dumps(d), flush=True)
 
 
+def optimizer_rows(dev, rounds=5):
+    """`optimizer step`: one optim.OneCycleAdam.step() -- gradient-norm clip, decoupled decay, Adam, schedule -- over the parameter
+    lists of rpn.RPN() and of the RCNN net, the composed torch route against the two launches of csrc/optim.hip, alternated in one
+    process; per route the median, minimum and maximum over `rounds` windows of 20 calls.  The gradients are fixed tensors (the
+    pointer table is uploaded once).  Traffic floor of the fused route: the gradient read twice, parameter and both moments read
+    and written once: 32 bytes per element."""
+    from . import point_rcnn
+    from .optim import OneCycleAdam
+    g = torch.Generator().manual_seed(3)
+    for name, net in (("rpn.RPN()", rpn.RPN()), ("rcnn_net", point_rcnn.PointRCNN(mode="TRAIN").rcnn_net)):
+        shapes = [p.shape for p in net.parameters() if p.requires_grad]
+        opts = {}
+        for fused in (False, True):
+            ps = [torch.nn.Parameter((torch.randn(s, generator=g) * 0.1).to(dev)) for s in shapes]
+            for p in ps:
+                p.grad = (torch.randn(p.shape, generator=g) * 0.01).to(dev)
+            opts[fused] = OneCycleAdam(ps, 10000, fused=fused)
+        times = {False: [], True: []}
+        for _ in range(rounds):
+            for fused in (False, True):
+                times[fused].append(timeit(opts[fused].step))
+        n = sum(int(torch.Size(s).numel()) for s in shapes)
+        for fused in (False, True):
+            t = sorted(times[fused])
+            d = {"op": "optimizer step (%s)" % ("fused" if fused else "composed"), "shape": "%s: %d tensors, %d elements" % (name, len(shapes), n),
+                 "median_us": round(t[len(t) // 2] * 1e6, 1), "min_us": round(t[0] * 1e6, 1), "max_us": round(t[-1] * 1e6, 1)}
+            if fused:
+                d.update(traffic_floor_MB=round(32 * n / 1e6, 2), floor_GBps_at_median=round(32 * n / t[len(t) // 2] / 1e9, 1),
+                         table_uploads=opts[True].table_uploads)
+            print(json.dumps(d), flush=True)
+
+
 def rcnn_offline_rows(dev, B=4, M=300, G=12, R=64, N=16384, C=128, S=512):
     """`rcnn_offline_batch`: kitti_input.RCNNOfflinePreparer's device side (`--train_mode rcnn_offline`, ROI_SAMPLE_JIT False) at the
     workload's shape -- RoI sampling (IoU matrix + lists + picks + noise loop), pooling of the sampled RoIs (prcnn_roipool3d, mask +
@@ -309,11 +341,14 @@ def eval_stats_rows(dev, B=32, shapes=((100, 12), (512, 24)), N=16384, rounds=5)
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
-    ap.add_argument("--only", default=None, help="run one row family only: eval_stats")
+    ap.add_argument("--only", default=None, help="run one row family only: eval_stats | optimizer")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     if args.only == "eval_stats":
         eval_stats_rows(dev)
+        return
+    if args.only == "optimizer":
+        optimizer_rows(dev)
         return
     B = 8 if args.quick else 32
     N = 16384
@@ -422,6 +457,8 @@ def main():
     rpn_loss_rows(dev)
     # ---- the RCNN training loss and its gradient: composed torch against the device passes (csrc/rcnn_loss.hip)
     rcnn_loss_rows(dev)
+    # ---- the adam_onecycle parameter update: composed torch against the two launches of csrc/optim.hip
+    optimizer_rows(dev)
     # ---- the evaluation statistics of a batch: the reference's per-frame loop on this library against the device passes (csrc/eval_stats.hip)
     eval_stats_rows(dev)
 

@@ -1523,3 +1523,59 @@ def eval_stats_accumulate(state, gt_max, num_gt, B, det_num=None, seg=None, cls_
     _cabi.check(_cabi.lib().prcnn_eval_stats_accumulate(_p(gt_max), _p(num_gt), S, B, G, _p(det_num), _p(seg), _p(cls_label), is64, N,
                                                         int(seg_mode), _p(pred_class), _p(gt_iou), R, float(cls_fg), float(cls_bg),
                                                         float(refine_thresh), _p(state), _stream()), "prcnn_eval_stats_accumulate")
+
+
+# ------------------------------------------------------------------ adam_onecycle parameter update (csrc/optim.hip)
+OPTIM_CHUNK = 4096                       # PRCNN_OPTIM_CHUNK: elements per chunk, one workgroup each
+OPTIM_SCALARS = ("decay", "one_minus_beta1", "beta2", "one_minus_beta2", "bias2_sqrt", "eps", "neg_step")
+
+
+def optim_chunk_rows(numels):
+    """the chunk table of tensors with these element counts, as a list of (tensor, first element) rows: every element of every
+    tensor exactly once, in order; a tensor without elements has no row"""
+    return [(t, first) for t, n in enumerate(numels) for first in range(0, int(n), OPTIM_CHUNK)]
+
+
+def _optim_tables(tensors, chunks):
+    _chk(tensors, "tensors", torch.int64, 2); _chk(chunks, "chunks", torch.int64, 2)
+    if tensors.shape[1] != 5 or chunks.shape[1] != 2:
+        raise ValueError("optim: tensors must be (T, 5) [param, grad, exp_avg, exp_avg_sq, numel] and chunks (C, 2) [tensor, first], "
+                         "got %s and %s" % (tuple(tensors.shape), tuple(chunks.shape)))
+    if chunks.shape[0] and not tensors.shape[0]:
+        raise ValueError("optim: %d chunks of an empty tensor table" % chunks.shape[0])
+    return chunks.shape[0]
+
+
+def optim_grad_norm(tensors, chunks, partial=None):
+    """tensors (T,5) i64 and chunks (C,2) i64 on the device (prcnn_optim_tensor_t / prcnn_optim_chunk_t rows; the caller vouches for
+    the addresses in them) -> partial (C) f64, the sum of grad^2 over every chunk.  One launch, nothing read back."""
+    C = _optim_tables(tensors, chunks)
+    if partial is None:
+        partial = torch.empty((C,), dtype=torch.float64, device=tensors.device)
+    elif tuple(_chk(partial, "partial", torch.float64, 1).shape) != (C,):
+        raise ValueError("optim_grad_norm: partial must be (%d,)" % C)
+    _cabi.check(_cabi.lib().prcnn_optim_grad_norm(_p(tensors), _p(chunks), C, _p(partial), _stream()), "prcnn_optim_grad_norm")
+    return partial
+
+
+def optim_step(tensors, chunks, scalars, partial=None, max_norm=1.0, coef=None, state=None):
+    """clip coefficient + decay + Adam over every chunk in one launch.  scalars: the seven OPTIM_SCALARS (optim.adam_scalars).
+    coef None: the coefficient is formed from `partial` (optim_grad_norm) and max_norm, and {norm, coef} go to state (2) f32;
+    coef (1) f32 on the device: it is used as it is.  -> state (None with a caller's coef).  Nothing is read back."""
+    C = _optim_tables(tensors, chunks)
+    if len(scalars) != len(OPTIM_SCALARS):
+        raise ValueError("optim_step: scalars must be the %d values %s" % (len(OPTIM_SCALARS), ", ".join(OPTIM_SCALARS)))
+    if coef is not None:
+        if _chk(coef, "coef").numel() != 1:
+            raise ValueError("optim_step: coef must hold one float")
+        state = None
+    else:
+        if partial is None or tuple(_chk(partial, "partial", torch.float64, 1).shape) != (C,):
+            raise ValueError("optim_step: without coef, partial must be the (%d,) float64 result of optim_grad_norm" % C)
+        if state is None:
+            state = torch.zeros((2,), dtype=_F32, device=tensors.device)
+        elif _chk(state, "state", _F32, 1).numel() != 2:
+            raise ValueError("optim_step: state must be (2,) float32")
+    _cabi.check(_cabi.lib().prcnn_optim_step(_p(tensors), _p(chunks), C, _p(partial), float(max_norm), _p(coef), _p(state),
+                                             *[float(s) for s in scalars], _stream()), "prcnn_optim_step")
+    return state
