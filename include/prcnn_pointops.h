@@ -58,6 +58,8 @@ typedef void* prcnn_stream_t; /* hipStream_t */
 #define PRCNN_EUNSUPPORTED (-3) /* valid request this build has no kernel for */
 
 int prcnn_abi_version(void);   /* 12: + prcnn_switches_reload, prcnn_switch_get (the PRCNN_* kernel switches are read once, through one table);
+                                 * still 12 (additive): + prcnn_aug_scene_sample, prcnn_aug_scene_workspace_bytes, prcnn_aug_scene_count,
+                                 * prcnn_aug_scene_fill (the offline GT-augmented scenes, the train_aug split, generated on the device);
                                  * still 12 (additive): + prcnn_optim_chunk_elems, prcnn_optim_grad_norm, prcnn_optim_step (the adam_onecycle
                                  * parameter update: clip, decay and Adam over all tensors in two launches);
                                  * still 12 (additive): + prcnn_eval_gt_max_iou, prcnn_eval_stats_accumulate, prcnn_eval_stats_workspace_bytes
@@ -671,6 +673,54 @@ int prcnn_gt_database_fill(const float* raw, const int64_t* offsets, int B, int6
                            const float* calib, const float* boxes3d, const int32_t* num_boxes, int G, const int64_t* obj_offsets,
                            int64_t total_out, float* points, float* intensity, int32_t* src, void* workspace,
                            size_t workspace_bytes, prcnn_stream_t stream);
+
+/* ======================================================================================================
+ * Offline GT-augmented scenes (aug_scene.hip).  tools/generate_aug_scene.py for a batch of frames: step 1 of the reference's offline
+ * RCNN recipe (the `train_aug` split that eval_rcnn.py --save_rpn_feature and train_rcnn.py --train_mode rcnn_offline then read).
+ *
+ * prcnn_aug_scene_sample: AugSceneGenerator.aug_one_scene's sampling loop (:157-219), one launch, no host round trip.
+ *   gt_boxes3d (B, G, 7) + num_gt (B) i32 or NULL: the frame's non-DontCare labels; planes (B, 4) f64 road planes;
+ *   frame_ids (B) i32: the key of the random table, the NEW sample id (epoch + 1) * 10000 + sample_id;
+ *   db_boxes (D, 7), db_npts (D) i32: the database; scope: 6 doubles x0 x1 y0 y1 z0 z1 (PC_AREA_SCOPE), required;
+ *   -> count (B), db_id (B, K) (-1 past count), boxes3d (B, K, 7) placed and unenlarged, y_shift (B, K) f64,
+ *      stats (B, 3) i32 extra_gt_num, cnt, tries spent; status (B) i32: 0 ok, 1 the reference raises (D <= 1, or an IoU against an
+ *      empty list), 2 a bound was exceeded.
+ *   It is not the online loop of prcnn_gt_aug_sample: extra_gt_num = randint(10, 15) (stream 60); 50 tries and a try skipped by the range
+ *   check or the "< 5 points" check is spent; the index draw randint(0, D - 1) never draws the last entry (stream 61, position = try);
+ *   range check, then `cnt > extra_gt_num` break, then "< 5 points", plane move (double), cnt += 1, collision; the collision is the
+ *   arithmetic of prcnn_boxes_iou3d between the moved, unenlarged box and the list (labels and accepted boxes with w + 0.5, l + 0.5),
+ *   accepted iff the maximum is < 1e-8 as float32.  cnt <= 15 bounds the accepted objects.
+ *   PRCNN_EINVAL for K < 15, K > 64, G + 15 > 256, a null pointer.
+ *
+ * prcnn_aug_scene_count / prcnn_aug_scene_fill: the augmented cloud (:240-248, :205-231).  raw, offsets, max_points_per_frame, calib,
+ *   img_hw, scope as prcnn_scene_prepare; acc_* = the sampler's outputs; db_points (db_total_points, 3), db_intensity, db_offsets (D+1) i64.
+ *   Per frame: lidar -> rect (canonical), the valid flag, every valid point inside an accepted box tested with h + 2 (the test of
+ *   prcnn_pts_in_boxes3d) dropped, the survivors in raw order, then the accepted objects' database points in acceptance order, each
+ *   object's in database order, with y - y_shift.  A frame with status 1 or count 0 comes out as its valid cloud.
+ *   prcnn_aug_scene_count -> rows (B) i32: the rows of every frame (-1: more than fit the count).  The caller forms out_offsets (B+1) i64,
+ *   their exclusive scan, and total_out = out_offsets[B]; the workspace's content must survive from the count to the fill.
+ *   prcnn_aug_scene_fill  -> out (total_out, 4) [x y z intensity] (the raw intensity), src (total_out) i32: the raw index of a scan
+ *   point, -1 - (database point row) of a pasted one.
+ *   A row's position comes from prefix sums (tile, wave, lane; object sizes), never from an atomic append: two runs give identical
+ *   bytes.  No row outside [0, total_out) or outside its frame's [out_offsets[b], out_offsets[b+1]) is written.
+ *   PRCNN_EINVAL for K outside 1..64, a null pointer, a workspace smaller than prcnn_aug_scene_workspace_bytes, out not 16-byte aligned.
+ * ====================================================================================================== */
+int prcnn_aug_scene_sample(const float* gt_boxes3d, const int32_t* num_gt, const double* planes, const int32_t* frame_ids, int B, int G,
+                           const float* db_boxes, const int32_t* db_npts, int D, const double* scope, int K, uint32_t seed,
+                           int32_t* count, int32_t* db_id, float* boxes3d, double* y_shift, int32_t* stats, int32_t* status,
+                           prcnn_stream_t stream);
+size_t prcnn_aug_scene_workspace_bytes(int64_t max_points_per_frame, int B);
+int prcnn_aug_scene_count(const float* raw, const int64_t* offsets, int B, int64_t total_points, int max_points_per_frame,
+                          const float* calib, const int32_t* img_hw, const double* scope, const int32_t* acc_count,
+                          const int32_t* acc_db_id, const float* acc_boxes3d, const int32_t* acc_status, int K,
+                          const int64_t* db_offsets, int D, int64_t db_total_points, int32_t* rows, void* workspace,
+                          size_t workspace_bytes, prcnn_stream_t stream);
+int prcnn_aug_scene_fill(const float* raw, const int64_t* offsets, int B, int64_t total_points, int max_points_per_frame,
+                         const float* calib, const int32_t* img_hw, const double* scope, const int32_t* acc_count,
+                         const int32_t* acc_db_id, const float* acc_boxes3d, const double* acc_y_shift, const int32_t* acc_status,
+                         int K, const float* db_points, const float* db_intensity, const int64_t* db_offsets, int D,
+                         int64_t db_total_points, const int64_t* out_offsets, int64_t total_out, float* out, int32_t* src,
+                         void* workspace, size_t workspace_bytes, prcnn_stream_t stream);
 
 /* ======================================================================================================
  * Training-mode SharedMLP (csrc/mlp_train.h) -- BASELINE config 4, `train_rcnn.py --train_mode rpn`.

@@ -132,6 +132,10 @@ SIGNATURES = {
     "prcnn_gt_database_workspace_bytes": (_Z, [_L, _I, _I]),
     "prcnn_gt_database_count": (_I, [_P, _P, _I, _L, _I, _P, _P, _P, _I, _P, _P, _Z, _P]),
     "prcnn_gt_database_fill": (_I, [_P, _P, _I, _L, _I, _P, _P, _P, _I, _P, _L, _P, _P, _P, _P, _Z, _P]),
+    "prcnn_aug_scene_sample": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _I, _P, _I, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
+    "prcnn_aug_scene_workspace_bytes": (_Z, [_L, _I]),
+    "prcnn_aug_scene_count": (_I, [_P, _P, _I, _L, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _L, _P, _P, _Z, _P]),
+    "prcnn_aug_scene_fill": (_I, [_P, _P, _I, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _L, _P, _L, _P, _P, _P, _Z, _P]),
     "prcnn_nms_batched": (_I, [_P, _P, _P, _I, _I, _F, _I, _I, _P, _P, _P, _Z, _P]),
     "prcnn_train_stack_work_bytes": (_Z, [_L, ctypes.POINTER(TrainLayer), _I, _I, _I]),
     "prcnn_train_stack_fwd": (_I, [ctypes.POINTER(TrainSrc), ctypes.POINTER(TrainLayer), _I, _I, _P, _I, _P, _I, _I, _P, _P, _Z, _P]),

@@ -31,6 +31,8 @@
 //   35     train_scene.hip: angle = np.random.uniform(-pi / AUG_ROT_RANGE, pi / AUG_ROT_RANGE) (:527), position 0 -- lo + (hi - lo) * u01(r)
 //   36     train_scene.hip: scale = np.random.uniform(0.95, 1.05) (:549), position 0 -- lo + (hi - lo) * u01(r)
 //   40, 42, 43, 50   rcnn_offline.hip (offline RoI sampling and noise; 41 left free); 51-53 its per-RoI augmentation (enable, angle, scale)
+//   60     aug_scene.hip: extra_gt_num = randint(10, 15) (tools/generate_aug_scene.py:157), position 0 -- 10 + below(r, 5)
+//   61     aug_scene.hip: per try t, randint(0, D - 1) (:175), position t -- below(r, D - 1); frame = the new sample id
 //   with u01(r) = fp32(r >> 8) * 2^-24 widened to double, below(r, n) = (r * n) >> 32.
 //   train_scene.hip also uses streams 0-2 for its own draw; there the position is the candidate's identity: the raw index
 //   for a scene point, n_raw + j for the j-th pasted point.

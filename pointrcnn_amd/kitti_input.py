@@ -66,6 +66,7 @@ class Calibration:
         self.P2 = np.asarray(calib["P2"], np.float32).reshape(3, 4)
         self.R0 = np.asarray(calib["R0"], np.float32).reshape(3, 3)
         self.V2C = np.asarray(calib["Tr_velo2cam"], np.float32).reshape(3, 4)
+        self.rect_input = False             # load_aug_frame sets it for a train_aug frame: its points are already rect coordinates
 
     @classmethod
     def from_text(cls, text):
@@ -76,9 +77,15 @@ class Calibration:
         """(4,3) fp32 M with pts_rect = [pts_lidar, 1] . M -- formed exactly as calibration.py:57 forms it"""
         return np.dot(self.V2C.T, self.R0.T)
 
-    def packed(self):
-        """(24,) fp32 row of prcnn_scene_prepare's calib argument"""
-        return np.concatenate([self.lidar_to_rect_matrix().reshape(-1), self.P2.reshape(-1)]).astype(np.float32)
+    def packed(self, rect_input=None):
+        """(24,) fp32 row of prcnn_scene_prepare's calib argument.  rect_input (default: self.rect_input): the points are rect
+        coordinates already (a train_aug frame's rectified_data): the lidar -> rect part is the identity, and the canonical
+        ((x * 1 + y * 0) + z * 0) + 0 reproduces every coordinate (only the sign of a zero may change)"""
+        if self.rect_input if rect_input is None else rect_input:
+            M = np.concatenate([np.eye(3, dtype=np.float32), np.zeros((1, 3), np.float32)])
+        else:
+            M = self.lidar_to_rect_matrix()
+        return np.concatenate([M.reshape(-1), self.P2.reshape(-1)]).astype(np.float32)
 
 
 def get_lidar(lidar_file):
@@ -544,3 +551,322 @@ class TrainScenePreparer:
             out.update(gt_aug_status=torch.zeros((B,), dtype=torch.int32, device=dev), count=torch.zeros((B,), dtype=torch.int32, device=dev),
                        db_id=torch.zeros((B, 0), dtype=torch.int32, device=dev), stats=torch.zeros((B, 4), dtype=torch.int32, device=dev))
         return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# The offline GT-augmented scenes, the `train_aug` split (tools/generate_aug_scene.py; csrc/aug_scene.hip)
+# ---------------------------------------------------------------------------------------------------------
+AUG_SCENE_TRIES = 50
+
+
+def aug_scene_scope(class_name):
+    """PC_AREA_SCOPE of tools/generate_aug_scene.py:26-29 as 6 floats [x0 x1 y0 y1 z0 z1]"""
+    return [-40.0, 40.0, -1.0, 3.0, 0.0, 70.4] if class_name == "Car" else [-30.0, 30.0, -1.0, 3.0, 0.0, 50.0]
+
+
+def _mix32(x):
+    x &= 0xFFFFFFFF
+    x ^= x >> 16
+    x = (x * 0x7feb352d) & 0xFFFFFFFF
+    x ^= x >> 15
+    x = (x * 0x846ca68b) & 0xFFFFFFFF
+    return x ^ (x >> 16)
+
+
+def counter_rand(seed, stream, frame, i):
+    """csrc/counter_rand.h's r(stream, frame, i) on the host"""
+    return _mix32(i ^ _mix32(frame * 0x9E3779B9 + _mix32(seed + stream * 0x85EBCA6B)))
+
+
+def get_image_shape(img_file):
+    """kitti_dataset.get_image_shape (lib/datasets/kitti_dataset.py:33-38): (height, width, 3), from the PNG header alone"""
+    with open(img_file, "rb") as f:
+        head = f.read(24)
+    if head[:8] != b"\x89PNG\r\n\x1a\n" or head[12:16] != b"IHDR":
+        raise ValueError("get_image_shape: %s is not a PNG file" % img_file)
+    return int.from_bytes(head[20:24], "big"), int.from_bytes(head[16:20], "big"), 3
+
+
+def valid_flag_host(pts_rect, P2, img_shape, scope):
+    """rect_to_img + get_valid_flag under the canonical contract of csrc/scene.hip (scene_project) in numpy: fp32, every operation
+    rounded on its own, left to right; the PC_AREA_SCOPE comparisons in double.  pts_rect (n,3) f32, scope 6 floats or None -> (n,) bool"""
+    r = np.ascontiguousarray(pts_rect, np.float32)
+    P = np.asarray(P2, np.float32).reshape(3, 4)
+    x, y, z = r[:, 0], r[:, 1], r[:, 2]
+    h = [((x * P[k, 0] + y * P[k, 1]) + z * P[k, 2]) + P[k, 3] for k in range(3)]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u, v = h[0] / z, h[1] / z
+    depth = h[2] - P[2, 3]
+    ok = (u >= 0) & (u < np.float32(img_shape[1])) & (v >= 0) & (v < np.float32(img_shape[0])) & (depth >= 0)
+    if scope is not None:
+        d = r.astype(np.float64)
+        for k in range(3):
+            ok &= (d[:, k] >= scope[2 * k]) & (d[:, k] <= scope[2 * k + 1])
+    return ok
+
+
+def aug_scene_sample_host(all_gt_boxes3d, plane, db_boxes, db_npts, scope, seed, frame, iou3d):
+    """One frame of prcnn_aug_scene_sample on the host (csrc/aug_scene_math.h restated): AugSceneGenerator.aug_one_scene's sampling
+    loop, tools/generate_aug_scene.py:157-219.  iou3d(a (1,7), b (M,7)) -> (1,M) float32 stands for boxes_iou3d_gpu: this package has
+    no host build of it, the caller brings one.  -> dict ids, boxes (n,7), y_shift (n,) f64, stats (extra_gt_num, cnt, spent), status"""
+    cur = np.array(all_gt_boxes3d, np.float32).reshape(-1, 7)
+    cur[:, 4] += np.float32(0.5)
+    cur[:, 5] += np.float32(0.5)
+    db_boxes = np.asarray(db_boxes, np.float32).reshape(-1, 7)
+    a, b, c, d = (np.float64(v) for v in plane)
+    D = db_boxes.shape[0]
+    extra = 10 + ((counter_rand(seed, 60, frame, 0) * 5) >> 32)
+    ids, boxes, shifts, status, cnt, spent = [], [], [], 0, 0, 0
+    for t in range(AUG_SCENE_TRIES):
+        spent = t + 1
+        if D <= 1:
+            status = 1
+            break
+        i = (counter_rand(seed, 61, frame, t) * (D - 1)) >> 32
+        box = db_boxes[i].copy()
+        x, y, z = (np.float64(v) for v in box[:3])
+        if not (scope[0] <= x <= scope[1] and scope[2] <= y <= scope[3] and scope[4] <= z <= scope[5]):
+            continue
+        if cnt > extra:
+            break
+        if db_npts[i] < 5:
+            continue
+        with np.errstate(all="ignore"):
+            move = y - ((-d - a * x) - c * z) / b
+            box[1] = np.float32(y - move)
+        cnt += 1
+        if cur.shape[0] == 0:
+            status = 1
+            break
+        v = np.asarray(iou3d(box.reshape(1, 7), cur), np.float32).reshape(-1)
+        if not bool((v < np.float32(1e-8)).all()):
+            continue
+        enl = box.copy()
+        enl[4] += np.float32(0.5)
+        enl[5] += np.float32(0.5)
+        cur = np.concatenate([cur, enl[None]])
+        ids.append(int(i)); boxes.append(box); shifts.append(float(move))
+    return {"ids": np.asarray(ids, np.int32), "boxes": np.asarray(boxes, np.float32).reshape(-1, 7),
+            "y_shift": np.asarray(shifts, np.float64), "stats": (int(extra), cnt, spent), "status": status}
+
+
+def aug_scene_build_host(scan, calib, img_shape, scope, boxes, ids, y_shift, db_points, db_intensity, db_offsets):
+    """One frame of prcnn_aug_scene_count / _fill on the host: lidar_to_rect_host, valid_flag_host, the library's host twin of
+    pts_in_boxes3d_cpu on the accepted boxes with h + 2, then the pasted objects with y - y_shift -> (n,4) f32, src (n,) i32"""
+    from . import _cabi
+    rect = np.ascontiguousarray(lidar_to_rect_host(scan, calib.packed()[:12].reshape(4, 3)))
+    keep = valid_flag_host(rect, calib.P2, img_shape, scope)
+    boxes = np.array(boxes, np.float32).reshape(-1, 7)
+    if boxes.shape[0]:
+        boxes[:, 3] += np.float32(2)
+        flags = np.zeros((boxes.shape[0], rect.shape[0]), np.int64)
+        _cabi.check(_cabi.lib().prcnn_host_pts_in_boxes3d(rect.ctypes.data, boxes.ctypes.data, rect.shape[0], boxes.shape[0],
+                                                          flags.ctypes.data), "prcnn_host_pts_in_boxes3d")
+        keep &= ~(flags == 1).any(axis=0)
+    rows = [np.concatenate([rect[keep], np.ascontiguousarray(scan[:, 3:4], np.float32)[keep]], 1)]
+    src = [np.nonzero(keep)[0].astype(np.int32)]
+    for i, move in zip(ids, y_shift):
+        o, e = int(db_offsets[i]), int(db_offsets[i + 1])
+        p = np.array(db_points[o:e], np.float32)
+        p[:, 1] = (p[:, 1].astype(np.float64) - np.float64(move)).astype(np.float32)
+        rows.append(np.concatenate([p, np.asarray(db_intensity[o:e], np.float32).reshape(-1, 1)], 1))
+        src.append((-1 - np.arange(o, e)).astype(np.int32))
+    return np.concatenate(rows).astype(np.float32), np.concatenate(src)
+
+
+def reprint_label_line(line):
+    """Object3d(line).to_kitti_format() (lib/utils/object3d.py:12-30, :97-102): every field parsed as a double, the 2-D box and the
+    position rounded to float32 before they are printed"""
+    f = line.strip().split(" ")
+    v = [float(t) for t in f[1:15]]
+    box2d, pos = np.array(v[3:7], np.float32), np.array(v[10:13], np.float32)
+    return "%s %.2f %d %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f" % (
+        f[0], v[0], int(v[1]), v[2], box2d[0], box2d[1], box2d[2], box2d[3], v[7], v[8], v[9], pos[0], pos[1], pos[2], v[13])
+
+
+def aug_object_lines(boxes3d, truncation, occlusion, P2, img_shape, class_name):
+    """save_kitti_format of tools/generate_aug_scene.py:38-63 for the accepted objects of one frame: the image box from the box
+    corners, clipped; boxes wider / taller than 0.8 of the image dropped; class, truncation %.2f, int(occlusion), then the 12 %.4f fields alpha, image box, h w l, x y z, ry"""
+    from . import kitti_output
+    b = np.asarray(boxes3d, np.float32).reshape(-1, 7)
+    if b.shape[0] == 0:
+        return []
+    H, W = int(img_shape[0]), int(img_shape[1])
+    ib = kitti_output.corners_to_image_boxes(kitti_output.box_corners(b), P2)
+    ib[:, 0::2] = np.clip(ib[:, 0::2], 0, W - 1)
+    ib[:, 1::2] = np.clip(ib[:, 1::2], 0, H - 1)
+    keep = ((ib[:, 2] - ib[:, 0]) < W * 0.8) & ((ib[:, 3] - ib[:, 1]) < H * 0.8)
+    alpha = kitti_output.observation_angle(b)
+    cols = np.column_stack([alpha.astype(np.float64), ib, b[:, 3:6].astype(np.float64), b[:, 0:3].astype(np.float64), b[:, 6].astype(np.float64)])
+    return ["%s %.2f %d" % (class_name, float(truncation[k]), int(occlusion[k])) + (" %.4f" * 12) % tuple(cols[k].tolist())
+            for k in range(b.shape[0]) if keep[k]]
+
+
+class AugSceneGenerator:
+    """tools/generate_aug_scene.py on a KITTI tree: for every epoch and frame of <split>, objects of the GT database pasted onto the road
+    plane where they collide with no label and no earlier paste, written as the `train_aug` split that step 2 (eval_rcnn.py
+    --save_rpn_feature) and step 3 (train_rcnn.py --train_mode rcnn_offline) of the reference's offline recipe read.
+    backend 'device': frames_per_batch frames per prcnn_aug_scene_sample / _count / _fill call; 'host': the same files with no GPU
+    (aug_scene_sample_host, aug_scene_build_host), which needs iou3d=, a host boxes_iou3d_gpu ((1,7), (M,7)) -> (1,M).
+    The truncation / occlusion an accepted object's label line carries are looked up in label_2/<gt_database.sample_id>.txt by exact
+    float32 box match, or given as truncation= / occlusion= arrays (D,)."""
+
+    def __init__(self, root_dir, gt_database, class_name="Car", split="train", include_similar=False, device="cuda", backend="device",
+                 truncation=None, occlusion=None, iou3d=None):
+        if class_name not in GT_DATABASE_CLASSES:
+            raise ValueError("AugSceneGenerator: class_name %r is not one of %s" % (class_name, sorted(GT_DATABASE_CLASSES)))
+        if backend not in ("device", "host"):
+            raise ValueError("AugSceneGenerator: backend %r is not 'device' or 'host'" % (backend,))
+        if backend == "host" and iou3d is None:
+            raise ValueError("AugSceneGenerator: backend 'host' needs iou3d=, a host boxes_iou3d_gpu")
+        split_file = os.path.join(root_dir, "KITTI", "ImageSets", split + ".txt")
+        if not os.path.isfile(split_file):
+            raise FileNotFoundError("AugSceneGenerator: no split file %s" % split_file)
+        with open(split_file) as f:
+            self.frames = [x.strip() for x in f.readlines() if x.strip()]
+        self.base = os.path.join(root_dir, "KITTI", "object", "testing" if split == "test" else "training")
+        self.db, self.class_name, self.split, self.backend, self.iou3d = gt_database, class_name, split, backend, iou3d
+        self.device = torch.device(device)
+        self.scope = aug_scene_scope(class_name)
+        white = list(GT_DATABASE_CLASSES[class_name])                       # generate_aug_scene.py:70-77, :98-111
+        if include_similar:
+            white += (["Van"] if "Car" in white else []) + (["Person_sitting"] if ("Pedestrian" in white or "Cyclist" in white) else [])
+        self.whitelist = white
+        if (truncation is None) != (occlusion is None):
+            raise ValueError("AugSceneGenerator: truncation and occlusion go together")
+        if truncation is not None:
+            self.truncation, self.occlusion = np.asarray(truncation, np.float64).reshape(-1), np.asarray(occlusion, np.float64).reshape(-1)
+            if self.truncation.shape[0] != gt_database.size or self.occlusion.shape[0] != gt_database.size:
+                raise ValueError("AugSceneGenerator: one truncation and one occlusion per database object (%d)" % gt_database.size)
+        else:
+            self.truncation, self.occlusion = self._lookup_trunc_occl()
+
+    def _lookup_trunc_occl(self):
+        db, boxes = self.db, self.db.boxes.cpu().numpy()
+        trunc, occl, cache = np.zeros(db.size), np.zeros(db.size), {}
+        for k in range(db.size):
+            sid = int(db.sample_id[k])
+            if sid < 0:
+                raise ValueError("AugSceneGenerator: database object %d does not say which frame it came from (sample_id -1): "
+                                 "pass truncation= and occlusion=" % k)
+            if sid not in cache:
+                with open(os.path.join(self.base, "label_2", "%06d.txt" % sid)) as f:
+                    cache[sid] = read_label_lines(f.readlines())
+            lab = cache[sid]
+            hit = np.nonzero((lab["boxes3d"] == boxes[k]).all(axis=1))[0]
+            if len(hit) == 0:
+                raise ValueError("AugSceneGenerator: no label of frame %06d has the box of database object %d" % (sid, k))
+            trunc[k], occl[k] = lab["truncation"][hit[0]], lab["occlusion"][hit[0]]
+        return trunc, occl
+
+    def _read_frame(self, fid):
+        with open(os.path.join(self.base, "label_2", "%06d.txt" % fid)) as f:
+            lines = [ln for ln in f.readlines() if ln.strip()]
+        lab = read_label_lines(lines)
+        with open(os.path.join(self.base, "planes", "%06d.txt" % fid)) as f:
+            plane = road_plane_from_lines(f.readlines())
+        return {"id": fid, "scan": get_lidar(os.path.join(self.base, "velodyne", "%06d.bin" % fid)),
+                "calib": Calibration(os.path.join(self.base, "calib", "%06d.txt" % fid)),
+                "img_shape": get_image_shape(os.path.join(self.base, "image_2", "%06d.png" % fid)), "plane": plane,
+                "all_gt": lab["boxes3d"][lab["cls_type"] != "DontCare"],                             # filtrate_dc_objects :89-96
+                "kept_lines": [ln for ln, c in zip(lines, lab["cls_type"]) if c in self.whitelist]}   # filtrate_objects :98-111
+
+    def _host_batch(self, batch, base_id, seed):
+        db = self.db
+        dbb, dbn, dbo = db.boxes.cpu().numpy(), db.npts.cpu().numpy(), db.offsets.cpu().numpy()
+        dbp, dbi = db.points.cpu().numpy(), db.intensity.cpu().numpy()
+        out = []
+        for fr in batch:
+            s = aug_scene_sample_host(fr["all_gt"], fr["plane"], dbb, dbn, self.scope, seed, base_id + fr["id"], self.iou3d)
+            use = s["status"] != 1
+            cloud, _ = aug_scene_build_host(fr["scan"], fr["calib"], fr["img_shape"], self.scope, s["boxes"] if use else s["boxes"][:0],
+                                            s["ids"] if use else [], s["y_shift"], dbp, dbi, dbo)
+            out.append((s["status"], s["ids"], s["boxes"], cloud))
+        return out
+
+    def _device_batch(self, batch, base_id, seed):
+        from . import ops
+        dev, db, B = self.device, self.db, len(batch)
+        packed = pack_scans([fr["scan"] for fr in batch], [fr["calib"] for fr in batch], [fr["img_shape"] for fr in batch])
+        G = max(max(len(fr["all_gt"]) for fr in batch), 1)
+        gt = np.zeros((B, G, 7), np.float32)
+        for k, fr in enumerate(batch):
+            gt[k, :len(fr["all_gt"])] = fr["all_gt"]
+        T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
+        acc = ops.aug_scene_sample(T(gt), T(np.array([len(fr["all_gt"]) for fr in batch], np.int32)),
+                                   T(np.stack([fr["plane"] for fr in batch]).astype(np.float64)),
+                                   T(np.array([base_id + fr["id"] for fr in batch], np.int32)), db.boxes, db.npts, self.scope, seed)
+        rows, off, cloud, _ = ops.aug_scene_build(packed["raw"].to(dev), packed["offsets"].to(dev), packed["max_points"], packed["calib"].to(dev),
+                                                  packed["img_hw"].to(dev), self.scope, acc, db.points, db.intensity, db.offsets)
+        status, count, ids, boxes = (acc[k].cpu().numpy() for k in ("status", "count", "db_id", "boxes3d"))
+        off, cloud = off.cpu().numpy(), cloud.cpu().numpy()
+        return [(int(status[k]), ids[k, :count[k]], boxes[k, :count[k]], cloud[off[k]:off[k + 1]]) for k in range(B)]
+
+    def generate(self, save_dir, aug_times=4, seed=0, frames_per_batch=8, image_sets_dir=None):
+        """generate_aug_scene (:285-305): <save_dir>/rectified_data/%06d.bin (float32 (n,4) rect x y z intensity) and
+        <save_dir>/aug_label/%06d.txt (the frame's kept labels re-printed, then one line per accepted object) for the new ids
+        (epoch + 1) * 10000 + sample_id, and <save_dir>/<split>_aug.txt: the original ids, then the new ones, no trailing newline
+        (copied to image_sets_dir when given).  The new id keys the random table, so the epochs of one frame differ.
+        -> one dict per written frame: sample_id (the new id), status, count.  A status-1 frame (fewer than two database objects, or a
+        try that reaches the collision test with no label to test against) is written unaugmented and reported here; the reference
+        would crash there."""
+        data_dir, label_dir = os.path.join(save_dir, "rectified_data"), os.path.join(save_dir, "aug_label")
+        os.makedirs(data_dir, exist_ok=True)
+        os.makedirs(label_dir, exist_ok=True)
+        split_list, report = list(self.frames), []
+        run = self._host_batch if self.backend == "host" else self._device_batch
+        for epoch in range(int(aug_times)):
+            base_id, batch = (epoch + 1) * 10000, []
+
+            def flush():
+                for fr, (status, ids, boxes, cloud) in zip(batch, run(batch, base_id, int(seed)) if batch else []):
+                    new_id = base_id + fr["id"]
+                    np.ascontiguousarray(cloud, np.float32).tofile(os.path.join(data_dir, "%06d.bin" % new_id))
+                    lines = [reprint_label_line(ln) for ln in fr["kept_lines"]]
+                    if status != 1 and len(ids):
+                        lines += aug_object_lines(boxes, self.truncation[ids], self.occlusion[ids], fr["calib"].P2, fr["img_shape"], self.class_name)
+                    with open(os.path.join(label_dir, "%06d.txt" % new_id), "w") as f:
+                        f.write("".join(ln + "\n" for ln in lines))
+                    split_list.append("%06d" % new_id)
+                    report.append({"sample_id": new_id, "status": int(status), "count": int(len(ids)) if status != 1 else 0})
+                batch.clear()
+            for fid in self.frames:
+                fr = self._read_frame(int(fid))
+                if self.class_name != "Car" and not fr["kept_lines"]:       # :259-260
+                    continue
+                batch.append(fr)
+                if len(batch) >= max(1, int(frames_per_batch)):
+                    flush()
+            flush()
+        split_file = os.path.join(save_dir, "%s_aug.txt" % self.split)
+        with open(split_file, "w") as f:
+            f.write("\n".join(split_list))
+        if image_sets_dir is not None:
+            os.makedirs(image_sets_dir, exist_ok=True)
+            with open(os.path.join(image_sets_dir, "%s_aug.txt" % self.split), "w") as f:
+                f.write("\n".join(split_list))
+        return report
+
+
+def load_aug_frame(root_dir, aug_root, sample_id):
+    """One frame of the train_aug split as kitti_dataset.py / kitti_rcnn_dataset.py read it: id < 10000 the original files (velodyne
+    scan in lidar coordinates), id >= 10000 <aug_root>/rectified_data/%06d.bin (rect coordinates already) and <aug_root>/aug_label/%06d.txt,
+    with the calibration, image shape and road plane of id % 10000.  -> dict sample_id, pts (n,4) f32, rect_input, label_lines, calib
+    (its packed() row carries the identity lidar -> rect for a rect_input frame: ScenePreparer / TrainScenePreparer take the frame as it
+    is), img_shape, plane (None without a planes folder)"""
+    sample_id = int(sample_id)
+    base = os.path.join(root_dir, "KITTI", "object", "training")
+    src = sample_id % 10000
+    aug = sample_id >= 10000
+    calib = Calibration(os.path.join(base, "calib", "%06d.txt" % src))
+    calib.rect_input = aug
+    pts_file = os.path.join(aug_root, "rectified_data", "%06d.bin" % sample_id) if aug else os.path.join(base, "velodyne", "%06d.bin" % src)
+    label_file = os.path.join(aug_root, "aug_label", "%06d.txt" % sample_id) if aug else os.path.join(base, "label_2", "%06d.txt" % src)
+    with open(label_file) as f:
+        lines = [ln for ln in f.readlines() if ln.strip()]
+    plane_file, plane = os.path.join(base, "planes", "%06d.txt" % src), None
+    if os.path.isfile(plane_file):
+        with open(plane_file) as f:
+            plane = road_plane_from_lines(f.readlines())
+    return {"sample_id": sample_id, "pts": get_lidar(pts_file), "rect_input": aug, "label_lines": lines, "calib": calib,
+            "img_shape": get_image_shape(os.path.join(base, "image_2", "%06d.png" % src)), "plane": plane}

@@ -134,6 +134,32 @@ def gt_database_row(dev, B=8, n_raw=120000, nbox=8):
          bytes=2 * raw.numel() * 4 + P * 20 + B * nbox * 4, kernels=[("gtdb_kernel", 0), ("gtdb_scan_kernel", 0)])
 
 
+def aug_scene_row(dev, B=8, n_raw=120000, G=12, D=2000):
+    """The offline GT-augmented scenes (kitti_input.AugSceneGenerator's device pass) at one KITTI-sized batch: the sampling loop, then
+    count, scan, the host read of the total, fill, paste.  Traffic floor of the builder: the raw scans read twice plus the rows written."""
+    import numpy as np
+    from . import kitti_input
+    r = np.random.default_rng(27)
+    calib = kitti_input.Calibration.from_text(kitti_input.KITTI_CALIB_TXT)
+    box = lambda n: (r.random((n, 7)) * [60., .8, 60., .3, .3, 1., 6.28] + [-30., 1.2, 5., 1.4, 1.5, 3.4, -3.14]).astype(np.float32)   # noqa: E731
+    dbb, npd = box(D), r.integers(5, 400, D)
+    gdb = kitti_input.GTDatabase.from_arrays(dbb, np.zeros(D, np.float32), [r.random((int(n), 3)).astype(np.float32) + dbb[i, :3] for i, n in enumerate(npd)],
+                                             [r.random(int(n)).astype(np.float32) for n in npd], hard_ratio=0.0, device=dev)
+    pk = kitti_input.pack_scans([kitti_input.synthetic_scan(n_raw, seed=400 + b) for b in range(B)], [calib] * B, [(375, 1242)] * B, pin=False)
+    raw, off, cal, hw = (pk[k].to(dev) for k in ("raw", "offsets", "calib", "img_hw"))
+    gt = torch.from_numpy(np.stack([box(G) for _ in range(B)])).to(dev)
+    planes = torch.tensor([[0.0, -1.0, 0.0, 1.65]] * B, dtype=torch.float64, device=dev)
+    ids = torch.arange(10000, 10000 + B, dtype=torch.int32, device=dev)
+    scope = kitti_input.aug_scene_scope("Car")
+    sample = lambda: ops.aug_scene_sample(gt, None, planes, ids, gdb.boxes, gdb.npts, scope, 5)      # noqa: E731
+    acc = sample()
+    emit("aug_scene_sample", "B%d G%d D%d (%d objects accepted)" % (B, G, D, int(acc["count"].sum())), timeit(sample), kernels=[("augs_sample_kernel", 0)])
+    build = lambda: ops.aug_scene_build(raw, off, pk["max_points"], cal, hw, scope, acc, gdb.points, gdb.intensity, gdb.offsets)      # noqa: E731
+    rows = build()[2].shape[0]
+    emit("aug_scene_build", "B%d x %d raw points (%d rows out; includes the host read of the total)" % (B, n_raw, rows), timeit(build),
+         bytes=2 * raw.numel() * 4 + rows * 20, kernels=[("augs_tile_kernel", 0), ("augs_scan_kernel", 0), ("augs_paste_kernel", 0)])
+
+
 def rpn_loss_rows(dev, B=16, N=16384, rounds=5):
     """`rpn_loss fwd+bwd`: train_functions.get_rpn_loss + backward at the training step's shape (bs16 x 16 384 points, C = 76, about
     3 % foreground and 10 % ignored), composed torch against the fused device passes, alternated in one process; per route the median
@@ -452,6 +478,9 @@ def main():
 
     # ---- the GT-augmentation database from raw scans and labels (kitti_input.GTDatabase.from_kitti)
     gt_database_row(dev)
+
+    # ---- the offline GT-augmented scenes, the train_aug split (kitti_input.AugSceneGenerator)
+    aug_scene_row(dev)
 
     # ---- the RPN training loss and its gradient: composed torch against the one-pass kernels (csrc/rpn_loss.hip)
     rpn_loss_rows(dev)

@@ -1450,6 +1450,89 @@ def gt_database_build(raw, offsets, max_points_per_frame, calib, boxes3d, num_bo
 
 
 # ---------------------------------------------------------------------------------------------------------
+# Offline GT-augmented scenes, the train_aug split (csrc/aug_scene.hip)
+# ---------------------------------------------------------------------------------------------------------
+AUG_SCENE_MAX_ACCEPT = 15            # cnt <= extra_gt_num + 1 <= 15 (csrc/aug_scene_math.h)
+
+
+def aug_scene_sample(gt_boxes3d, num_gt, planes, frame_ids, db_boxes, db_npts, area_scope, seed=0, max_accept=AUG_SCENE_MAX_ACCEPT):
+    """The sampling loop of AugSceneGenerator.aug_one_scene (tools/generate_aug_scene.py:157-219) for a batch, one launch.
+    gt_boxes3d (B,G,7) non-DontCare labels, num_gt (B) i32 or None, planes (B,4) f64, frame_ids (B) i32 the new sample ids
+    ((epoch + 1) * 10000 + sample_id: the key of the random table), db_boxes (D,7), db_npts (D) i32, area_scope 6 floats.
+    -> dict: count (B) i32, db_id (B,K) i32 (-1 past count), boxes3d (B,K,7) placed and unenlarged, y_shift (B,K) f64, stats (B,3) i32
+    (extra_gt_num, cnt, tries spent), status (B) i32: 0 ok, 1 the reference raises, 2 a bound was exceeded (include/prcnn_pointops.h)"""
+    _chk(gt_boxes3d, "gt_boxes3d", ndim=3); _chk(planes, "planes", torch.float64, 2); _chk(frame_ids, "frame_ids", _INT, 1)
+    _chk(db_boxes, "db_boxes", ndim=2); _chk(db_npts, "db_npts", _INT, 1)
+    B, G, C = gt_boxes3d.shape
+    D, K = db_boxes.shape[0], int(max_accept)
+    if C != 7 or tuple(planes.shape) != (B, 4) or frame_ids.shape[0] != B:
+        raise ValueError("aug_scene_sample: gt_boxes3d must be (B, G, 7), planes (B, 4), frame_ids (B,)")
+    if db_boxes.shape[1] != 7 or db_npts.shape[0] != D:
+        raise ValueError("aug_scene_sample: db_boxes (D, 7) and db_npts (D,) disagree")
+    if num_gt is not None:
+        _chk(num_gt, "num_gt", _INT, 1)
+        if num_gt.shape[0] != B:
+            raise ValueError("aug_scene_sample: num_gt must be (%d,)" % B)
+    dev = gt_boxes3d.device
+    for name, t in (("num_gt", num_gt), ("planes", planes), ("frame_ids", frame_ids), ("db_boxes", db_boxes), ("db_npts", db_npts)):
+        if t is not None and t.device != dev:
+            raise RuntimeError("aug_scene_sample: %s is on %s, gt_boxes3d on %s" % (name, t.device, dev))
+    if area_scope is None or len(area_scope) != 6:
+        raise ValueError("aug_scene_sample: area_scope must be 6 floats [x0 x1 y0 y1 z0 z1]")
+    out = {"count": torch.empty((B,), dtype=_INT, device=dev), "db_id": torch.empty((B, max(K, 0)), dtype=_INT, device=dev),
+           "boxes3d": torch.empty((B, max(K, 0), 7), dtype=_F32, device=dev),
+           "y_shift": torch.empty((B, max(K, 0)), dtype=torch.float64, device=dev),
+           "stats": torch.empty((B, 3), dtype=_INT, device=dev), "status": torch.empty((B,), dtype=_INT, device=dev)}
+    _cabi.check(_cabi.lib().prcnn_aug_scene_sample(
+        _p(gt_boxes3d), _p(num_gt), _p(planes), _p(frame_ids), B, G, _p(db_boxes), _p(db_npts), D, ctypes.cast(_scope(area_scope), ctypes.c_void_p),
+        K, int(seed) & 0xFFFFFFFF, _p(out["count"]), _p(out["db_id"]), _p(out["boxes3d"]), _p(out["y_shift"]), _p(out["stats"]),
+        _p(out["status"]), _stream()), "prcnn_aug_scene_sample")
+    return out
+
+
+def aug_scene_build(raw, offsets, max_points_per_frame, calib, img_hw, scope, accepted, db_points, db_intensity, db_offsets, guard_rows=0):
+    """The augmented clouds of AugSceneGenerator.aug_one_epoch_scene (tools/generate_aug_scene.py:240-248, :205-231) for a batch.
+    raw .. scope as scene_prepare; accepted = aug_scene_sample's dict; db_points (P,3), db_intensity (P), db_offsets (D+1) i64.
+    -> rows (B) i32, offsets (B+1) i64 (their exclusive scan), out (total,4) [x y z intensity], src (total) i32: per frame the valid
+    points outside every accepted box (h + 2) in raw order (src = raw index), then the accepted objects' points with y - y_shift
+    (src = -1 - database row).  One host read (the total) between the two passes.  guard_rows: extra rows allocated behind the
+    output, which the fill must leave alone (tests)."""
+    B, total, dev = _frames(raw, offsets, calib, img_hw)
+    cnt, ids, boxes = _chk(accepted["count"], "count", _INT, 1), _chk(accepted["db_id"], "db_id", _INT, 2), _chk(accepted["boxes3d"], "boxes3d", ndim=3)
+    shift, status = _chk(accepted["y_shift"], "y_shift", torch.float64, 2), _chk(accepted["status"], "status", _INT, 1)
+    K = ids.shape[1]
+    if cnt.shape[0] != B or ids.shape[0] != B or tuple(boxes.shape) != (B, K, 7) or tuple(shift.shape) != (B, K) or status.shape[0] != B:
+        raise ValueError("aug_scene_build: the accepted objects must describe %d frames" % B)
+    _chk(db_points, "db_points", ndim=2); _chk(db_intensity, "db_intensity", ndim=1)
+    if db_offsets.dtype != torch.int64 or not db_offsets.is_contiguous() or db_offsets.device != dev or db_offsets.dim() != 1 or db_offsets.shape[0] < 1:
+        raise ValueError("aug_scene_build: db_offsets must be a contiguous (D+1,) int64 tensor on the device of raw")
+    if db_points.shape[1] != 3 or db_intensity.shape[0] != db_points.shape[0]:
+        raise ValueError("aug_scene_build: db_points (P, 3) needs one intensity per point")
+    D, PT = db_offsets.shape[0] - 1, db_points.shape[0]
+    L = _cabi.lib()
+    mp = int(max_points_per_frame)
+    ws = torch.empty((int(L.prcnn_aug_scene_workspace_bytes(mp, B)),), dtype=torch.uint8, device=dev)
+    rows = torch.empty((B,), dtype=_INT, device=dev)
+    sc = _scope(scope)
+    _cabi.check(L.prcnn_aug_scene_count(_p(raw), _p(offsets), B, total, mp, _p(calib), _p(img_hw), sc, _p(cnt), _p(ids), _p(boxes), _p(status), K,
+                                        _p(db_offsets), D, PT, _p(rows), _p(ws), ws.numel(), _stream()), "prcnn_aug_scene_count")
+    off = torch.zeros((B + 1,), dtype=torch.int64, device=dev)
+    off[1:] = torch.cumsum(rows, 0, dtype=torch.int64)
+    if B and int(rows.min()) < 0:                       # host read
+        raise RuntimeError("aug_scene_build: a frame holds more rows than an int32 counts")
+    n = int(off[-1])                                    # the outputs are sized by the data
+    out = torch.empty((n + int(guard_rows), 4), dtype=_F32, device=dev)
+    src = torch.empty((n + int(guard_rows),), dtype=_INT, device=dev)
+    if guard_rows:
+        out[n:] = -12345.0
+        src[n:] = -12345
+    _cabi.check(L.prcnn_aug_scene_fill(_p(raw), _p(offsets), B, total, mp, _p(calib), _p(img_hw), sc, _p(cnt), _p(ids), _p(boxes), _p(shift),
+                                       _p(status), K, _p(db_points), _p(db_intensity), _p(db_offsets), D, PT, _p(off), n, _p(out), _p(src),
+                                       _p(ws), ws.numel(), _stream()), "prcnn_aug_scene_fill")
+    return rows, off, out, src
+
+
+# ---------------------------------------------------------------------------------------------------------
 # Evaluation statistics (csrc/eval_stats.hip)
 # ---------------------------------------------------------------------------------------------------------
 EVAL_STATS_MAX_GT = 128
