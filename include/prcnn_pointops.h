@@ -58,6 +58,7 @@ typedef void* prcnn_stream_t; /* hipStream_t */
 #define PRCNN_EUNSUPPORTED (-3) /* valid request this build has no kernel for */
 
 int prcnn_abi_version(void);   /* 12: + prcnn_switches_reload, prcnn_switch_get (the PRCNN_* kernel switches are read once, through one table);
+                                 * still 12 (additive): + prcnn_kitti_result_text (the KITTI result files' text formatted on the device);
                                  * still 12 (additive): + prcnn_aug_scene_sample, prcnn_aug_scene_workspace_bytes, prcnn_aug_scene_count,
                                  * prcnn_aug_scene_fill (the offline GT-augmented scenes, the train_aug split, generated on the device);
                                  * still 12 (additive): + prcnn_optim_chunk_elems, prcnn_optim_grad_norm, prcnn_optim_step (the adam_onecycle
@@ -1029,6 +1030,27 @@ int prcnn_optim_grad_norm(const prcnn_optim_tensor_t* tensors, const prcnn_optim
 int prcnn_optim_step(const prcnn_optim_tensor_t* tensors, const prcnn_optim_chunk_t* chunks, int64_t num_chunks, const double* partial,
                      float max_norm, const float* coef, float* state, float decay, float one_minus_beta1, float beta2,
                      float one_minus_beta2, float bias2_sqrt, float eps, float neg_step, prcnn_stream_t stream);
+
+/* ======================================================================================================
+ * KITTI result files formatted on the device (csrc/kitti_text.hip, per-box arithmetic and the "%.4f" conversion:
+ * csrc/kitti_text_math.h; pointrcnn_amd/kitti_output.py DeviceResultWriter) -- tools/eval_rcnn.py:69-94 save_kitti_format for a
+ * whole batch in one launch.  boxes (B,M,7) f32 [x, y, z, h, w, l, ry], scores (B,M) f32; candidate j < num[b] of frame b is box
+ * keep[b,j] (keep null: box j; num null: all M); P2 (B,12) f64 the 3x4 projections row-major, img_hw (B,2) i32 [H, W];
+ * class_name 1..15 bytes.  Per candidate: float32 corners (ref_trig cosf / sinf), float64 projection, min / max over the corners
+ * with numpy's NaN rule, clip to the image, kept iff (x2-x1) < W*0.8 and (y2-y1) < H*0.8; alpha in float32 from ref_trig atan2f.
+ *   text     (B, M * PRCNN_KITTI_LINE_MAX) u8: the kept candidates' lines "<class> -1 -1" + 13 x " %.4f" + "\n" [alpha, x1 y1 x2 y2,
+ *            h w l, x y z, ry, score] in j order, packed from offset 0; text_len (B) i32 their bytes.  The digits are printf's:
+ *            the exact binary value rounded to four decimals, ties to even, "-" whenever the sign bit is set.
+ *   status   (B) i32: 0; 1 = a printed field of a kept box is not finite or not below 2^31 in magnitude (format the frame on the
+ *            host); 2 = num[b] outside [0, M] or a keep index outside [0, M) (nothing is read through it).  status != 0 comes with
+ *            text_len 0, and the frame's text bytes then mean nothing.
+ *   rows     (B,M,13) f64 | null: the 13 values of candidate j; valid (B,M) u8 | null: the size test's flag.  Zeros past num.
+ * One launch, one workgroup per frame, no workspace, no host synchronisation, no allocation.  B == 0 or M == 0: nothing to do.
+ * ====================================================================================================== */
+#define PRCNN_KITTI_LINE_MAX 256
+int prcnn_kitti_result_text(const float* boxes, const float* scores, const int32_t* keep, const int32_t* num, int B, int M,
+                            const double* P2, const int32_t* img_hw, const char* class_name, uint8_t* text, int32_t* text_len,
+                            int32_t* status, double* rows, uint8_t* valid, prcnn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -85,6 +85,114 @@ def write_detections(pred_boxes3d, raw_scores, keep, num, sample_ids, calibs, im
     return out
 
 
+# ---- the same files with the text formatted on the device (csrc/kitti_text.hip) ----
+class ResultTextHandle:
+    """one formatted batch in flight: the pinned buffers its text is copied into, the event that says they are filled, and what the
+    host route needs for a frame the device declined (status 1)"""
+
+    def __init__(self, slot, B, M, event, class_name, calibs, img_shapes, tensors):
+        self.slot, self.B, self.M, self.event, self.class_name = slot, B, M, event, class_name
+        self.calibs, self.img_shapes, self.tensors = calibs, img_shapes, tensors
+
+
+class DeviceResultWriter:
+    """write_detections with the lines formatted by prcnn_kitti_result_text: `format` launches the kernel on the current stream and
+    queues the copy of text / text_len / status / num into pinned host buffers; `write` (or `lines`) waits for that copy alone and
+    moves bytes into files.  A caller formats batch i, then writes batch i - 1: the host never waits for the detector.  `depth`
+    buffer sets are reused in turn (a set still in flight is waited for before it is reused).  The digits are those of kitti_lines
+    up to the host libm's float trigonometry against numpy's (csrc/kitti_text_math.h); a frame holding a value the device
+    formatter does not print (status 1: not finite, or 2^31 and above) is formatted by kitti_lines on the host."""
+
+    def __init__(self, device="cuda:0", depth=2):
+        import torch
+        self._torch, self.device, self.depth = torch, torch.device(device), int(depth)
+        self._sets, self._turn = {}, 0
+
+    def _set(self, B, M):
+        from . import ops
+        torch = self._torch
+        key = (B, M, self._turn % self.depth)
+        self._turn += 1
+        s = self._sets.get(key)
+        if s is None:
+            W = M * ops.KITTI_LINE_MAX
+            dev = dict(text=torch.empty((B, W), dtype=torch.uint8, device=self.device),
+                       ints=torch.zeros((3, B), dtype=torch.int32, device=self.device),              # text_len, status, num
+                       P2=torch.empty((B, 12), dtype=torch.float64, device=self.device),
+                       hw=torch.empty((B, 2), dtype=torch.int32, device=self.device))
+            host = {k: torch.empty(v.shape, dtype=v.dtype, pin_memory=True) for k, v in dev.items()}
+            s = self._sets[key] = dict(dev=dev, host=host, event=None)
+        elif s["event"] is not None:
+            s["event"].synchronize()                   # the set's previous batch: its copies must be over before the buffers change
+        return s
+
+    def format(self, boxes, scores, keep, num, calibs, img_shapes, class_name="Car"):
+        """boxes (B,M,7) f32, scores (B,M) f32, keep (B,M) i32 | None, num (B) i32 | None on the device (PointRCNN.detections);
+        calibs: B objects with a (3,4) P2; img_shapes: B (H, W, ...).  -> the handle `write` / `lines` take.  No synchronisation."""
+        from . import ops
+        torch = self._torch
+        B, M = int(boxes.shape[0]), int(boxes.shape[1])
+        if len(calibs) != B or len(img_shapes) != B:
+            raise ValueError("DeviceResultWriter.format: %d frames, %d calibrations, %d image shapes" % (B, len(calibs), len(img_shapes)))
+        s = self._set(B, M)
+        dev, host = s["dev"], s["host"]
+        host["P2"].numpy()[:] = np.stack([np.asarray(c.P2, np.float64).reshape(12) for c in calibs]) if B else 0
+        host["hw"].numpy()[:] = np.array([[int(sh[0]), int(sh[1])] for sh in img_shapes], np.int32).reshape(B, 2)
+        dev["P2"].copy_(host["P2"], non_blocking=True)
+        dev["hw"].copy_(host["hw"], non_blocking=True)
+        boxes, scores = boxes.contiguous(), scores.contiguous()
+        keep = None if keep is None else keep.contiguous()
+        num = None if num is None else num.contiguous()
+        ops.kitti_result_text(boxes, scores, dev["P2"], dev["hw"], keep=keep, num=num, class_name=class_name,
+                              out=(dev["text"], dev["ints"][0], dev["ints"][1]))
+        if num is None:
+            dev["ints"][2].fill_(M)
+        else:
+            dev["ints"][2].copy_(num)
+        host["text"].copy_(dev["text"], non_blocking=True)
+        host["ints"].copy_(dev["ints"], non_blocking=True)
+        s["event"] = torch.cuda.Event()
+        s["event"].record()
+        return ResultTextHandle(s, B, M, s["event"], class_name, list(calibs), list(img_shapes), (boxes, scores, keep))
+
+    def _host_frame(self, h, b, n):
+        """status 1: the frame through kitti_lines"""
+        boxes, scores, keep = h.tensors
+        k = np.arange(n) if keep is None else keep[b, :n].cpu().numpy().astype(np.int64)
+        lines = kitti_lines(boxes[b].cpu().numpy()[k], scores[b].cpu().numpy()[k], h.calibs[b].P2, h.img_shapes[b], h.class_name)
+        return "".join(ln + "\n" for ln in lines).encode()
+
+    def lines(self, handle):
+        """-> the B frames' text as byte strings (complete lines, each ending in a newline).  Waits for the handle's copy."""
+        if handle.slot["event"] is not handle.event:
+            raise RuntimeError("DeviceResultWriter: this handle's buffers hold a later batch (more than `depth` batches in flight)")
+        handle.event.synchronize()
+        host = handle.slot["host"]
+        text, (text_len, status, num) = host["text"].numpy(), host["ints"].numpy()
+        out = []
+        for b in range(handle.B):
+            if status[b] == 2:
+                raise ValueError("DeviceResultWriter: frame %d has num = %d outside [0, %d] or a keep index outside the frame"
+                                 % (b, int(num[b]), handle.M))
+            out.append(self._host_frame(handle, b, int(num[b])) if status[b] == 1 else text[b, :int(text_len[b])].tobytes())
+        return out
+
+    def write(self, handle, sample_ids, kitti_output_dir, skip_empty=False):
+        """<dir>/<sample_id %06d>.txt per frame; skip_empty: no file for a frame whose num is 0 (eval_rcnn.py:607-610: the joint loop
+        leaves those to the empty-file dump).  -> the per-frame byte strings"""
+        if len(sample_ids) != handle.B:
+            raise ValueError("DeviceResultWriter.write: %d frames, %d sample ids" % (handle.B, len(sample_ids)))
+        out = self.lines(handle)
+        num = handle.slot["host"]["ints"].numpy()[2]
+        os.makedirs(kitti_output_dir, exist_ok=True)
+        for b, blob in enumerate(out):
+            if skip_empty and num[b] == 0:
+                continue
+            with open(os.path.join(kitti_output_dir, "%06d.txt" % int(sample_ids[b])), "wb") as f:
+                f.write(blob)
+        return out
+
+
 # ---- RPN feature dumps (the on-disk hand-over between `eval_rcnn.py --save_rpn_feature` and `--train_mode rcnn` / `rcnn_offline`) ----
 _FEATURE_SUFFIX = {"features": "", "xyz": "_xyz", "seg": "_seg", "intensity": "_intensity", "rawscore": "_rawscore"}
 

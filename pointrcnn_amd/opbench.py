@@ -19,7 +19,9 @@ Algorithmic work per unit follows SURVEY.md 8(d).
 """
 import argparse
 import json
+import os
 
+import numpy as np
 import torch
 
 from . import ops, rpn
@@ -364,12 +366,128 @@ def eval_stats_rows(dev, B=32, shapes=((100, 12), (512, 24)), N=16384, rounds=5)
                               "launches_per_update": 2 if route == "device" else None}), flush=True)
 
 
+class _P2:
+    """KITTI training frame 000000's camera matrix: what a calibration object carries for the result writers"""
+    P2 = np.array([[721.5377, 0, 609.5593, 44.85728], [0, 721.5377, 172.854, 0.2163791], [0, 0, 1, 0.002745884]], np.float32)
+
+
+def _kitti_like_detections(B, M, g):
+    """boxes in front of the camera as a detector emits them (a few very close or off to the side: clipped, some dropped by the
+    0.8-of-the-image test), scores, a shuffled keep list and per-frame counts"""
+    span = torch.tensor([50., 1.4, 68., .76, .81, 1.94, 6.28])
+    base = torch.tensor([-25., .8, 2., 1.22, 1.30, 3.11, -3.14])
+    boxes = torch.rand(B, M, 7, generator=g) * span + base
+    boxes[:, :4, 2] = torch.rand(B, 4, generator=g) * 1.8 + 1.2
+    scores = torch.randn(B, M, generator=g) * 3
+    keep = torch.stack([torch.randperm(M, generator=g) for _ in range(B)]).to(torch.int32)
+    num = torch.randint(M // 2, M + 1, (B,), generator=g, dtype=torch.int32)
+    return boxes, scores, keep, num
+
+
+def _tmpfs_dir():
+    import tempfile
+    return tempfile.mkdtemp(prefix="prcnn_opbench_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
+
+
+def result_writer_rows(dev, B=32, Ms=(100, 512), rounds=5, iters=5):
+    """`result_writer`: one batch of detections -> one KITTI result file per frame, at bs32 x 100 and bs32 x 512 boxes, files on a
+    memory-backed path.  Host route: kitti_output.write_detections (four device-to-host copies, then numpy and a Python `%` per line).
+    Device route: DeviceResultWriter.format + write (one launch, the text's copy, bytes into files).  Both are timed on the host
+    clock from a drained device, back to back (the device route's wait for its own kernel and copy is inside its time), alternated in
+    one process; the kernel alone is timed with HIP events.  The device route must be the faster one in every round."""
+    import shutil
+    import time
+    from . import kitti_output
+    g = torch.Generator().manual_seed(33)
+    for M in Ms:
+        boxes, scores, keep, num = (t.to(dev).contiguous() for t in _kitti_like_detections(B, M, g))
+        calibs, shapes, ids = [_P2] * B, [(375, 1242, 3)] * B, list(range(B))
+        writer = kitti_output.DeviceResultWriter(dev)
+        dirs = {"host": _tmpfs_dir(), "device": _tmpfs_dir()}
+
+        def host():
+            kitti_output.write_detections(boxes, scores, keep, num, ids, calibs, shapes, dirs["host"])
+
+        def device():
+            writer.write(writer.format(boxes, scores, keep, num, calibs, shapes), ids, dirs["device"])
+
+        def window(fn):
+            fn()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(iters):
+                fn()
+            return (time.perf_counter() - t0) / iters
+        times = {"host": [], "device": []}
+        try:
+            for _ in range(rounds):
+                times["host"].append(window(host))
+                times["device"].append(window(device))
+            lines = sum(open("%s/%06d.txt" % (dirs["device"], i)).read().count("\n") for i in ids)
+        finally:
+            for d in dirs.values():
+                shutil.rmtree(d, ignore_errors=True)
+        P2 = torch.from_numpy(_P2.P2).double().reshape(1, 12).repeat(B, 1).to(dev)
+        hw = torch.tensor([[375, 1242]] * B, dtype=torch.int32, device=dev)
+        out = ops.kitti_result_text(boxes, scores, P2, hw, keep=keep, num=num)
+        kernel = timeit(lambda: ops.kitti_result_text(boxes, scores, P2, hw, keep=keep, num=num, out=out))
+        faster = all(d < h for d, h in zip(times["device"], times["host"]))
+        for route in ("host", "device"):
+            t = sorted(times[route])
+            print(json.dumps({"op": "result_writer (%s)" % route, "shape": "B%d M%d, %d lines" % (B, M, lines),
+                              "median_ms_per_batch": round(t[len(t) // 2] * 1e3, 3), "min_ms": round(t[0] * 1e3, 3), "max_ms": round(t[-1] * 1e3, 3),
+                              "rounds_ms": [round(x * 1e3, 3) for x in times[route]],
+                              "kernel_us": round(kernel * 1e6, 1) if route == "device" else None,
+                              "device_faster_in_every_round": faster}), flush=True)
+        if not faster:
+            raise AssertionError("result_writer: the device route was not faster than the host route in every round at M=%d: %s" % (M, times))
+
+
+def eval_loop_rows(dev, B=16, nbatches=3, rounds=5):
+    """`eval_loop`: eval_one_epoch_joint over synthetic scenes (randomly initialised detector) in frames per second, with the host
+    result writer (writer=None) and with the device writer, alternated in one process.  No bar attached."""
+    import shutil
+    import time
+    from . import eval_stats, kitti_output
+    from .point_rcnn import PointRCNN
+    torch.manual_seed(0)
+    model = rpn.randomize_bn_stats(PointRCNN(mode="TEST")).to(dev).eval()
+    pts = rpn.synthetic_clouds(B * nbatches, 16384, device=dev)
+    batches = [{"sample_id": list(range(k * B, (k + 1) * B)), "pts_input": pts[k * B:(k + 1) * B]} for k in range(nbatches)]
+    writer = kitti_output.DeviceResultWriter(dev)
+    times = {"host": [], "device": []}
+    out = _tmpfs_dir()
+    try:
+        for r in range(rounds + 1):                               # round 0 warms both routes up
+            for route, w in (("host", None), ("device", writer)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                eval_stats.eval_one_epoch_joint(model, batches, "%s/%s" % (out, route), lambda i: _P2, lambda i: (375, 1242, 3), writer=w)
+                torch.cuda.synchronize()
+                if r:
+                    times[route].append(time.perf_counter() - t0)
+        files = ["%s/device/final_result/data/%06d.txt" % (out, i) for i in range(B * nbatches)]
+        lines = sum(open(f).read().count("\n") for f in files if os.path.exists(f))
+    finally:
+        shutil.rmtree(out, ignore_errors=True)
+    for route in ("host", "device"):
+        fps = sorted(B * nbatches / t for t in times[route])
+        print(json.dumps({"op": "eval_loop joint (%s writer)" % route, "shape": "%d batches of %d frames, 16384 points, %d detections" % (nbatches, B, lines),
+                          "median_frames_per_s": round(fps[len(fps) // 2], 1), "min": round(fps[0], 1), "max": round(fps[-1], 1)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
-    ap.add_argument("--only", default=None, help="run one row family only: eval_stats | optimizer")
+    ap.add_argument("--only", default=None, help="run one row family only: eval_stats | optimizer | result_writer | eval_loop")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
+    if args.only == "result_writer":
+        result_writer_rows(dev)
+        return
+    if args.only == "eval_loop":
+        eval_loop_rows(dev)
+        return
     if args.only == "eval_stats":
         eval_stats_rows(dev)
         return
@@ -490,6 +608,10 @@ def main():
     optimizer_rows(dev)
     # ---- the evaluation statistics of a batch: the reference's per-frame loop on this library against the device passes (csrc/eval_stats.hip)
     eval_stats_rows(dev)
+    # ---- the result files of a batch: kitti_output.write_detections against the text formatted on the device (csrc/kitti_text.hip),
+    # and the joint evaluation loop with either writer
+    result_writer_rows(dev)
+    eval_loop_rows(dev)
 
     # ---- NMS (default RPN path: normal, 6300 boxes, thr 0.8) and rotated
     c = torch.rand(6300, 2, generator=g) * torch.tensor([80.0, 70.0])

@@ -1662,3 +1662,41 @@ def optim_step(tensors, chunks, scalars, partial=None, max_norm=1.0, coef=None, 
     _cabi.check(_cabi.lib().prcnn_optim_step(_p(tensors), _p(chunks), C, _p(partial), float(max_norm), _p(coef), _p(state),
                                              *[float(s) for s in scalars], _stream()), "prcnn_optim_step")
     return state
+
+
+# ------------------------------------------------------------------ KITTI result text (csrc/kitti_text.hip)
+KITTI_LINE_MAX = 256                     # PRCNN_KITTI_LINE_MAX: bytes reserved per candidate line
+KITTI_FIELDS = 13
+
+
+def kitti_result_text(boxes, scores, P2, img_hw, keep=None, num=None, class_name="Car", out=None, want_rows=False):
+    """the result-file text of a batch [tools/eval_rcnn.py:69-94 save_kitti_format]: boxes (B,M,7), scores (B,M), P2 (B,12) f64,
+    img_hw (B,2) i32 [H, W]; candidate j < num[b] is box keep[b,j] (keep None: box j; num None: all M).  out: (text, text_len, status)
+    to write into.  -> text (B, M * KITTI_LINE_MAX) u8, text_len (B) i32, status (B) i32 [, rows (B,M,13) f64, valid (B,M) u8 with
+    want_rows].  One launch, nothing read back."""
+    _chk(boxes, "boxes", ndim=3); _chk(scores, "scores", ndim=2)
+    B, M = boxes.shape[:2]
+    if boxes.shape[2] != 7 or tuple(scores.shape) != (B, M):
+        raise ValueError("kitti_result_text: boxes must be (B, M, 7) and scores (B, M), got %s and %s" % (tuple(boxes.shape), tuple(scores.shape)))
+    if tuple(_chk(P2, "P2", torch.float64, 2).shape) != (B, 12) or tuple(_chk(img_hw, "img_hw", _INT, 2).shape) != (B, 2):
+        raise ValueError("kitti_result_text: P2 must be (%d, 12) float64 and img_hw (%d, 2) int32" % (B, B))
+    if keep is not None and tuple(_chk(keep, "keep", _INT, 2).shape) != (B, M):
+        raise ValueError("kitti_result_text: keep must be (%d, %d)" % (B, M))
+    if num is not None and tuple(_chk(num, "num", _INT, 1).shape) != (B,):
+        raise ValueError("kitti_result_text: num must be (%d,)" % B)
+    name = class_name.encode()
+    dev = boxes.device
+    if out is None:
+        out = (torch.empty((B, M * KITTI_LINE_MAX), dtype=torch.uint8, device=dev), torch.zeros((B,), dtype=_INT, device=dev),
+               torch.zeros((B,), dtype=_INT, device=dev))
+    text, text_len, status = out
+    if tuple(_chk(text, "text", torch.uint8, 2).shape) != (B, M * KITTI_LINE_MAX) or tuple(_chk(text_len, "text_len", _INT, 1).shape) != (B,) \
+            or tuple(_chk(status, "status", _INT, 1).shape) != (B,):
+        raise ValueError("kitti_result_text: out must be text (%d, %d) u8, text_len (%d,) and status (%d,) i32" % (B, M * KITTI_LINE_MAX, B, B))
+    rows = valid = None
+    if want_rows:
+        rows = torch.zeros((B, M, KITTI_FIELDS), dtype=torch.float64, device=dev)
+        valid = torch.zeros((B, M), dtype=torch.uint8, device=dev)
+    _cabi.check(_cabi.lib().prcnn_kitti_result_text(_p(boxes), _p(scores), _p(keep), _p(num), B, M, _p(P2), _p(img_hw), name, _p(text),
+                                                    _p(text_len), _p(status), _p(rows), _p(valid), _stream()), "prcnn_kitti_result_text")
+    return (text, text_len, status, rows, valid) if want_rows else (text, text_len, status)
