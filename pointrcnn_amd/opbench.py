@@ -518,6 +518,20 @@ def main():
     emit("ball_query2", "B%d N%d M4096 r(.1,.5) ns(16,32)" % (B, N),
          timeit(lambda: ops.ball_query2(0.1, 16, 0.5, 32, xyz, new_xyz)), pairs=B * N * 4096)
     emit("three_nn", "B%d n%d m4096" % (B, N), timeit(lambda: ops.three_nn(xyz, new_xyz)), pairs=B * N * 4096)
+    # the short levels (scans of neighbor.hip; several lanes share a query): SA3 / SA4 ball query, FP2 / FP3 three_nn, and the RCNN
+    # stage's first query on 512-point RoI clouds
+    lv = [new_xyz]
+    for npoint in (1024, 256, 64):
+        lv.append(ops.gather_rows(lv[-1], ops.furthest_point_sample(lv[-1], npoint)))
+    emit("ball_query2 SA3", "B%d N1024 M256 r(1,2) ns(16,32)" % B, timeit(lambda: ops.ball_query2(1.0, 16, 2.0, 32, lv[1], lv[2])), pairs=B * 1024 * 256)
+    emit("ball_query2 SA4", "B%d N256 M64 r(2,4) ns(16,32)" % B, timeit(lambda: ops.ball_query2(2.0, 16, 4.0, 32, lv[2], lv[3])), pairs=B * 256 * 64)
+    emit("three_nn FP2", "B%d n1024 m256" % B, timeit(lambda: ops.three_nn(lv[1], lv[2], want_weight=True)), pairs=B * 1024 * 256)
+    emit("three_nn FP3", "B%d n256 m64" % B, timeit(lambda: ops.three_nn(lv[2], lv[3], want_weight=True)), pairs=B * 256 * 64)
+    R = 16 * B
+    roi_pts = (torch.rand(R, 512, 3, generator=g) * torch.tensor([2.0, 2.0, 4.5])).to(dev)
+    roi_ctr = ops.gather_rows(roi_pts, ops.furthest_point_sample(roi_pts, 128))
+    emit("ball_query RCNN SA1", "B%d N512 M128 r.2 ns64" % R, timeit(lambda: ops.ball_query(0.2, 64, roi_pts, roi_ctr)), pairs=R * 512 * 128)
+    del lv, roi_pts, roi_ctr
 
     # ---- gather-class ops in the op-surface (B,C,N) layout
     feat = torch.randn(B, 96, 4096, device=dev)
