@@ -63,6 +63,8 @@ int prcnn_abi_version(void);   /* 12: + prcnn_switches_reload, prcnn_switch_get 
                                  * prcnn_aug_scene_fill (the offline GT-augmented scenes, the train_aug split, generated on the device);
                                  * still 12 (additive): + prcnn_optim_chunk_elems, prcnn_optim_grad_norm, prcnn_optim_step (the adam_onecycle
                                  * parameter update: clip, decay and Adam over all tensors in two launches);
+                                 * still 12 (additive): + prcnn_optim_step_adam, prcnn_optim_step_sgd (TRAIN.OPTIMIZER adam and sgd on the
+                                 * same tables and launches);
                                  * still 12 (additive): + prcnn_eval_gt_max_iou, prcnn_eval_stats_accumulate, prcnn_eval_stats_workspace_bytes
                                  * (recall, segmentation IoU and RCNN accuracy of the evaluation loops counted on the device);
                                  * still 12 (additive): + prcnn_rcnn_offline_sample, prcnn_rcnn_offline_finish (RCNN offline training batches);
@@ -1030,6 +1032,21 @@ int prcnn_optim_grad_norm(const prcnn_optim_tensor_t* tensors, const prcnn_optim
 int prcnn_optim_step(const prcnn_optim_tensor_t* tensors, const prcnn_optim_chunk_t* chunks, int64_t num_chunks, const double* partial,
                      float max_norm, const float* coef, float* state, float decay, float one_minus_beta1, float beta2,
                      float one_minus_beta2, float bias2_sqrt, float eps, float neg_step, prcnn_stream_t stream);
+
+/* TRAIN.OPTIMIZER adam and sgd (pointrcnn_amd/optim.py ClipAdam / ClipSGD): the same tables, partial sums, coefficient and {norm, coef}
+ * state as prcnn_optim_step, after the same prcnn_optim_grad_norm launch.  A tensor whose grad is null is not touched at all.
+ *   prcnn_optim_step_adam  torch.optim.Adam with L2 decay: g = grad * coef; with weight_decay != 0, g = g + weight_decay * param;
+ *                          exp_avg, exp_avg_sq and the parameter step as in prcnn_optim_step (no decoupled decay).
+ *   prcnn_optim_step_sgd   torch.optim.SGD: g as above; exp_avg = exp_avg * momentum + g; param += neg_lr * exp_avg.  The momentum
+ *                          buffer is the row's exp_avg (exp_avg_sq is not read); with momentum == 0 neither is: param += neg_lr * g.
+ *                          No dampening, no Nesterov. */
+int prcnn_optim_step_adam(const prcnn_optim_tensor_t* tensors, const prcnn_optim_chunk_t* chunks, int64_t num_chunks,
+                          const double* partial, float max_norm, const float* coef, float* state, float weight_decay,
+                          float one_minus_beta1, float beta2, float one_minus_beta2, float bias2_sqrt, float eps, float neg_step,
+                          prcnn_stream_t stream);
+int prcnn_optim_step_sgd(const prcnn_optim_tensor_t* tensors, const prcnn_optim_chunk_t* chunks, int64_t num_chunks, const double* partial,
+                         float max_norm, const float* coef, float* state, float weight_decay, float momentum, float neg_lr,
+                         prcnn_stream_t stream);
 
 /* ======================================================================================================
  * KITTI result files formatted on the device (csrc/kitti_text.hip, per-box arithmetic and the "%.4f" conversion:

@@ -167,6 +167,8 @@ SIGNATURES = {
     "prcnn_optim_chunk_elems": (_Z, []),
     "prcnn_optim_grad_norm": (_I, [_P, _P, _L, _P, _P]),
     "prcnn_optim_step": (_I, [_P, _P, _L, _P, _F, _P, _P, _F, _F, _F, _F, _F, _F, _F, _P]),
+    "prcnn_optim_step_adam": (_I, [_P, _P, _L, _P, _F, _P, _P, _F, _F, _F, _F, _F, _F, _F, _P]),
+    "prcnn_optim_step_sgd": (_I, [_P, _P, _L, _P, _F, _P, _P, _F, _F, _F, _P]),
     "prcnn_kitti_result_text": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, ctypes.c_char_p, _P, _P, _P, _P, _P, _P]),
 }
 

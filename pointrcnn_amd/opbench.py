@@ -225,6 +225,51 @@ def optimizer_rows(dev, rounds=5):
             print(json.dumps(d), flush=True)
 
 
+def optimizer_mode_rows(dev, rounds=5):
+    """`optimizer step adam` / `optimizer step sgd`: one optim.ClipAdam / ClipSGD step on the device route over rpn.RPN()'s parameter
+    list (TRAIN.LR, WEIGHT_DECAY, MOMENTUM, GRAD_NORM_CLIP of default.yaml) against clip_grad_norm_ + torch.optim.Adam / SGD
+    (foreach=True) on the same shapes, alternated in one process; per route the median, minimum and maximum over `rounds` windows of
+    20 calls.  The gradients are fixed tensors; clip_grad_norm_ rescales the torch route's in memory, which after the first call
+    leaves their norm at the clip and changes no timing.
+    Traffic floor of the device route: the gradient read twice, the parameter and its state read and written once: 32 bytes per
+    element for adam, 24 for sgd."""
+    from .optim import ClipAdam, ClipSGD
+    g = torch.Generator().manual_seed(3)
+    shapes = [p.shape for p in rpn.RPN().parameters() if p.requires_grad]
+    n = sum(int(torch.Size(s).numel()) for s in shapes)
+
+    def tensors():
+        ps = [torch.nn.Parameter((torch.randn(s, generator=g) * 0.1).to(dev)) for s in shapes]
+        for p in ps:
+            p.grad = (torch.randn(p.shape, generator=g) * 0.01).to(dev)
+        return ps
+    for mode, floor_bytes in (("adam", 32), ("sgd", 24)):
+        ps, qs = tensors(), tensors()
+        if mode == "adam":
+            ours, stock = ClipAdam(ps, lr=0.002, weight_decay=0.001, grad_norm_clip=1.0, fused=True), \
+                torch.optim.Adam(qs, lr=0.002, weight_decay=0.001, foreach=True)
+        else:
+            ours, stock = ClipSGD(ps, lr=0.002, momentum=0.9, weight_decay=0.001, grad_norm_clip=1.0, fused=True), \
+                torch.optim.SGD(qs, lr=0.002, momentum=0.9, weight_decay=0.001, foreach=True)
+
+        def torch_step():
+            torch.nn.utils.clip_grad_norm_(qs, 1.0, foreach=True)
+            stock.step()
+        routes = {"torch foreach": torch_step, "device": ours.step}
+        times = {k: [] for k in routes}
+        for _ in range(rounds):
+            for k, fn in routes.items():
+                times[k].append(timeit(fn))
+        for k in routes:
+            t = sorted(times[k])
+            d = {"op": "optimizer step %s (%s)" % (mode, k), "shape": "rpn.RPN(): %d tensors, %d elements" % (len(shapes), n),
+                 "median_us": round(t[len(t) // 2] * 1e6, 1), "min_us": round(t[0] * 1e6, 1), "max_us": round(t[-1] * 1e6, 1)}
+            if k == "device":
+                d.update(traffic_floor_MB=round(floor_bytes * n / 1e6, 2), floor_GBps_at_median=round(floor_bytes * n / t[len(t) // 2] / 1e9, 1),
+                         table_uploads=ours.table_uploads)
+            print(json.dumps(d), flush=True)
+
+
 def rcnn_offline_rows(dev, B=4, M=300, G=12, R=64, N=16384, C=128, S=512):
     """`rcnn_offline_batch`: kitti_input.RCNNOfflinePreparer's device side (`--train_mode rcnn_offline`, ROI_SAMPLE_JIT False) at the
     workload's shape -- RoI sampling (IoU matrix + lists + picks + noise loop), pooling of the sampled RoIs (prcnn_roipool3d, mask +
@@ -493,6 +538,7 @@ def main():
         return
     if args.only == "optimizer":
         optimizer_rows(dev)
+        optimizer_mode_rows(dev)
         return
     B = 8 if args.quick else 32
     N = 16384
@@ -620,6 +666,8 @@ def main():
     rcnn_loss_rows(dev)
     # ---- the adam_onecycle parameter update: composed torch against the two launches of csrc/optim.hip
     optimizer_rows(dev)
+    # ---- TRAIN.OPTIMIZER adam and sgd: clip_grad_norm_ + torch's foreach step against the same two launches
+    optimizer_mode_rows(dev)
     # ---- the evaluation statistics of a batch: the reference's per-frame loop on this library against the device passes (csrc/eval_stats.hip)
     eval_stats_rows(dev)
     # ---- the result files of a batch: kitti_output.write_detections against the text formatted on the device (csrc/kitti_text.hip),

@@ -1641,27 +1641,51 @@ def optim_grad_norm(tensors, chunks, partial=None):
     return partial
 
 
+def _optim_update(who, fn, names, tensors, chunks, scalars, partial, max_norm, coef, state):
+    C = _optim_tables(tensors, chunks)
+    if len(scalars) != len(names):
+        raise ValueError("%s: scalars must be the %d values %s" % (who, len(names), ", ".join(names)))
+    if coef is not None:
+        if _chk(coef, "coef").numel() != 1:
+            raise ValueError("%s: coef must hold one float" % who)
+        state = None
+    else:
+        if partial is None or tuple(_chk(partial, "partial", torch.float64, 1).shape) != (C,):
+            raise ValueError("%s: without coef, partial must be the (%d,) float64 result of optim_grad_norm" % (who, C))
+        if state is None:
+            state = torch.zeros((2,), dtype=_F32, device=tensors.device)
+        elif _chk(state, "state", _F32, 1).numel() != 2:
+            raise ValueError("%s: state must be (2,) float32" % who)
+    _cabi.check(getattr(_cabi.lib(), fn)(_p(tensors), _p(chunks), C, _p(partial), float(max_norm), _p(coef), _p(state),
+                                         *[float(s) for s in scalars], _stream()), fn)
+    return state
+
+
 def optim_step(tensors, chunks, scalars, partial=None, max_norm=1.0, coef=None, state=None):
     """clip coefficient + decay + Adam over every chunk in one launch.  scalars: the seven OPTIM_SCALARS (optim.adam_scalars).
     coef None: the coefficient is formed from `partial` (optim_grad_norm) and max_norm, and {norm, coef} go to state (2) f32;
     coef (1) f32 on the device: it is used as it is.  -> state (None with a caller's coef).  Nothing is read back."""
-    C = _optim_tables(tensors, chunks)
-    if len(scalars) != len(OPTIM_SCALARS):
-        raise ValueError("optim_step: scalars must be the %d values %s" % (len(OPTIM_SCALARS), ", ".join(OPTIM_SCALARS)))
-    if coef is not None:
-        if _chk(coef, "coef").numel() != 1:
-            raise ValueError("optim_step: coef must hold one float")
-        state = None
-    else:
-        if partial is None or tuple(_chk(partial, "partial", torch.float64, 1).shape) != (C,):
-            raise ValueError("optim_step: without coef, partial must be the (%d,) float64 result of optim_grad_norm" % C)
-        if state is None:
-            state = torch.zeros((2,), dtype=_F32, device=tensors.device)
-        elif _chk(state, "state", _F32, 1).numel() != 2:
-            raise ValueError("optim_step: state must be (2,) float32")
-    _cabi.check(_cabi.lib().prcnn_optim_step(_p(tensors), _p(chunks), C, _p(partial), float(max_norm), _p(coef), _p(state),
-                                             *[float(s) for s in scalars], _stream()), "prcnn_optim_step")
-    return state
+    return _optim_update("optim_step", "prcnn_optim_step", OPTIM_SCALARS, tensors, chunks, scalars, partial, max_norm, coef, state)
+
+
+OPTIM_ADAM_SCALARS = ("weight_decay",) + OPTIM_SCALARS[1:]
+OPTIM_SGD_SCALARS = ("weight_decay", "momentum", "neg_lr")
+
+
+def optim_step_adam(tensors, chunks, scalars, partial=None, max_norm=1.0, coef=None, state=None):
+    """torch.optim.Adam with L2 decay (TRAIN.OPTIMIZER adam; optim.ClipAdam) over every chunk in one launch: as optim_step, but
+    scalars are the seven OPTIM_ADAM_SCALARS (weight_decay is added to the gradient, nothing is decayed) and a tensor without a
+    gradient is not touched."""
+    return _optim_update("optim_step_adam", "prcnn_optim_step_adam", OPTIM_ADAM_SCALARS, tensors, chunks, scalars, partial, max_norm,
+                         coef, state)
+
+
+def optim_step_sgd(tensors, chunks, scalars, partial=None, max_norm=1.0, coef=None, state=None):
+    """torch.optim.SGD with momentum (TRAIN.OPTIMIZER sgd; optim.ClipSGD) over every chunk in one launch.  scalars: the three
+    OPTIM_SGD_SCALARS.  The momentum buffer is column exp_avg of `tensors`; exp_avg_sq is not read, and with momentum 0 neither
+    is.  A tensor without a gradient is not touched."""
+    return _optim_update("optim_step_sgd", "prcnn_optim_step_sgd", OPTIM_SGD_SCALARS, tensors, chunks, scalars, partial, max_norm,
+                         coef, state)
 
 
 # ------------------------------------------------------------------ KITTI result text (csrc/kitti_text.hip)

@@ -8,6 +8,9 @@ MOMS=[0.95, 0.85], DIV_FACTOR=10, PCT_START=0.4) stepped every iteration, with c
     OneCycleAdam              clip + decoupled decay + Adam + schedule in ONE step(); two routes, one arithmetic contract
                               (csrc/optim_math.h): composed torch ops on any device, or two launches of csrc/optim.hip over all
                               parameter tensors (ops.optim_grad_norm, ops.optim_step) for CUDA(HIP) parameters.
+    ClipAdam, ClipSGD         TRAIN.OPTIMIZER adam and sgd (tools/train_rcnn.py:90-94): torch.optim.Adam / SGD that clip the gradient
+                              norm inside step(); stock torch on any device, or the same two launches (ops.optim_step_adam,
+                              ops.optim_step_sgd).  State and state_dict() are torch's; see _ClipInStep.
 
 Per element and iteration t = 1, 2, ... with (lr, beta1) = one_cycle(t - 1):
     g = grad * coef,  coef = min(max_norm / (norm + 1e-6), 1)        norm: 2-norm over all gradients; always applied, as torch does
@@ -22,6 +25,7 @@ Where this differs from `clip_grad_norm_` + `torch.optim.Adam`:
     is missing in some iteration is decayed, keeps its moments, and is bias-corrected by the global t afterwards.
   * Non-finite gradients are not special-cased (a NaN norm gives NaN parameters, as in torch).
 """
+import math
 import os
 
 import numpy as np
@@ -85,6 +89,7 @@ class OneCycleAdam(torch.optim.Optimizer):
 
     last_grad_norm: a 0-dim tensor on the parameters' device holding the gradient norm of the last step; reading it is the
     caller's synchronisation, step() itself reads nothing back.  table_uploads counts the pointer-table uploads of the device route."""
+    clips_in_step = True                               # a trainer must not call clip_grad_norm_ in front of step()
 
     def __init__(self, params, total_steps, lr_max=0.002, moms=(0.95, 0.85), div_factor=10.0, pct_start=0.4, weight_decay=0.001,
                  grad_norm_clip=1.0, betas2=0.99, eps=1e-8, fused=None):
@@ -186,29 +191,198 @@ class OneCycleAdam(torch.optim.Optimizer):
 
     # ------------------------------------------------------------------ device route
     def _step_device(self, params, rows, scalars, max_norm):
-        from . import ops
         if not params:
             return
-        dev = params[0].device
-        d = self._dev
-        numels = [r[4] for r in rows]
-        if d is None or d["numels"] != numels or d["device"] != dev:
-            chunks = ops.optim_chunk_rows(numels)
-            d = self._dev = dict(numels=numels, device=dev, rows=None,
-                                 table=torch.zeros((len(params), 5), dtype=torch.int64, device=dev),
-                                 chunks=torch.tensor(chunks, dtype=torch.int64).reshape(-1, 2).to(dev),
-                                 partial=torch.zeros((len(chunks),), dtype=torch.float64, device=dev),
-                                 state=torch.zeros((2,), dtype=torch.float32, device=dev),
-                                 one=torch.ones((1,), dtype=torch.float32, device=dev),
-                                 staging=_Staging((len(params), 5)))
-        if rows != d["rows"]:                           # the caching allocator normally hands the same gradient addresses back
-            d["staging"].upload(rows, d["table"])
-            d["rows"] = rows
-            self.table_uploads += 1
-        if max_norm is None:
-            ops.optim_step(d["table"], d["chunks"], scalars, coef=d["one"])
-            self.last_grad_norm = None
-        else:
-            ops.optim_grad_norm(d["table"], d["chunks"], partial=d["partial"])
-            ops.optim_step(d["table"], d["chunks"], scalars, partial=d["partial"], max_norm=max_norm, state=d["state"])
-            self.last_grad_norm = d["state"][0]
+        _device_launches(self, _device_tables(self, rows, params[0].device), "optim_step", scalars, max_norm)
+
+
+def _device_tables(opt, rows, dev):
+    """the device route's tables of optimizer `opt` (kept in opt._dev) for these pointer rows [param, grad, exp_avg, exp_avg_sq, numel]:
+    chunk rows, partial sums and the {norm, coef} state are built once per list of element counts; the pointer table is uploaded
+    again (through the pinned staging; opt.table_uploads counts) only when an address changed"""
+    from . import ops
+    d = opt._dev
+    numels = [r[4] for r in rows]
+    if d is None or d["numels"] != numels or d["device"] != dev:
+        chunks = ops.optim_chunk_rows(numels)
+        d = opt._dev = dict(numels=numels, device=dev, rows=None,
+                            table=torch.zeros((len(rows), 5), dtype=torch.int64, device=dev),
+                            chunks=torch.tensor(chunks, dtype=torch.int64).reshape(-1, 2).to(dev),
+                            partial=torch.zeros((len(chunks),), dtype=torch.float64, device=dev),
+                            state=torch.zeros((2,), dtype=torch.float32, device=dev),
+                            one=torch.ones((1,), dtype=torch.float32, device=dev),
+                            staging=_Staging((len(rows), 5)))
+    if rows != d["rows"]:                               # the caching allocator normally hands the same gradient addresses back
+        d["staging"].upload(rows, d["table"])
+        d["rows"] = rows
+        opt.table_uploads += 1
+    return d
+
+
+def _device_launches(opt, d, update, scalars, max_norm):
+    """the norm launch and the update launch `update` (a name in ops, looked up at the call); sets opt.last_grad_norm"""
+    from . import ops
+    if max_norm is None:
+        getattr(ops, update)(d["table"], d["chunks"], scalars, coef=d["one"])
+        opt.last_grad_norm = None
+    else:
+        ops.optim_grad_norm(d["table"], d["chunks"], partial=d["partial"])
+        getattr(ops, update)(d["table"], d["chunks"], scalars, partial=d["partial"], max_norm=max_norm, state=d["state"])
+        opt.last_grad_norm = d["state"][0]
+
+
+def _f32_cuda(*tensors):
+    return all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and not t.is_sparse for t in tensors)
+
+
+class _ClipInStep:
+    """What ClipAdam and ClipSGD share: TRAIN.OPTIMIZER adam / sgd of the reference (tools/train_rcnn.py:88-93) with the
+    clip_grad_norm_ of its Trainer._train_it (train_utils.py:135) inside step(), on two routes.
+
+      composed   literally clip_grad_norm_(params, grad_norm_clip) followed by torch's own step(): `.grad` is rescaled in memory.
+      device     ops.optim_grad_norm and one update launch over all tensors (csrc/optim.hip, arithmetic csrc/optim_math.h): `.grad`
+                 keeps its bits; read the norm from last_grad_norm.  lr is read from param_groups[0]["lr"] at every step, so a
+                 scheduler's change is used at once.  The state is torch's own (state_dict() loads into the stock class and back).
+
+    fused, last_grad_norm, table_uploads: as OneCycleAdam's.  clips_in_step tells a trainer not to clip a second time."""
+    clips_in_step = True
+
+    def _init_clip(self, grad_norm_clip, fused):
+        if grad_norm_clip is not None and not grad_norm_clip > 0:
+            raise ValueError("%s: grad_norm_clip must be > 0 or None, got %r" % (type(self).__name__, grad_norm_clip))
+        self.grad_norm_clip = grad_norm_clip
+        self.fused = fused
+        self.last_grad_norm = None
+        self.table_uploads = 0
+        self._dev = None
+
+    def add_param_group(self, param_group):
+        if self.param_groups:
+            raise ValueError("%s: one parameter group" % type(self).__name__)
+        super().add_param_group(param_group)
+
+    def _rows_known(self, rows):
+        """the same addresses are the tensors that passed the eligibility check last time"""
+        return self._dev is not None and rows == self._dev["rows"]
+
+    def _device_rows(self, params):
+        """-> (pointer rows, scalars) of the device route, the state brought to where torch's own step would leave it; or a string:
+        why this step cannot take the device route"""
+        raise NotImplementedError
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        params = self.param_groups[0]["params"]
+        with_grad = [p for p in params if p.grad is not None]
+        want = self.fused if self.fused is not None else (FUSED_OPTIM and bool(with_grad) and with_grad[0].is_cuda)
+        if want and with_grad:
+            got = self._device_rows(params)
+            if isinstance(got, str):
+                if self.fused:
+                    raise RuntimeError("%s(fused=True): %s" % (type(self).__name__, got))
+                want = False
+        if want:
+            if with_grad:
+                rows, scalars = got
+                _device_launches(self, _device_tables(self, rows, with_grad[0].device), self._update, scalars, self.grad_norm_clip)
+            else:
+                self.last_grad_norm = None
+            return loss
+        self.last_grad_norm = None
+        if self.grad_norm_clip is not None:
+            self.last_grad_norm = torch.nn.utils.clip_grad_norm_(params, self.grad_norm_clip)
+        super().step()
+        return loss
+
+
+def _step_count(s):
+    return int(s.item()) if torch.is_tensor(s) else int(s)
+
+
+class ClipAdam(_ClipInStep, torch.optim.Adam):
+    """torch.optim.Adam (L2 weight decay added to the gradient) that clips the gradient norm inside step(); see _ClipInStep.
+    torch counts `step` per parameter and the kernel takes one bias correction per launch, so the device route runs only when
+    all parameters that have a gradient share one `step`; otherwise that step takes the composed route."""
+    _update = "optim_step_adam"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, maximize=False,
+                 grad_norm_clip=None, fused=None):
+        if amsgrad or maximize:
+            raise ValueError("ClipAdam: amsgrad and maximize are not built")
+        torch.optim.Adam.__init__(self, params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self._init_clip(grad_norm_clip, fused)
+        self._steps = None
+
+    def _packed_steps(self, states):
+        """torch keeps `step` as one 0-dim float32 CPU tensor per parameter; a hundred scalar increments a step cost more than both
+        launches.  The counters of these states are therefore made views of ONE flat tensor (the layout stays torch's: its own
+        step() increments the views in place, state_dict() hands them out) -> that tensor, element k the `step` of states[k].
+        Packed again when a counter is another object than last time (the first step, load_state_dict)."""
+        pack = self._steps
+        if pack is None or len(pack[1]) != len(states) or any(st["step"] is not v for st, v in zip(states, pack[1])):
+            flat = torch.tensor([float(_step_count(st["step"])) for st in states], dtype=torch.float32)
+            views = list(flat.unbind(0))
+            for st, v in zip(states, views):
+                st["step"] = v
+            pack = self._steps = (flat, views)
+        return pack[0]
+
+    def _device_rows(self, params):
+        g = self.param_groups[0]
+        rows, states, check = [], [], []
+        for p in params:
+            st = self.state[p] if p.grad is not None or p in self.state else {}
+            if p.grad is not None:
+                if not st:                           # as torch.optim.Adam._init_group
+                    st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                check += [p, p.grad, st["exp_avg"], st["exp_avg_sq"]]
+                states.append(st)
+            rows.append((p.data_ptr(), 0 if p.grad is None else p.grad.data_ptr(), st["exp_avg"].data_ptr() if st else 0,
+                         st["exp_avg_sq"].data_ptr() if st else 0, p.numel()))
+        if not self._rows_known(rows) and not _f32_cuda(*check):
+            return "the device route needs contiguous float32 CUDA(HIP) parameters, gradients and moments"
+        flat = self._packed_steps(states)
+        steps = {int(flat.min()), int(flat.max())}
+        if len(steps) != 1:
+            return "the parameters that have a gradient do not share one `step` (%s)" % sorted(steps)
+        t = steps.pop() + 1
+        flat.add_(1)
+        beta1, beta2 = g["betas"]
+        return rows, (g["weight_decay"], 1 - beta1, beta2, 1 - beta2, math.sqrt(1 - beta2 ** t), g["eps"],
+                      -(float(g["lr"]) / (1 - beta1 ** t)))
+
+
+class ClipSGD(_ClipInStep, torch.optim.SGD):
+    """torch.optim.SGD with momentum that clips the gradient norm inside step(); see _ClipInStep.  The device route keeps torch's
+    `momentum_buffer` (created as zeros, which gives torch's first step buf = g exactly); momentum 0 keeps none."""
+    _update = "optim_step_sgd"
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, maximize=False,
+                 grad_norm_clip=None, fused=None):
+        if nesterov or dampening != 0 or maximize:
+            raise ValueError("ClipSGD: nesterov, dampening and maximize are not built")
+        torch.optim.SGD.__init__(self, params, lr=lr, momentum=momentum, weight_decay=weight_decay)
+        self._init_clip(grad_norm_clip, fused)
+
+    def _device_rows(self, params):
+        g = self.param_groups[0]
+        rows, check = [], []
+        for p in params:
+            buf = None
+            if p.grad is not None:
+                if g["momentum"] != 0:
+                    st = self.state[p]
+                    buf = st.get("momentum_buffer")
+                    if buf is None:
+                        buf = st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                check += [p, p.grad] + ([] if buf is None else [buf])
+            rows.append((p.data_ptr(), 0 if p.grad is None else p.grad.data_ptr(), 0 if buf is None else buf.data_ptr(), 0, p.numel()))
+        if not self._rows_known(rows) and not _f32_cuda(*check):
+            return "the device route needs contiguous float32 CUDA(HIP) parameters, gradients and momentum buffers"
+        return rows, (g["weight_decay"], g["momentum"], -float(g["lr"]))
