@@ -792,6 +792,25 @@ int prcnn_train_stack_fwd(const prcnn_train_src_t* src, const prcnn_train_layer_
 int prcnn_train_stack_bwd(const prcnn_train_src_t* src, const prcnn_train_layer_t* layers, int nl, int pool_ns, const float* a_dump,
                           int ld_dump, const float* gout, int ld_gout, const uint8_t* arg, float* gin, int ld_gin, void* work,
                           size_t work_bytes, prcnn_stream_t stream);
+/* The same two passes with the forward / dgrad GEMMs of the eligible layers on the split-bf16 x 6 arithmetic of the inference
+ * layers (every fp32 operand cut exactly into three bf16 pieces, six v_mfma_f32_32x32x16_bf16 products, fp32 accumulation:
+ * fp32-grade results, csrc/mlp_train.h).  Opt-in: prcnn_train_stack_fwd / _bwd above are unchanged.  Each takes what its twin
+ * takes plus a table of nl device pointers to scratch for the split weight images, written per call; entry l NULL = layer l on
+ * the fp32 pipe.
+ *   wsplit[l]    prcnn_wsplit_bytes(Nout, K) bytes, 16-byte aligned.  Used when layer l reads plain rows (every layer l > 0, layer
+ *                0 of a mode-0 source), K % 32 == 0 and its rows (and pro_scale / pro_shift) are 16-byte aligned;
+ *   wsplit_t[l]  prcnn_wsplit_bytes(Kin, Nout) bytes (Kin as for wpack_t), 16-byte aligned.  Used when Nout % 32 == 0.
+ * A layer that does not meet its condition runs the fp32 kernel it runs in the twin, whatever its entry holds; wgrad, the
+ * statistics, pooling and every reduction are the twin's launches.  wpack / wpack_t are written as in the twin (the split images come
+ * next to them, not instead).
+ * Non-finite operands: a row whose fp32 result is +-inf or NaN in SOME column comes out non-finite (NaN) in EVERY column of its
+ * 32-column blocks; rows with finite operands are unaffected by their neighbours.  Nothing is recomputed on the fp32 pipe. */
+int prcnn_train_stack_fwd_split(const prcnn_train_src_t* src, const prcnn_train_layer_t* layers, int nl, int pool_ns, float* a_dump,
+                                int ld_dump, float* out, int ld_out, int col_off, uint8_t* arg, void* const* wsplit, void* work,
+                                size_t work_bytes, prcnn_stream_t stream);
+int prcnn_train_stack_bwd_split(const prcnn_train_src_t* src, const prcnn_train_layer_t* layers, int nl, int pool_ns, const float* a_dump,
+                                int ld_dump, const float* gout, int ld_gout, const uint8_t* arg, float* gin, int ld_gin,
+                                void* const* wsplit_t, void* work, size_t work_bytes, prcnn_stream_t stream);
 /* Padding-free rows for a grouped stack (exact: ball_query pads a group with copies of its first hit; copies are identical rows).
  * prcnn_train_group_rows builds the distinct-row list deterministically (count -> exclusive scan -> fill, group order);
  * prcnn_flat_rows_grad scatters the first layer's row gradients back: dfeat[ridx[r], 0:C] += G[r, 0:C] for the live rows. */

@@ -21,6 +21,8 @@
 //                                   in channels-last rows the 32 lanes of an operand are 32 consecutive channels of one row,
 //                                   which is exactly the v_mfma_f32_32x32x2_f32 A / B layout when the reduction runs over rows
 //                                   (no LDS, no barrier); row ranges are split over workgroups, partial tiles reduced in fixed order.
+//   opt-in    train_fwd_s_kernel, train_dgrad_s_kernel: the forward of plain-row layers and dgrad on the split-bf16 x 6 arithmetic of
+//                                   the inference layers (prcnn_train_stack_fwd_split / _bwd_split; see the block above those kernels).
 // Nothing here folds BatchNorm or removes padded rows: the arithmetic is the reference's, row for row.
 #pragma once
 
@@ -38,6 +40,78 @@ struct TrainFwd {
     const float* mult;
     float* slab_w;
 };
+
+// The forward epilogue (shared by train_fwd_kernel and train_fwd_s_kernel: one accumulator layout): raw y store + the column
+// statistics of this wave's 64-row slab.
+template <int WNB>
+__device__ __forceinline__ void train_fwd_epilogue(const TrainFwd& T, const MlpParams& P, const f32x16 (&acc)[2][WNB], const long row0,
+                                                   const int nb0, const int wm, const int wn, const int lane, const bool n_active) {
+    const int h = lane >> 5, j = lane & 31;
+    if (!n_active && !(T.slab_w && nb0 == 0 && wn == 0)) return;
+    // ---- epilogue: raw store + column statistics of this wave's 64-row slab ---------------------------------------------
+    const long wrow0 = row0 + wm * 64;
+    const long left = P.rows - wrow0;
+    const int cnt = left >= 64 ? 64 : (left > 0 ? (int)left : 0);          // live rows of the slab (wave-uniform)
+    // row weights (multiplicities; 1 without padding-free rows) of this lane's 32 rows, and the slab's weight sum
+    float w0[16], w1[16], wsum = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int rin = (r & 3) + 8 * (r >> 2) + 4 * h;
+        const long g0 = wrow0 + rin, g1 = g0 + 32;
+        w0[r] = g0 < P.rows ? (T.mult ? T.mult[g0] : 1.f) : 0.f;
+        w1[r] = g1 < P.rows ? (T.mult ? T.mult[g1] : 1.f) : 0.f;
+        wsum += w0[r] + w1[r];
+    }
+    wsum += __shfl_xor(wsum, 32);                                           // (every lane of a half holds the same 32 rows)
+    const float inv_w = wsum > 0.f ? 1.0f / wsum : 0.f;
+    if (T.slab_w && lane == 0 && nb0 == 0 && wn == 0 && cnt > 0) T.slab_w[wrow0 >> 6] = wsum;
+#pragma unroll
+    for (int nn = 0; nn < WNB; nn++) {
+        const int nb = nb0 + wn * WNB + nn;
+        if (nb >= P.NB) continue;
+        const int n = nb * 32 + j;
+        const bool n_ok = n < P.Nout;
+        const f32x16& a0 = acc[0][nn];
+        const f32x16& a1 = acc[1][nn];
+        float s = 0.f;
+        if (cnt == 64 && nb * 32 + 32 <= P.Nout) {       // whole slab x block inside y: unguarded stores, back to back (see layer_epilogue)
+            float* o = P.out + (wrow0 + 4 * h) * P.ld_out + P.col_off + n;
+            const long ld = P.ld_out;
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int rr = (r & 3) + 8 * (r >> 2);
+                s += w0[r] * a0[r] + w1[r] * a1[r];
+                o[rr * ld] = a0[r];
+                o[(32 + rr) * ld] = a1[r];
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int rin = (r & 3) + 8 * (r >> 2) + 4 * h;
+                const long g0 = wrow0 + rin, g1 = g0 + 32;
+                s += w0[r] * a0[r] + w1[r] * a1[r];
+                if (n_ok && g0 < P.rows) P.out[g0 * P.ld_out + P.col_off + n] = a0[r];
+                if (n_ok && g1 < P.rows) P.out[g1 * P.ld_out + P.col_off + n] = a1[r];
+            }
+        }
+        if (T.part) {
+            s += __shfl_xor(s, 32);
+            const float mean = s * inv_w;
+            float m2 = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const float d0 = a0[r] - mean, d1 = a1[r] - mean;
+                m2 += w0[r] * (d0 * d0) + w1[r] * (d1 * d1);
+            }
+            m2 += __shfl_xor(m2, 32);
+            if (h == 0 && n_ok && cnt > 0) {
+                const long slab = wrow0 >> 6;
+                T.part[(slab * 2 + 0) * T.ld_part + n] = mean;
+                T.part[(slab * 2 + 1) * T.ld_part + n] = m2;
+            }
+        }
+    }
+}
 
 // FASTP (plain rows, 16-byte aligned, K a multiple of 4): the chunk loads are unconditional 16-byte loads from clamped addresses (rows
 // past the end are clamped -- never stored or counted --, k-pieces past K re-read the last piece and are zeroed by multiplication), so
@@ -154,70 +228,7 @@ __global__ __launch_bounds__(MLP_THREADS, ((WNB == 1 && MODE != MODE_INTERP) ? 3
         store_chunk(min(c + 1, nchunks - 1), buf ^ 1);
         __syncthreads();
     }
-    if (!n_active && !(T.slab_w && nb0 == 0 && wn == 0)) return;
-    // ---- epilogue: raw store + column statistics of this wave's 64-row slab ---------------------------------------------
-    const long wrow0 = row0 + wm * 64;
-    const long left = P.rows - wrow0;
-    const int cnt = left >= 64 ? 64 : (left > 0 ? (int)left : 0);          // live rows of the slab (wave-uniform)
-    // row weights (multiplicities; 1 without padding-free rows) of this lane's 32 rows, and the slab's weight sum
-    float w0[16], w1[16], wsum = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const int rin = (r & 3) + 8 * (r >> 2) + 4 * h;
-        const long g0 = wrow0 + rin, g1 = g0 + 32;
-        w0[r] = g0 < P.rows ? (T.mult ? T.mult[g0] : 1.f) : 0.f;
-        w1[r] = g1 < P.rows ? (T.mult ? T.mult[g1] : 1.f) : 0.f;
-        wsum += w0[r] + w1[r];
-    }
-    wsum += __shfl_xor(wsum, 32);                                           // (every lane of a half holds the same 32 rows)
-    const float inv_w = wsum > 0.f ? 1.0f / wsum : 0.f;
-    if (T.slab_w && lane == 0 && nb0 == 0 && wn == 0 && cnt > 0) T.slab_w[wrow0 >> 6] = wsum;
-#pragma unroll
-    for (int nn = 0; nn < WNB; nn++) {
-        const int nb = nb0 + wn * WNB + nn;
-        if (nb >= P.NB) continue;
-        const int n = nb * 32 + j;
-        const bool n_ok = n < P.Nout;
-        const f32x16& a0 = acc[0][nn];
-        const f32x16& a1 = acc[1][nn];
-        float s = 0.f;
-        if (cnt == 64 && nb * 32 + 32 <= P.Nout) {       // whole slab x block inside y: unguarded stores, back to back (see layer_epilogue)
-            float* o = P.out + (wrow0 + 4 * h) * P.ld_out + P.col_off + n;
-            const long ld = P.ld_out;
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int rr = (r & 3) + 8 * (r >> 2);
-                s += w0[r] * a0[r] + w1[r] * a1[r];
-                o[rr * ld] = a0[r];
-                o[(32 + rr) * ld] = a1[r];
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int rin = (r & 3) + 8 * (r >> 2) + 4 * h;
-                const long g0 = wrow0 + rin, g1 = g0 + 32;
-                s += w0[r] * a0[r] + w1[r] * a1[r];
-                if (n_ok && g0 < P.rows) P.out[g0 * P.ld_out + P.col_off + n] = a0[r];
-                if (n_ok && g1 < P.rows) P.out[g1 * P.ld_out + P.col_off + n] = a1[r];
-            }
-        }
-        if (T.part) {
-            s += __shfl_xor(s, 32);
-            const float mean = s * inv_w;
-            float m2 = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const float d0 = a0[r] - mean, d1 = a1[r] - mean;
-                m2 += w0[r] * (d0 * d0) + w1[r] * (d1 * d1);
-            }
-            m2 += __shfl_xor(m2, 32);
-            if (h == 0 && n_ok && cnt > 0) {
-                const long slab = wrow0 >> 6;
-                T.part[(slab * 2 + 0) * T.ld_part + n] = mean;
-                T.part[(slab * 2 + 1) * T.ld_part + n] = m2;
-            }
-        }
-    }
+    train_fwd_epilogue<WNB>(T, P, acc, row0, nb0, wm, wn, lane, n_active);
 }
 
 // Batch statistics from the slab partials, in two deterministic stages (everything in double, fixed summation order):
@@ -443,6 +454,39 @@ struct TrainDgrad {
     int KB, NB, Kin;              // k-blocks over N, n-blocks over Kin
     float* out; int ld_out;
 };
+// The dgrad epilogue (shared by train_dgrad_kernel and train_dgrad_s_kernel): the store of the wave's 64 x (32 WNB) block.
+template <int WNB>
+__device__ __forceinline__ void train_dgrad_epilogue(const TrainDgrad& D, const f32x16 (&acc)[2][WNB], const long row0, const int nb0,
+                                                     const int wm, const int wn, const int lane, const long live, const bool n_active) {
+    const int h = lane >> 5, j = lane & 31;
+    if (!n_active) return;
+    const long wrow0 = row0 + wm * 64;
+#pragma unroll
+    for (int nn = 0; nn < WNB; nn++) {
+        const int nb = nb0 + wn * WNB + nn;
+        if (nb >= D.NB) continue;
+        const int n = nb * 32 + j;
+        if (wrow0 + 64 <= live && nb * 32 + 32 <= D.Kin) {     // whole block inside the output: unguarded stores (see layer_epilogue)
+            float* o = D.out + (wrow0 + 4 * h) * D.ld_out + n;
+            const long ld = D.ld_out;
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int rr = (r & 3) + 8 * (r >> 2);
+                o[rr * ld] = acc[0][nn][r];
+                o[(32 + rr) * ld] = acc[1][nn][r];
+            }
+            continue;
+        }
+        if (n >= D.Kin) continue;
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int rin = (r & 3) + 8 * (r >> 2) + 4 * h;
+            const long g0 = wrow0 + rin, g1 = g0 + 32;
+            if (g0 < live) D.out[g0 * D.ld_out + n] = acc[0][nn][r];
+            if (g1 < live) D.out[g1 * D.ld_out + n] = acc[1][nn][r];
+        }
+    }
+}
 // POOL as in train_wgrad_lds_kernel (0: G per row; 1: pooled over fixed groups; 2: over the groups of padding-free rows).  The rows a
 // thread stages are the same for every chunk, so their group / slot are looked up once; the chunk loads themselves are unconditional
 // 16-byte loads from clamped addresses (pieces past N zeroed by multiplication).
@@ -556,33 +600,239 @@ __global__ __launch_bounds__(MLP_THREADS, (WNB == 1 ? 3 : 2)) void train_dgrad_k
         store_chunk(min(c + 1, nchunks - 1), buf ^ 1);
         __syncthreads();
     }
-    if (!n_active) return;
-    const long wrow0 = row0 + wm * 64;
+    train_dgrad_epilogue<WNB>(D, acc, row0, nb0, wm, wn, lane, live, n_active);
+}
+
+// =====================================================================================================
+// Split-bf16 x 6 forward and dgrad (OPT-IN: prcnn_train_stack_fwd_split / _bwd_split hand a split weight image per eligible layer;
+// the fp32 kernels above stay the default).  The operand plan is layer_s_tile's (mlp.hip): the staged fp32 value -- AFTER the
+// element-wise transform, relu(y_prev * scale + shift) in the forward, bwd_dy4(G, y, cst) in dgrad -- is cut exactly into three
+// bf16 pieces (split3) on its way into LDS, three planes per buffer with 80-byte rows (2 x 3 x 128 x 80 = 61 440 bytes: two
+// workgroups per CU); the weights come pre-split (pack_weight_split_kernel's chain = 0 image) through a two-step register ring;
+// six v_mfma_f32_32x32x16_bf16 per 16-wide k-step, smallest terms first, fp32 accumulators in mlp_layer_b_kernel's layout, so
+// the two epilogues above are shared with the fp32 kernels.  The reduction width (K forward, N dgrad) is a multiple of 32: no
+// partial chunk.  The staged chunk is requested ONE chunk ahead (dgrad holds 2 x 4 rows + six constant vectors per chunk in flight).
+// Registers at the 256 of two waves per SIMD (__launch_bounds__(256, 2); the LDS allows no third workgroup): forward 148 / 194
+// (narrow / wide), dgrad 185 / 243 unpooled, 203 narrow pooled; the two WIDE POOLED dgrad forms need 256 and spill 9 (28 bytes of
+// scratch per lane) -- they run the last layer of a pooled stack only.
+// Non-finite operands: the split of +-inf is (inf, NaN, NaN) and a NaN piece reaches every product of ITS row -- the weights are
+// finite, and an MFMA row depends on that row of A only.  Rule: NO recomputation on the fp32 pipe (split_redo_f32 is the inference
+// kernels' choice); a row with a non-finite staged value comes out non-finite (NaN) in every column where the fp32 kernel gives
+// +-inf or NaN in some, every other row of the tile is computed as if its neighbours were finite.  A training step with an infinite
+// activation is lost under either arithmetic (the batch statistics turn NaN).
+// =====================================================================================================
+template <int WNB, class Stage>
+__device__ __forceinline__ void train_s_tile(Stage& st, const uint4* __restrict__ wsplit, const int KS, const int NB, const int nb0,
+                                             const int tid, unsigned char* __restrict__ Ls, f32x16 (&acc)[2][WNB]) {
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
+    const int h = lane >> 5, j = lane & 31;
+    const int c4 = tid & 7, r0 = tid >> 3;
+    const int nchunks = KS >> 1;
+    auto store_chunk = [&](int c, int buf) {
 #pragma unroll
-    for (int nn = 0; nn < WNB; nn++) {
-        const int nb = nb0 + wn * WNB + nn;
-        if (nb >= D.NB) continue;
-        const int n = nb * 32 + j;
-        if (wrow0 + 64 <= live && nb * 32 + 32 <= D.Kin) {     // whole block inside the output: unguarded stores (see layer_epilogue)
-            float* o = D.out + (wrow0 + 4 * h) * D.ld_out + n;
-            const long ld = D.ld_out;
+        for (int u = 0; u < 4; u++) {
+            const float4 v = st.value(u, c);
+            uint32_t b[3][4];
+            split3(v.x, b[0][0], b[1][0], b[2][0]);
+            split3(v.y, b[0][1], b[1][1], b[2][1]);
+            split3(v.z, b[0][2], b[1][2], b[2][2]);
+            split3(v.w, b[0][3], b[1][3], b[2][3]);
 #pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int rr = (r & 3) + 8 * (r >> 2);
-                o[rr * ld] = acc[0][nn][r];
-                o[(32 + rr) * ld] = acc[1][nn][r];
-            }
-            continue;
+            for (int p = 0; p < 3; p++)
+                *reinterpret_cast<uint2*>(Ls + (buf * 3 + p) * SPL_PLANE + (r0 + 32 * u) * SPL_LDB + c4 * 8) =
+                    make_uint2(bf16_pair(b[p][0], b[p][1]), bf16_pair(b[p][2], b[p][3]));
         }
-        if (n >= D.Kin) continue;
+    };
 #pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const int rin = (r & 3) + 8 * (r >> 2) + 4 * h;
-            const long g0 = wrow0 + rin, g1 = g0 + 32;
-            if (g0 < live) D.out[g0 * D.ld_out + n] = acc[0][nn][r];
-            if (g1 < live) D.out[g1 * D.ld_out + n] = acc[1][nn][r];
+    for (int r = 0; r < 2; r++)
+#pragma unroll
+        for (int n = 0; n < WNB; n++) acc[r][n] = (f32x16){0};
+    // B ring: slot (g & 1) holds this wave's operands of k-step g, requested two steps ahead; unconditional loads (column blocks
+    // past the width re-read the last block, k-steps past the end the last step -- neither result is stored / reached)
+    uint4 bq[2][WNB][3];
+    const uint4* bptr[WNB];
+#pragma unroll
+    for (int n = 0; n < WNB; n++) bptr[n] = wsplit + ((long)min(nb0 + wn * WNB + n, NB - 1) * KS) * 192 + lane;
+    auto load_b = [&](int g, int slot) {
+        const long off = (long)min(g, KS - 1) * 192;
+#pragma unroll
+        for (int n = 0; n < WNB; n++)
+#pragma unroll
+            for (int p = 0; p < 3; p++) bq[slot][n][p] = bptr[n][off + p * 64];
+    };
+    bf16x8 a0[2][3], a1[2][3];                            // the A operands of the chunk's two k-steps
+    auto read_a = [&](int buf, int stp, bf16x8 (&a)[2][3]) {
+        const unsigned char* a_base = Ls + buf * 3 * SPL_PLANE + (wm * 64 + j) * SPL_LDB + h * 16 + stp * 32;
+#pragma unroll
+        for (int r = 0; r < 2; r++)
+#pragma unroll
+            for (int p = 0; p < 3; p++)
+                a[r][p] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(a_base + p * SPL_PLANE + r * 32 * SPL_LDB));
+    };
+#define TSPL_TERM(A, SL, PA, PB)                                                                                                  \
+    _Pragma("unroll") for (int r = 0; r < 2; r++) _Pragma("unroll") for (int n = 0; n < WNB; n++)                                  \
+        acc[r][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[r][PA], __builtin_bit_cast(bf16x8, bq[SL][n][PB]), acc[r][n], 0, 0, 0)
+#define TSPL_STEP(A, SL)                     /* smallest terms first */                                                           \
+    do {                                                                                                                          \
+        TSPL_TERM(A, SL, 0, 2); TSPL_TERM(A, SL, 2, 0); TSPL_TERM(A, SL, 1, 1);                                                   \
+        TSPL_TERM(A, SL, 0, 1); TSPL_TERM(A, SL, 1, 0); TSPL_TERM(A, SL, 0, 0);                                                   \
+    } while (0)
+    load_b(0, 0);
+    load_b(1, 1);
+    st.load(0);
+    store_chunk(0, 0);
+    __syncthreads();
+    for (int c = 0; c < nchunks; c++) {
+        const int buf = c & 1;
+        const bool more = c + 1 < nchunks;               // (workgroup-uniform)
+        if (more) st.load(c + 1);
+        read_a(buf, 0, a0);
+        TSPL_STEP(a0, 0);
+        load_b(c * 2 + 2, 0);
+        read_a(buf, 1, a1);
+        if (more) store_chunk(c + 1, buf ^ 1);           // the split of the next chunk covers the LDS reads' latency
+        TSPL_STEP(a1, 1);
+        load_b(c * 2 + 3, 1);
+        __syncthreads();
+    }
+#undef TSPL_STEP
+#undef TSPL_TERM
+}
+
+// forward, plain rows: the staged value is the raw row or relu(y_prev * scale + shift), train_fwd_kernel's prologue
+struct TrainFwdStage {
+    const float* arow[4];
+    const float *ps_p, *pb_p;                             // NULL: raw rows
+    float4 ra[4], ps, pb;
+    __device__ __forceinline__ void load(int c) {
+        if (ps_p) { ps = ld4(ps_p + c * MLP_BK); pb = ld4(pb_p + c * MLP_BK); }
+#pragma unroll
+        for (int u = 0; u < 4; u++) ra[u] = ld4(arow[u] + c * MLP_BK);
+    }
+    __device__ __forceinline__ float4 value(int u, int) const {
+        float4 v = ra[u];
+        if (ps_p) {
+            v.x = fmaxf(v.x * ps.x + pb.x, 0.f); v.y = fmaxf(v.y * ps.y + pb.y, 0.f);
+            v.z = fmaxf(v.z * ps.z + pb.z, 0.f); v.w = fmaxf(v.w * ps.w + pb.w, 0.f);
+        }
+        return v;
+    }
+};
+// T.P.wsplit: the split image of W (chain = 0), K a multiple of 32, 16-byte aligned rows
+template <int WNB>
+__global__ __launch_bounds__(MLP_THREADS, 2) void train_fwd_s_kernel(const TrainFwd T) {
+    MlpParams P = T.P;
+    P.rows = effective_rows(T.P);
+    const long row0 = (long)blockIdx.x * MLP_BM;
+    const int nb0 = blockIdx.y * 2 * WNB;
+    if (row0 >= P.rows) return;                           // (device-side row count: tiles past the live rows exit at once)
+    __shared__ __attribute__((aligned(16))) unsigned char Ls[2 * 3 * SPL_PLANE];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c4 = tid & 7, r0 = tid >> 3;
+    TrainFwdStage st;
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        long grow = row0 + r0 + 32 * u;
+        if (grow >= P.rows) grow = P.rows - 1;            // clamped: results of dead rows are never stored or counted
+        st.arow[u] = P.in + grow * P.ld_in + c4 * 4;
+    }
+    st.ps_p = T.pro_scale ? T.pro_scale + c4 * 4 : nullptr;
+    st.pb_p = T.pro_scale ? T.pro_shift + c4 * 4 : nullptr;
+    f32x16 acc[2][WNB];
+    train_s_tile<WNB>(st, reinterpret_cast<const uint4*>(P.wsplit), P.K / 16, P.NB, nb0, tid, Ls, acc);
+    const int wm = wave >> 1, wn = wave & 1;
+    train_fwd_epilogue<WNB>(T, P, acc, row0, nb0, wm, wn, lane, (nb0 + wn * WNB) < P.NB);
+}
+
+// dgrad: the staged value is dy, rebuilt from (G, y, cst) exactly as train_dgrad_kernel stages it
+template <int POOL>
+struct TrainDgradStage {
+    const TrainBwd* T;
+    int grow[4], ggrp[4];                                 // (rows < 2^31, train_dgrad_split_ok: eight registers the wide pooled form needs)
+    int gslot[4], c4;
+    float rm[4];
+    float4 rg[4], ry[4], sc, sh, mu, is, c1, c2;
+    uchar4 rarg[4];
+    __device__ __forceinline__ void load(int c) {
+        const TrainBwd& B = *T;
+        const int k = c * MLP_BK + c4 * 4;                // (N is a multiple of 32: always inside)
+        sc = ld4(B.cst + k); sh = ld4(B.cst + B.ld_c + k); mu = ld4(B.cst + 2 * B.ld_c + k); is = ld4(B.cst + 3 * B.ld_c + k);
+        c1 = ld4(B.cst + 4 * B.ld_c + k); c2 = ld4(B.cst + 5 * B.ld_c + k);
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            rg[u] = ld4(B.G + ggrp[u] * (long)B.ldG + k);
+            if (POOL != 0) rarg[u] = *reinterpret_cast<const uchar4*>(B.arg + ggrp[u] * (long)B.N + k);
+            ry[u] = ld4(B.y + grow[u] * (long)B.ld_y + k);
         }
     }
+    __device__ __forceinline__ float4 value(int u, int) const {
+        float4 g = rg[u];
+        if (POOL != 0) {
+            const int sl = gslot[u];
+            g.x = rarg[u].x == sl ? g.x : 0.f; g.y = rarg[u].y == sl ? g.y : 0.f;
+            g.z = rarg[u].z == sl ? g.z : 0.f; g.w = rarg[u].w == sl ? g.w : 0.f;
+        }
+        return bwd_dy4(g, ry[u], sc, sh, mu, is, c1, c2, rm[u]);
+    }
+};
+struct TrainDgradS {
+    TrainDgrad D;                 // wpack unused; KB = N / 8
+    const uint4* wsplit;          // the split image of W^T (Kin x N, chain = 0), N a multiple of 32
+};
+template <int WNB, int POOL>
+__global__ __launch_bounds__(MLP_THREADS, 2) void train_dgrad_s_kernel(const TrainDgradS S) {
+    const TrainDgrad& D = S.D;
+    const TrainBwd& T = D.B;
+    const long row0 = (long)blockIdx.x * MLP_BM;
+    const int nb0 = blockIdx.y * 2 * WNB;
+    const long live = bwd_live_rows(T);
+    if (row0 >= live) return;                             // (device-side row count)
+    __shared__ __attribute__((aligned(16))) unsigned char Ls[2 * 3 * SPL_PLANE];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r0 = tid >> 3;
+    TrainDgradStage<POOL> st;
+    st.T = &T; st.c4 = tid & 7;
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        long gl = row0 + r0 + 32 * u;
+        if (gl >= live) gl = live - 1;
+        const int g = (int)gl;
+        st.grow[u] = g;
+        st.rm[u] = T.mult ? T.mult[g] : 1.f;
+        if (POOL == 2) { st.ggrp[u] = T.row_grp[g]; st.gslot[u] = g - T.seg_off[st.ggrp[u]]; }
+        else if (POOL == 1) { st.ggrp[u] = g / T.pool_ns; st.gslot[u] = g - st.ggrp[u] * T.pool_ns; }
+        else { st.ggrp[u] = g; st.gslot[u] = 0; }
+    }
+    f32x16 acc[2][WNB];
+    train_s_tile<WNB>(st, S.wsplit, T.N / 16, D.NB, nb0, tid, Ls, acc);
+    const int wm = wave >> 1, wn = wave & 1;
+    train_dgrad_epilogue<WNB>(D, acc, row0, nb0, wm, wn, lane, live, (nb0 + wn * WNB) < D.NB);
+}
+
+// the split image (pack_weight_split_kernel's chain = 0 layout) of W^T for dgrad: "row" kin of the image is column t_col0 + kin of
+// W (Nout x K, torch layout), its k index is W's row; a grouped layer 0 leaves its three xyz columns out (t_col0 = 3)
+__global__ void train_pack_split_t_kernel(const float* __restrict__ w, int Nout, int K, int kin_t, int t_col0, int KS, int NB,
+                                          uint4* __restrict__ img) {
+    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;            // one thread per (column block, k-step, lane)
+    if (e >= (long)NB * KS * 64) return;
+    const int lane = (int)(e & 63);
+    const long blk = e >> 6;
+    const int ks = (int)(blk % KS), nb = (int)(blk / KS);
+    const int kin = nb * 32 + (lane & 31), hh = lane >> 5;
+    uint32_t b[3][8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const int n = ks * 16 + 8 * hh + i;
+        const float v = (kin < kin_t && n < Nout) ? w[(long)n * K + t_col0 + kin] : 0.f;
+        split3(v, b[0][i], b[1][i], b[2][i]);
+    }
+#pragma unroll
+    for (int p = 0; p < 3; p++)
+        img[(blk * 3 + p) * 64 + lane] = make_uint4(bf16_pair(b[p][0], b[p][1]), bf16_pair(b[p][2], b[p][3]),
+                                                    bf16_pair(b[p][4], b[p][5]), bf16_pair(b[p][6], b[p][7]));
 }
 
 // dW[n, k] = sum_r dy[r, n] * a[r, k].  Both operands go from global memory straight into MFMA operand registers: per step a wave
@@ -1285,6 +1535,15 @@ static size_t train_work_layout(int64_t rows, int nl, const prcnn_train_layer_t*
     return off;
 }
 
+// Which layers the split-bf16 kernels take (decided here, per layer; everything else keeps its fp32 kernel):
+//   forward  the layer's source is plain rows (every layer l > 0, layer 0 of a plain source), K % 32 == 0, 16-byte aligned rows
+//            (and prologue tables)
+//   dgrad    the layer's N % 32 == 0 (the reduction runs over the layer's output channels); fewer than 2^31 rows
+static bool train_fwd_split_ok(int mode, int K, const float* in, int ld_in, const float* pro_scale, const float* pro_shift) {
+    return mode == MODE_PLAIN && K % 32 == 0 && K >= 32 && ld_in % 4 == 0 && aligned16(in) && aligned16(pro_scale) && aligned16(pro_shift);
+}
+static bool train_dgrad_split_ok(int N, long rows) { return N % 32 == 0 && N >= 32 && rows < (1L << 31); }
+
 static int train_check_layers(const prcnn_train_layer_t* L, int nl) {
     PRCNN_REQUIRE(L && nl > 0 && nl <= 8, "prcnn_train_stack: 1..8 layers");
     for (int l = 0; l < nl; l++) {
@@ -1301,9 +1560,11 @@ PRCNN_API size_t prcnn_train_stack_work_bytes(int64_t rows, const prcnn_train_la
     return train_work_layout(rows, nl, layers, K0, backward != 0, nullptr, nullptr);
 }
 
-PRCNN_API int prcnn_train_stack_fwd(const prcnn_train_src_t* src, const prcnn_train_layer_t* L, int nl, int pool_ns, float* a_dump,
-                                    int ld_dump, float* out, int ld_out, int col_off, uint8_t* arg, void* work, size_t work_bytes,
-                                    prcnn_stream_t stream) {
+// wsplit: NULL (prcnn_train_stack_fwd: every layer on the fp32 pipe, the launches of every release so far) or nl split-image
+// pointers (prcnn_train_stack_fwd_split); an eligible layer with a non-NULL entry runs train_fwd_s_kernel
+static int train_stack_fwd_run(const prcnn_train_src_t* src, const prcnn_train_layer_t* L, int nl, int pool_ns, float* a_dump, int ld_dump,
+                               float* out, int ld_out, int col_off, uint8_t* arg, void* const* wsplit, void* work, size_t work_bytes,
+                               prcnn_stream_t stream) {
     TrainFwd T0 = {};
     int rc = train_fill_src(src, T0.P);
     if (rc) return rc;
@@ -1363,7 +1624,16 @@ PRCNN_API int prcnn_train_stack_fwd(const prcnn_train_src_t* src, const prcnn_tr
     } while (0)
         const bool fastp = mode == MODE_PLAIN && P.vec_a && K % 4 == 0 && K >= 4 && P.ld_in % 4 == 0 && aligned16(P.in) &&
                            (!T.pro_scale || l > 0) && !sw_present(SW_TRAIN_FWD_GENERIC);
-        if (fastp) {
+        void* ws = wsplit ? wsplit[l] : nullptr;
+        if (ws && train_fwd_split_ok(mode, K, P.in, P.ld_in, T.pro_scale, T.pro_shift)) {
+            PRCNN_REQUIRE(aligned16(ws), "prcnn_train_stack_fwd_split: layer %d: split image not 16-byte aligned", l);
+            const int KS = K / 16;
+            hipLaunchKernelGGL(pack_weight_split_kernel, dim3(prcnn_divup((long)P.NB * KS * 64, 256)), dim3(256), 0, s, L[l].W, N, K, KS, P.NB, 0,
+                               reinterpret_cast<uint4*>(ws));
+            P.wsplit = ws;
+            if (wide) hipLaunchKernelGGL((train_fwd_s_kernel<2>), grid, dim3(MLP_THREADS), 0, s, T);
+            else hipLaunchKernelGGL((train_fwd_s_kernel<1>), grid, dim3(MLP_THREADS), 0, s, T);
+        } else if (fastp) {
             if (wide) hipLaunchKernelGGL((train_fwd_kernel<MODE_PLAIN, 2, true>), grid, dim3(MLP_THREADS), 0, s, T);
             else hipLaunchKernelGGL((train_fwd_kernel<MODE_PLAIN, 1, true>), grid, dim3(MLP_THREADS), 0, s, T);
         } else if (mode == MODE_PLAIN) TRAIN_FWD(MODE_PLAIN);
@@ -1388,14 +1658,28 @@ PRCNN_API int prcnn_train_stack_fwd(const prcnn_train_src_t* src, const prcnn_tr
     return PRCNN_OK;
 }
 
+PRCNN_API int prcnn_train_stack_fwd(const prcnn_train_src_t* src, const prcnn_train_layer_t* L, int nl, int pool_ns, float* a_dump,
+                                    int ld_dump, float* out, int ld_out, int col_off, uint8_t* arg, void* work, size_t work_bytes,
+                                    prcnn_stream_t stream) {
+    return train_stack_fwd_run(src, L, nl, pool_ns, a_dump, ld_dump, out, ld_out, col_off, arg, nullptr, work, work_bytes, stream);
+}
+PRCNN_API int prcnn_train_stack_fwd_split(const prcnn_train_src_t* src, const prcnn_train_layer_t* L, int nl, int pool_ns, float* a_dump,
+                                          int ld_dump, float* out, int ld_out, int col_off, uint8_t* arg, void* const* wsplit, void* work,
+                                          size_t work_bytes, prcnn_stream_t stream) {
+    PRCNN_REQUIRE(wsplit, "prcnn_train_stack_fwd_split: null split-image table");
+    return train_stack_fwd_run(src, L, nl, pool_ns, a_dump, ld_dump, out, ld_out, col_off, arg, wsplit, work, work_bytes, stream);
+}
+
 template <int KQ, int NQ, int WK, int WN>
 static void launch_wgrad(const TrainWgrad& W, const WgradPlan& p, hipStream_t s) {
     hipLaunchKernelGGL((train_wgrad_kernel<KQ, NQ, WK, WN>), dim3(p.splits, p.tiles_k, p.tiles_n), dim3(256), 0, s, W);
 }
 
-PRCNN_API int prcnn_train_stack_bwd(const prcnn_train_src_t* src, const prcnn_train_layer_t* L, int nl, int pool_ns, const float* a_dump,
-                                    int ld_dump, const float* gout, int ld_gout, const uint8_t* arg, float* gin, int ld_gin, void* work,
-                                    size_t work_bytes, prcnn_stream_t stream) {
+// wsplit_t: NULL (prcnn_train_stack_bwd) or nl pointers to split images of W^T (prcnn_train_stack_bwd_split); a layer whose dgrad is
+// eligible and whose entry is non-NULL runs train_dgrad_s_kernel
+static int train_stack_bwd_run(const prcnn_train_src_t* src, const prcnn_train_layer_t* L, int nl, int pool_ns, const float* a_dump,
+                               int ld_dump, const float* gout, int ld_gout, const uint8_t* arg, float* gin, int ld_gin, void* const* wsplit_t,
+                               void* work, size_t work_bytes, prcnn_stream_t stream) {
     PRCNN_REQUIRE(src && gout, "prcnn_train_stack_bwd: null pointer");
     int rc = train_check_layers(L, nl);
     if (rc) return rc;
@@ -1475,14 +1759,41 @@ PRCNN_API int prcnn_train_stack_bwd(const prcnn_train_src_t* src, const prcnn_tr
         if (wide) hipLaunchKernelGGL((train_dgrad_kernel<2, POOL>), grid, dim3(MLP_THREADS), 0, s, D);           \
         else hipLaunchKernelGGL((train_dgrad_kernel<1, POOL>), grid, dim3(MLP_THREADS), 0, s, D);                \
     } while (0)
-        if (T.pool_ns == 0) TRAIN_DGRAD(0);
+#define TRAIN_DGRAD_S(POOL)                                                                                      \
+    do {                                                                                                         \
+        if (wide) hipLaunchKernelGGL((train_dgrad_s_kernel<2, POOL>), grid, dim3(MLP_THREADS), 0, s, DS);        \
+        else hipLaunchKernelGGL((train_dgrad_s_kernel<1, POOL>), grid, dim3(MLP_THREADS), 0, s, DS);             \
+    } while (0)
+        void* wst = wsplit_t ? wsplit_t[l] : nullptr;
+        if (wst && train_dgrad_split_ok(N, rows)) {
+            PRCNN_REQUIRE(aligned16(wst), "prcnn_train_stack_bwd_split: layer %d: split image not 16-byte aligned", l);
+            const int KS = N / 16;
+            hipLaunchKernelGGL(train_pack_split_t_kernel, dim3(prcnn_divup((long)D.NB * KS * 64, 256)), dim3(256), 0, s, L[l].W, N, K, D.Kin,
+                               K - D.Kin, KS, D.NB, reinterpret_cast<uint4*>(wst));
+            TrainDgradS DS = {D, reinterpret_cast<const uint4*>(wst)};
+            if (T.pool_ns == 0) TRAIN_DGRAD_S(0);
+            else if (T.pool_ns > 0) TRAIN_DGRAD_S(1);
+            else TRAIN_DGRAD_S(2);
+        } else if (T.pool_ns == 0) TRAIN_DGRAD(0);
         else if (T.pool_ns > 0) TRAIN_DGRAD(1);
         else TRAIN_DGRAD(2);
+#undef TRAIN_DGRAD_S
 #undef TRAIN_DGRAD
         G = D.out; ldG = D.ld_out;
     }
     PRCNN_LAUNCH_CHECK("prcnn_train_stack_bwd");
     return PRCNN_OK;
+}
+PRCNN_API int prcnn_train_stack_bwd(const prcnn_train_src_t* src, const prcnn_train_layer_t* L, int nl, int pool_ns, const float* a_dump,
+                                    int ld_dump, const float* gout, int ld_gout, const uint8_t* arg, float* gin, int ld_gin, void* work,
+                                    size_t work_bytes, prcnn_stream_t stream) {
+    return train_stack_bwd_run(src, L, nl, pool_ns, a_dump, ld_dump, gout, ld_gout, arg, gin, ld_gin, nullptr, work, work_bytes, stream);
+}
+PRCNN_API int prcnn_train_stack_bwd_split(const prcnn_train_src_t* src, const prcnn_train_layer_t* L, int nl, int pool_ns, const float* a_dump,
+                                          int ld_dump, const float* gout, int ld_gout, const uint8_t* arg, float* gin, int ld_gin,
+                                          void* const* wsplit_t, void* work, size_t work_bytes, prcnn_stream_t stream) {
+    PRCNN_REQUIRE(wsplit_t, "prcnn_train_stack_bwd_split: null split-image table");
+    return train_stack_bwd_run(src, L, nl, pool_ns, a_dump, ld_dump, gout, ld_gout, arg, gin, ld_gin, wsplit_t, work, work_bytes, stream);
 }
 
 PRCNN_API int prcnn_group_rows_grad(const float* G, int ldG, const int32_t* idx, int B, int M, int ns, int C, int N, float* dfeat,

@@ -193,6 +193,53 @@ def rpn_loss_rows(dev, B=16, N=16384, rounds=5):
         print(json.dumps(d), flush=True)
 
 
+def train_split_rows(dev, B=16, rounds=5):
+    """`train stack fwd+bwd`: one SharedMLPTrain forward + backward at two RPN training shapes -- an SA2-like padding-free stack
+    (4096 -> 1024 centres, radius 2.5, nsample 32, [96 + 3, 64, 96, 128]) and an FP-like plain stack (B x 16 384 rows, [256, 128, 128]) -- with
+    train_mlp.TRAIN_SPLIT 0 (fp32 MFMA throughout) against 6 (split-bf16 forward / dgrad on the eligible layers), alternated in one
+    process; per setting the median, minimum and maximum over `rounds` windows of 20 calls.  `split_launches`: the per-call weight
+    split launches the setting adds."""
+    from . import train_mlp
+    g = torch.Generator().manual_seed(5)
+    xyz = rpn.synthetic_clouds(B, 16384, device=dev)
+    xyz1 = ops.gather_rows(xyz, ops.furthest_point_sample(xyz, 4096))
+    nx2 = ops.gather_rows(xyz1, ops.furthest_point_sample(xyz1, 1024))
+    idx = ops.ball_query(2.5, 32, xyz1, nx2)          # (radius 1.0 finds the centre alone among these uniform FPS samples)
+    gr = train_mlp.GroupRows(idx, nx2, 4096)
+    stacks = (("SA2-like padding-free", train_mlp.Source("group", xyz=xyz1.reshape(1, -1, 3), rows=gr), 32,
+               torch.randn(B, 4096, 96, generator=g).to(dev), [99, 64, 96, 128], B * 1024),
+              ("FP-like plain", train_mlp.Source("plain"), 0, torch.randn(B * 16384, 256, generator=g).to(dev), [256, 128, 128], B * 16384))
+    for name, src, ns, x0, chans, groups in stacks:
+        x0.requires_grad_(True)
+        bns = [torch.nn.BatchNorm1d(n).to(dev).train() for n in chans[1:]]
+        params = []
+        for k, n, bn in zip(chans[:-1], chans[1:], bns):
+            params += [(torch.randn(n, k, generator=g) / k ** 0.5).to(dev).requires_grad_(True), bn.weight, bn.bias]
+        gout = torch.randn(groups, chans[-1], generator=g).to(dev)
+
+        def step():
+            x0.grad = None
+            train_mlp.SharedMLPTrain.apply(src, bns, ns, x0, None, *params).backward(gout)
+        times = {0: [], 6: []}
+        keep = train_mlp.TRAIN_SPLIT
+        try:
+            for _ in range(rounds):
+                for terms in (0, 6):
+                    train_mlp.TRAIN_SPLIT = terms
+                    times[terms].append(timeit(step))
+        finally:
+            train_mlp.TRAIN_SPLIT = keep
+        rows = int(gr.rows_dev.item()) if ns else groups
+        fwd_split = sum(1 for l, k in enumerate(chans[:-1]) if k % 32 == 0 and (l > 0 or src.mode == "plain"))
+        bwd_split = sum(1 for n in chans[1:] if n % 32 == 0)
+        for terms in (0, 6):
+            t = sorted(times[terms])
+            print(json.dumps({"op": "train stack fwd+bwd (%s)" % ("split-bf16 x 6" if terms else "fp32 MFMA"),
+                              "shape": "%s: B%d, %d rows, %s" % (name, B, rows, chans), "median_us": round(t[len(t) // 2] * 1e6, 1),
+                              "min_us": round(t[0] * 1e6, 1), "max_us": round(t[-1] * 1e6, 1),
+                              "split_launches": (fwd_split + bwd_split) if terms else 0}), flush=True)
+
+
 def optimizer_rows(dev, rounds=5):
     """`optimizer step`: one optim.OneCycleAdam.step() -- gradient-norm clip, decoupled decay, Adam, schedule -- over the parameter
     lists of rpn.RPN() and of the RCNN net, the composed torch route against the two launches of csrc/optim.hip, alternated in one
@@ -524,7 +571,7 @@ def eval_loop_rows(dev, B=16, nbatches=3, rounds=5):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
-    ap.add_argument("--only", default=None, help="run one row family only: eval_stats | optimizer | result_writer | eval_loop")
+    ap.add_argument("--only", default=None, help="run one row family only: eval_stats | optimizer | train_split | result_writer | eval_loop")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     if args.only == "result_writer":
@@ -539,6 +586,9 @@ def main():
     if args.only == "optimizer":
         optimizer_rows(dev)
         optimizer_mode_rows(dev)
+        return
+    if args.only == "train_split":
+        train_split_rows(dev)
         return
     B = 8 if args.quick else 32
     N = 16384
@@ -664,6 +714,8 @@ def main():
     rpn_loss_rows(dev)
     # ---- the RCNN training loss and its gradient: composed torch against the device passes (csrc/rcnn_loss.hip)
     rcnn_loss_rows(dev)
+    # ---- a training stack forward + backward: fp32 MFMA against the opt-in split-bf16 forward / dgrad (csrc/mlp_train.h)
+    train_split_rows(dev, B=4 if args.quick else 16)
     # ---- the adam_onecycle parameter update: composed torch against the two launches of csrc/optim.hip
     optimizer_rows(dev)
     # ---- TRAIN.OPTIMIZER adam and sgd: clip_grad_norm_ + torch's foreach step against the same two launches

@@ -26,6 +26,13 @@ from .ops import _p, _stream
 
 _F32 = torch.float32
 INTERP_GRAD_GATHER = os.environ.get("PRCNN_INTERP_GRAD_GATHER", "1") != "0"      # A/B switch: 0 = atomics
+# Arithmetic of the training stacks' forward / dgrad GEMMs (read once here, like ops.MLP_SPLIT_TERMS from PRCNN_MLP_SPLIT; not a
+# switch of the library): 0 (default) = fp32 MFMA throughout; 6 (PRCNN_TRAIN_SPLIT=1 or 6) = the eligible layers on split-bf16 x 6
+# (csrc/mlp_train.h: train_fwd_s_kernel / train_dgrad_s_kernel); wgrad and the ineligible layers stay on fp32 MFMA
+_TRAIN_SPLIT_ENV = os.environ.get("PRCNN_TRAIN_SPLIT", "")
+if _TRAIN_SPLIT_ENV not in ("", "0", "1", "6"):
+    raise RuntimeError("PRCNN_TRAIN_SPLIT=%r: 1 or 6 = six split-bf16 terms, 0 / unset = fp32 MFMA" % _TRAIN_SPLIT_ENV)
+TRAIN_SPLIT = 6 if _TRAIN_SPLIT_ENV in ("1", "6") else 0
 # bench.py's accounting: when a list, every stack forward appends (rows (int) or live-row counter (device tensor), [(K, N) per layer],
 # first layer takes an input gradient) -- nothing is read back here
 FLOP_LOG = None
@@ -170,7 +177,7 @@ def _wpack_floats(nout, k):
 class _Stack:
     """device buffers + the prcnn_train_layer_t array of one stack invocation (kept alive by the autograd context)"""
 
-    def __init__(self, params, bns, rows, K0, kin0, need_x, dev):
+    def __init__(self, params, bns, rows, K0, kin0, need_x, dev, plain=False):
         nl = len(bns)
         nout = [int(params[3 * l].shape[0]) for l in range(nl)]
         ks = [K0] + nout[:-1]
@@ -212,6 +219,26 @@ class _Stack:
             Ly.dW, Ly.dgamma, Ly.dbeta = _p(dW), (_p(dg) if gamma is not None else None), (_p(db) if beta is not None else None)
             self.grad_views.append((dW, dg if gamma is not None else None, db if beta is not None else None))
 
+        self.wsplit = self.wsplit_t = None
+        if TRAIN_SPLIT:
+            self._split_images(kins, wt_need, plain, dev)
+
+    def _split_images(self, kins, wt_need, plain, dev):
+        """scratch for the split weight images of the layers the split kernels can take (the library decides again, on the
+        pointers it sees: include/prcnn_pointops.h), one allocation; NULL entries keep a layer on the fp32 pipe"""
+        L = _cabi.lib()
+        nl, nout, ks = self.nl, self.nout, self.ks
+        fsz = [L.prcnn_wsplit_bytes(nout[l], ks[l]) if (ks[l] % 32 == 0 and (l > 0 or plain)) else 0 for l in range(nl)]
+        tsz = [L.prcnn_wsplit_bytes(kins[l], nout[l]) if (nout[l] % 32 == 0 and wt_need[l] and kins[l] > 0) else 0 for l in range(nl)]
+        self.sbuf = torch.empty((sum(fsz) + sum(tsz) + 16,), dtype=torch.uint8, device=dev)
+        self.wsplit, self.wsplit_t = (ctypes.c_void_p * nl)(), (ctypes.c_void_p * nl)()
+        o = (self.sbuf.data_ptr() + 15) // 16 * 16
+        for l in range(nl):
+            self.wsplit[l] = o if fsz[l] else None
+            o += fsz[l]
+            self.wsplit_t[l] = o if tsz[l] else None
+            o += tsz[l]
+
     def work(self, K0, backward, dev):
         nbytes = _cabi.lib().prcnn_train_stack_work_bytes(self.rows, self.layers, self.nl, K0, 1 if backward else 0)
         return torch.empty((nbytes + 256,), dtype=torch.uint8, device=dev), nbytes
@@ -244,7 +271,7 @@ class SharedMLPTrain(torch.autograd.Function):
         ns = pool_ns if pool_ns and pool_ns > 1 else 1
         flat = getattr(src, "rows", None)
         with torch.no_grad():
-            st = _Stack(params, bns, rows, K0, kin0, need_x, dev)
+            st = _Stack(params, bns, rows, K0, kin0, need_x, dev, plain=src.mode == "plain")
             a_dump, ld_dump = None, 0
             if src.mode != "plain":
                 ld_dump = _up(K0, 4)
@@ -253,8 +280,12 @@ class SharedMLPTrain(torch.autograd.Function):
             out = torch.empty((groups, N), dtype=_F32, device=dev)
             arg = torch.empty((groups, N), dtype=torch.uint8, device=dev) if (ns > 1 or flat is not None) else None
             work, nbytes = st.work(K0, False, dev)
-            _cabi.check(L.prcnn_train_stack_fwd(ctypes.byref(S), st.layers, nl, ns, _p(a_dump), ld_dump, _p(out), N, 0, _p(arg),
-                                                _aligned_ptr(work), nbytes, _stream()), "prcnn_train_stack_fwd")
+            if st.wsplit is not None:
+                _cabi.check(L.prcnn_train_stack_fwd_split(ctypes.byref(S), st.layers, nl, ns, _p(a_dump), ld_dump, _p(out), N, 0, _p(arg),
+                                                          st.wsplit, _aligned_ptr(work), nbytes, _stream()), "prcnn_train_stack_fwd_split")
+            else:
+                _cabi.check(L.prcnn_train_stack_fwd(ctypes.byref(S), st.layers, nl, ns, _p(a_dump), ld_dump, _p(out), N, 0, _p(arg),
+                                                    _aligned_ptr(work), nbytes, _stream()), "prcnn_train_stack_fwd")
             for bn in bns:
                 if bn is not None:
                     bn.num_batches_tracked += 1
@@ -280,8 +311,13 @@ class SharedMLPTrain(torch.autograd.Function):
             ld_gin = _up(ctx.kin0, 4)
             gin = torch.empty((rows, ld_gin), dtype=_F32, device=dev)
         work, nbytes = st.work(ctx.K0, True, dev)
-        _cabi.check(L.prcnn_train_stack_bwd(ctypes.byref(ctx.S), st.layers, st.nl, ctx.ns, _p(ctx.a_dump), ctx.ld_dump, _p(G), G.stride(0),
-                                            _p(ctx.arg), _p(gin), ld_gin, _aligned_ptr(work), nbytes, _stream()), "prcnn_train_stack_bwd")
+        if st.wsplit_t is not None:
+            _cabi.check(L.prcnn_train_stack_bwd_split(ctypes.byref(ctx.S), st.layers, st.nl, ctx.ns, _p(ctx.a_dump), ctx.ld_dump, _p(G),
+                                                      G.stride(0), _p(ctx.arg), _p(gin), ld_gin, st.wsplit_t, _aligned_ptr(work), nbytes,
+                                                      _stream()), "prcnn_train_stack_bwd_split")
+        else:
+            _cabi.check(L.prcnn_train_stack_bwd(ctypes.byref(ctx.S), st.layers, st.nl, ctx.ns, _p(ctx.a_dump), ctx.ld_dump, _p(G), G.stride(0),
+                                                _p(ctx.arg), _p(gin), ld_gin, _aligned_ptr(work), nbytes, _stream()), "prcnn_train_stack_bwd")
         grads = []
         params = ctx.keep[2]
         for l in range(st.nl):
