@@ -12,6 +12,7 @@
     kitti_eval_ref.npz -- outputs of the reference's own tools/kitti_object_eval_python evaluator (result strings, AP
         dictionaries, precision / recall arrays, per-frame overlaps, rotate_iou_gpu_eval matrices) on seeded synthetic
         annotations; numba is stubbed to identity (ref_kitti_eval.py), the code that runs is the reference's.
+        (kitti_stats_ref.npz, the same evaluator on crowded and adversarial frames, is written by make_kitti_stats_golden.py.)
     pointnet2_oracle.npz -- outputs of the CPU oracle (oracle/prcnn_oracle.c) for the PointNet++ ops, whose
         reference source is an empty git submodule (parity unpinned: these pin the ORACLE's behaviour across
         refactors, not the reference's).
