@@ -811,6 +811,19 @@ int prcnn_train_stack_fwd_split(const prcnn_train_src_t* src, const prcnn_train_
 int prcnn_train_stack_bwd_split(const prcnn_train_src_t* src, const prcnn_train_layer_t* layers, int nl, int pool_ns, const float* a_dump,
                                 int ld_dump, const float* gout, int ld_gout, const uint8_t* arg, float* gin, int ld_gin,
                                 void* const* wsplit_t, void* work, size_t work_bytes, prcnn_stream_t stream);
+/* prcnn_train_stack_bwd_split with the weight gradient of the WIDE layers on the split-bf16 x 6 arithmetic as well (opt-in; the two
+ * entry points above keep their launches).  A layer's wgrad runs train_wgrad_s_kernel where the twin runs the 128 x 128 LDS-staged
+ * fp32 kernel: K > 64 and Nout > 64, the layer's input rows 16-byte aligned with a row stride that is a multiple of 4, and
+ * PRCNN_WGRAD_DIRECT not set.  Both operands -- relu(a * scale + shift) or the raw first-layer rows, and dy rebuilt from (G, y) --
+ * are cut into three bf16 pieces after the transform; partial tiles, their fixed-order reduction (deterministic) and the workspace
+ * are the twin's.  Every other layer's wgrad, the reductions and the BatchNorm backward are the twin's launches; dgrad goes split
+ * per layer as in prcnn_train_stack_bwd_split, and a wsplit_t table of NULL entries (the table itself must not be NULL) keeps
+ * every dgrad on the fp32 pipe.
+ * Non-finite operands: nothing is recomputed on the fp32 pipe.  A dW entry whose fp32 value is non-finite comes out non-finite,
+ * possibly NaN where fp32 gives +-inf; entries whose operand rows are all finite are fp32-grade. */
+int prcnn_train_stack_bwd_wsplit(const prcnn_train_src_t* src, const prcnn_train_layer_t* layers, int nl, int pool_ns, const float* a_dump,
+                                 int ld_dump, const float* gout, int ld_gout, const uint8_t* arg, float* gin, int ld_gin,
+                                 void* const* wsplit_t, void* work, size_t work_bytes, prcnn_stream_t stream);
 /* Padding-free rows for a grouped stack (exact: ball_query pads a group with copies of its first hit; copies are identical rows).
  * prcnn_train_group_rows builds the distinct-row list deterministically (count -> exclusive scan -> fill, group order);
  * prcnn_flat_rows_grad scatters the first layer's row gradients back: dfeat[ridx[r], 0:C] += G[r, 0:C] for the live rows. */

@@ -1136,6 +1136,199 @@ static void launch_wgrad_lds(const TrainWgrad& Wg, dim3 grid, hipStream_t s) {
     else hipLaunchKernelGGL((train_wgrad_lds_kernel<POOL, MULT, false>), grid, dim3(256), 0, s, Wg);
 }
 
+// Split-bf16 x 6 twin of train_wgrad_lds_kernel (OPT-IN: prcnn_train_stack_bwd_wsplit; the fp32 kernel above stays the default).
+// Same tile, grid, partial layout, loads and transform; BOTH operands are activations, so both are cut into three bf16 pieces
+// (split3) after the transform, on their way into LDS, and both reach the MFMA with the ROW index in the lane's eight fragment
+// elements (v_mfma_f32_32x32x16_bf16: lane (h, j) holds rows 8h .. 8h+7 of channel j) -- i.e. transposed relative to the
+// channels-last rows they are loaded from.  The image is transposed planes read with 16-byte reads: a 16-row chunk, per operand
+// and piece one 4 KB plane [row half h][line 0..127][8 rows] of bf16, line = 64 wk + 32 x + j for channel 64 wk + 2 j + x of the
+// tile (the fp32 kernel's channel -> (wave half, block, lane) map, so its epilogue is this kernel's).  A wave reads a block's
+// operand as ONE ds_read_b128 per piece (32 lanes: 512 contiguous bytes, conflict-free); the staging thread (row pair rp, channel
+// quad) packs its two rows of a channel into one dword and stores it at [h][line][rp]: within a 32-lane half 8 quads x 4 row pairs,
+// two quads per bank (a 2-way ds_write_b32 conflict costs no extra cycle).  2 buffers x 2 operands x 3 planes x 4 KB = 48 KB: two
+// workgroups per CU, as the fp32 kernel.  Per chunk a wave issues 12 ds_read_b128 and 24 MFMAs (768 matrix-pipe cycles where the
+// fp32 kernel's 32 MFMAs of the same 16 rows take 2048), smallest terms first: a2 d0, a1 d1, a0 d2, a1 d0, a0 d1, a0 d0.
+// Fixed reduction order: two calls give identical bytes.
+// Non-finite operands: as for the forward / dgrad twins NOTHING is recomputed on the fp32 pipe.  The split of +-inf is (inf, NaN,
+// NaN), and here a row is a term of EVERY entry of its channels: a dW entry whose fp32 value is non-finite (one of its operand
+// values over the rows is +-inf or NaN) comes out non-finite, possibly NaN where fp32 gives +-inf; a non-finite a[r, k] reaches the
+// whole dW column k, a non-finite dy[r, n] the whole dW row n, exactly the entries that are non-finite in fp32 as well (up to
+// inf * 0).  Entries whose operand values are all finite are computed as if the others were, and meet the fp32-grade bars.
+#define WS_ROWS 16
+#define WS_PLANE 4096
+template <int POOL, bool MULT, bool PRO>
+__global__ __launch_bounds__(256, 2) void train_wgrad_s_kernel(const TrainWgrad W) {
+    const TrainBwd& T = W.B;
+    __shared__ __attribute__((aligned(16))) unsigned char Ls[2 * 2 * 3 * WS_PLANE];       // [buffer][operand a, d][piece]
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wk = wave >> 1, wn = wave & 1;
+    const int h = lane >> 5, j = lane & 31;
+    const int kt0 = blockIdx.y * 128, nt0 = blockIdx.z * 128;
+    // staging role: rows 8 rh + 2 rp + u (u = 0, 1) of the chunk, channels 4 cq .. 4 cq + 3 of the tile
+    const int rp = tid & 3, rh = (tid >> 5) & 1, cq = (tid >> 6) * 8 + ((tid >> 2) & 7);
+    const int ka = kt0 + 4 * cq, na = nt0 + 4 * cq;
+    const int kc = (ka + 4 <= W.lda) ? ka : 0, nc = (na + 4 <= T.N) ? na : 0;      // (lda and N are multiples of 4 here)
+    const float dead_n = (na + 4 <= T.N) ? 1.f : 0.f;
+    float4 ps = make_float4(1.f, 1.f, 1.f, 1.f), pb = make_float4(0.f, 0.f, 0.f, 0.f), km;
+    const bool ka_ok = ka + 4 <= W.lda;
+    km.x = (ka_ok && ka < W.K) ? 1.f : 0.f; km.y = (ka_ok && ka + 1 < W.K) ? 1.f : 0.f;
+    km.z = (ka_ok && ka + 2 < W.K) ? 1.f : 0.f; km.w = (ka_ok && ka + 3 < W.K) ? 1.f : 0.f;
+    if (PRO) { ps = ld4(W.pro_scale + kc); pb = ld4(W.pro_shift + kc); }
+    const float4 sc = ld4(T.cst + nc), sh = ld4(T.cst + T.ld_c + nc), mu = ld4(T.cst + 2 * T.ld_c + nc), is = ld4(T.cst + 3 * T.ld_c + nc);
+    const float4 c1 = ld4(T.cst + 4 * T.ld_c + nc), c2 = ld4(T.cst + 5 * T.ld_c + nc);
+    const long r_begin = (long)blockIdx.x * W.rows_per_split;
+    long r_end = r_begin + W.rows_per_split;
+    const long live = bwd_live_rows(T);
+    if (r_end > live) r_end = live;
+    const int nchunks = r_end > r_begin ? (int)((r_end - r_begin + WS_ROWS - 1) / WS_ROWS) : 0;
+    // channel 4 cq + i of the tile -> its line (i = 0: this value; i = 1: + 32; i = 2: + 1; i = 3: + 33), in bytes, + the row pair
+    unsigned char* const st_base = Ls + rh * (WS_PLANE / 2) + ((cq >> 4) * 64 + 2 * (cq & 15)) * 16 + rp * 4;
+    float4 ra[2], rg[2], ry[2];
+    uchar4 rarg[2];
+    int rso[2], gcur[2], gnext[2];
+    float mcur[2], mnext[2];
+    auto row_of = [&](int c, int u, bool& ok) {
+        long rr = r_begin + (long)c * WS_ROWS + 8 * rh + 2 * rp + u;
+        ok = rr < r_end;
+        return ok ? rr : r_end - 1;
+    };
+    auto load_meta = [&](int c, int (&g)[2], float (&m)[2]) {
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+            bool ok;
+            const long rr = row_of(c, u, ok);
+            g[u] = POOL == 2 ? T.row_grp[rr] : 0;
+            m[u] = MULT ? T.mult[rr] : 1.f;
+        }
+    };
+    auto load_data = [&](int c, const int (&g)[2]) {
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+            bool ok;
+            const long rr = row_of(c, u, ok);
+            ra[u] = ld4(W.a + rr * (long)W.lda + kc);
+            ry[u] = ld4(T.y + rr * (long)T.ld_y + nc);
+            if (POOL == 0) {
+                rg[u] = ld4(T.G + rr * (long)T.ldG + nc);
+            } else {
+                const long grp = POOL == 2 ? (long)g[u] : rr / T.pool_ns;
+                rg[u] = ld4(T.G + grp * (long)T.ldG + nc);
+                rarg[u] = *reinterpret_cast<const uchar4*>(T.arg + grp * (long)T.N + nc);
+                rso[u] = POOL == 2 ? (int)rr - T.seg_off[grp] : (int)(rr - grp * T.pool_ns);
+            }
+        }
+    };
+    auto pin4 = [](float4& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); };
+    // the two rows' values of one channel: three dwords (bf16 pairs, the even row in the low half) into the three planes
+    auto put = [&](unsigned char* q, float v0, float v1) {
+        uint32_t b0[3], b1[3];
+        split3(v0, b0[0], b0[1], b0[2]);
+        split3(v1, b1[0], b1[1], b1[2]);
+#pragma unroll
+        for (int p = 0; p < 3; p++) *reinterpret_cast<uint32_t*>(q + p * WS_PLANE) = bf16_pair(b0[p], b1[p]);
+    };
+    auto store_chunk = [&](int c, int buf, const float (&m)[2]) {
+        // (the optimiser otherwise hoists this arithmetic -- and with it the wait for the chunk's loads -- above the MFMA loop)
+#pragma unroll
+        for (int u = 0; u < 2; u++) { pin4(ra[u]); pin4(rg[u]); pin4(ry[u]); }
+        float4 a[2], d[2];
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+            bool ok;
+            (void)row_of(c, u, ok);
+            a[u] = ra[u];
+            if (PRO) { a[u].x = fmaxf(a[u].x * ps.x + pb.x, 0.f); a[u].y = fmaxf(a[u].y * ps.y + pb.y, 0.f); a[u].z = fmaxf(a[u].z * ps.z + pb.z, 0.f); a[u].w = fmaxf(a[u].w * ps.w + pb.w, 0.f); }
+            const float v = ok ? 1.f : 0.f;                       // rows past the range and channels past K contribute zero
+            a[u].x *= km.x * v; a[u].y *= km.y * v; a[u].z *= km.z * v; a[u].w *= km.w * v;
+            float4 g = rg[u];
+            if (POOL != 0) {
+                const int sl = rso[u];
+                g.x = rarg[u].x == sl ? g.x : 0.f; g.y = rarg[u].y == sl ? g.y : 0.f;
+                g.z = rarg[u].z == sl ? g.z : 0.f; g.w = rarg[u].w == sl ? g.w : 0.f;
+            }
+            d[u] = bwd_dy4(g, ry[u], sc, sh, mu, is, c1, c2, m[u]);
+            d[u].x *= dead_n; d[u].y *= dead_n; d[u].z *= dead_n; d[u].w *= dead_n;
+        }
+        unsigned char* qa = st_base + buf * (6 * WS_PLANE);
+        unsigned char* qd = qa + 3 * WS_PLANE;
+        put(qa, a[0].x, a[1].x); put(qa + 32 * 16, a[0].y, a[1].y); put(qa + 16, a[0].z, a[1].z); put(qa + 33 * 16, a[0].w, a[1].w);
+        put(qd, d[0].x, d[1].x); put(qd + 32 * 16, d[0].y, d[1].y); put(qd + 16, d[0].z, d[1].z); put(qd + 33 * 16, d[0].w, d[1].w);
+    };
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int x = 0; x < 2; x++)
+#pragma unroll
+        for (int z = 0; z < 2; z++) acc[x][z] = (f32x16){0};
+    if (nchunks > 0) {
+        load_meta(0, gcur, mcur);
+        load_data(0, gcur);
+        load_meta(min(1, nchunks - 1), gnext, mnext);
+        store_chunk(0, 0, mcur);
+        __syncthreads();
+        const unsigned char* const a_rd = Ls + h * (WS_PLANE / 2) + (wk * 64 + j) * 16;
+        const unsigned char* const d_rd = Ls + 3 * WS_PLANE + h * (WS_PLANE / 2) + (wn * 64 + j) * 16;
+        for (int c = 0; c < nchunks; c++) {
+            const int buf = c & 1;
+            const int c1n = min(c + 1, nchunks - 1);
+#pragma unroll
+            for (int u = 0; u < 2; u++) { gcur[u] = gnext[u]; mcur[u] = mnext[u]; }
+            load_data(c1n, gcur);
+            load_meta(min(c + 2, nchunks - 1), gnext, mnext);
+            __builtin_amdgcn_sched_barrier(0);     // the requests go out BEFORE the chunk's MFMAs
+            bf16x8 af[2][3], df[2][3];
+#pragma unroll
+            for (int x = 0; x < 2; x++)
+#pragma unroll
+                for (int p = 0; p < 3; p++) {
+                    af[x][p] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(a_rd + buf * (6 * WS_PLANE) + p * WS_PLANE + x * 512));
+                    df[x][p] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(d_rd + buf * (6 * WS_PLANE) + p * WS_PLANE + x * 512));
+                }
+#define WS_TERM(PA, PD)                                                                                                           \
+    _Pragma("unroll") for (int x = 0; x < 2; x++) _Pragma("unroll") for (int z = 0; z < 2; z++)                                    \
+        acc[x][z] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[x][PA], df[z][PD], acc[x][z], 0, 0, 0)
+            WS_TERM(2, 0); WS_TERM(1, 1); WS_TERM(0, 2);          // smallest terms first
+            WS_TERM(1, 0); WS_TERM(0, 1); WS_TERM(0, 0);
+#undef WS_TERM
+            __builtin_amdgcn_sched_barrier(0);
+            store_chunk(c1n, buf ^ 1, mcur);      // (the last iteration re-stages the last chunk into the idle buffer: no branch around the loads' consumer)
+            __syncthreads();
+        }
+    }
+    float* P = W.part + (long)blockIdx.x * T.N * W.K;
+    const int kbase = kt0 + wk * 64, nbase = nt0 + wn * 64;
+    if (kbase + 64 <= W.K && nbase + 64 <= T.N) {        // block inside dW: unguarded stores (see train_wgrad_kernel)
+#pragma unroll
+        for (int x = 0; x < 2; x++)
+#pragma unroll
+            for (int z = 0; z < 2; z++) {
+                float* q = P + (long)(nbase + 2 * j + z) * W.K + kbase + 8 * h + x;
+#pragma unroll
+                for (int e = 0; e < 16; e++) q[((e & 3) + 8 * (e >> 2)) * 2] = acc[x][z][e];
+            }
+        return;
+    }
+#pragma unroll
+    for (int x = 0; x < 2; x++)
+#pragma unroll
+        for (int z = 0; z < 2; z++) {
+            const int no = nbase + 2 * j + z;
+            if (no >= T.N) continue;
+#pragma unroll
+            for (int e = 0; e < 16; e++) {
+                const int i = (e & 3) + 8 * (e >> 2) + 4 * h;
+                const int ko = kbase + 2 * i + x;
+                if (ko < W.K) P[(long)no * W.K + ko] = acc[x][z][e];
+            }
+        }
+}
+
+template <int POOL, bool MULT>
+static void launch_wgrad_s(const TrainWgrad& Wg, dim3 grid, hipStream_t s) {
+    if (Wg.pro_scale) hipLaunchKernelGGL((train_wgrad_s_kernel<POOL, MULT, true>), grid, dim3(256), 0, s, Wg);
+    else hipLaunchKernelGGL((train_wgrad_s_kernel<POOL, MULT, false>), grid, dim3(256), 0, s, Wg);
+}
+
 // out[n, (k + k_unrot) % K] = sum over the partials, in a fixed order (deterministic).  Block = 16 elements x 16 lanes over the partial
 // index, eight loads in flight per lane (round 5: narrow layers have up to 4096 partials -- 1024 row ranges x 4 row groups -- and the
 // round-3 form walked them 4 lanes x 4 loads at a time: 256 dependent L2 round trips, 24 us per call, 0.8 ms per training step);
@@ -1676,10 +1869,11 @@ static void launch_wgrad(const TrainWgrad& W, const WgradPlan& p, hipStream_t s)
 }
 
 // wsplit_t: NULL (prcnn_train_stack_bwd) or nl pointers to split images of W^T (prcnn_train_stack_bwd_split); a layer whose dgrad is
-// eligible and whose entry is non-NULL runs train_dgrad_s_kernel
+// eligible and whose entry is non-NULL runs train_dgrad_s_kernel.  wgrad_split (prcnn_train_stack_bwd_wsplit): every layer that
+// reaches train_wgrad_lds_kernel runs train_wgrad_s_kernel in its place
 static int train_stack_bwd_run(const prcnn_train_src_t* src, const prcnn_train_layer_t* L, int nl, int pool_ns, const float* a_dump,
                                int ld_dump, const float* gout, int ld_gout, const uint8_t* arg, float* gin, int ld_gin, void* const* wsplit_t,
-                               void* work, size_t work_bytes, prcnn_stream_t stream) {
+                               bool wgrad_split, void* work, size_t work_bytes, prcnn_stream_t stream) {
     PRCNN_REQUIRE(src && gout, "prcnn_train_stack_bwd: null pointer");
     int rc = train_check_layers(L, nl);
     if (rc) return rc;
@@ -1736,7 +1930,11 @@ static int train_stack_bwd_run(const prcnn_train_src_t* src, const prcnn_train_l
         else if (p.WN == 1) launch_wgrad<2, 2, 2, 1>(Wg, p, s);
         else if (Wg.lda % 4 == 0 && aligned16(Wg.a) && !sw_present(SW_WGRAD_DIRECT)) {
             const dim3 wg(p.splits, p.tiles_k, p.tiles_n);
-            if (Wg.B.pool_ns == 0) { if (Wg.B.mult) launch_wgrad_lds<0, true>(Wg, wg, s); else launch_wgrad_lds<0, false>(Wg, wg, s); }
+            if (wgrad_split) {
+                if (Wg.B.pool_ns == 0) { if (Wg.B.mult) launch_wgrad_s<0, true>(Wg, wg, s); else launch_wgrad_s<0, false>(Wg, wg, s); }
+                else if (Wg.B.pool_ns > 0) launch_wgrad_s<1, false>(Wg, wg, s);
+                else launch_wgrad_s<2, true>(Wg, wg, s);
+            } else if (Wg.B.pool_ns == 0) { if (Wg.B.mult) launch_wgrad_lds<0, true>(Wg, wg, s); else launch_wgrad_lds<0, false>(Wg, wg, s); }
             else if (Wg.B.pool_ns > 0) launch_wgrad_lds<1, false>(Wg, wg, s);
             else launch_wgrad_lds<2, true>(Wg, wg, s);
         } else launch_wgrad<2, 2, 2, 2>(Wg, p, s);
@@ -1787,13 +1985,19 @@ static int train_stack_bwd_run(const prcnn_train_src_t* src, const prcnn_train_l
 PRCNN_API int prcnn_train_stack_bwd(const prcnn_train_src_t* src, const prcnn_train_layer_t* L, int nl, int pool_ns, const float* a_dump,
                                     int ld_dump, const float* gout, int ld_gout, const uint8_t* arg, float* gin, int ld_gin, void* work,
                                     size_t work_bytes, prcnn_stream_t stream) {
-    return train_stack_bwd_run(src, L, nl, pool_ns, a_dump, ld_dump, gout, ld_gout, arg, gin, ld_gin, nullptr, work, work_bytes, stream);
+    return train_stack_bwd_run(src, L, nl, pool_ns, a_dump, ld_dump, gout, ld_gout, arg, gin, ld_gin, nullptr, false, work, work_bytes, stream);
 }
 PRCNN_API int prcnn_train_stack_bwd_split(const prcnn_train_src_t* src, const prcnn_train_layer_t* L, int nl, int pool_ns, const float* a_dump,
                                           int ld_dump, const float* gout, int ld_gout, const uint8_t* arg, float* gin, int ld_gin,
                                           void* const* wsplit_t, void* work, size_t work_bytes, prcnn_stream_t stream) {
     PRCNN_REQUIRE(wsplit_t, "prcnn_train_stack_bwd_split: null split-image table");
-    return train_stack_bwd_run(src, L, nl, pool_ns, a_dump, ld_dump, gout, ld_gout, arg, gin, ld_gin, wsplit_t, work, work_bytes, stream);
+    return train_stack_bwd_run(src, L, nl, pool_ns, a_dump, ld_dump, gout, ld_gout, arg, gin, ld_gin, wsplit_t, false, work, work_bytes, stream);
+}
+PRCNN_API int prcnn_train_stack_bwd_wsplit(const prcnn_train_src_t* src, const prcnn_train_layer_t* L, int nl, int pool_ns, const float* a_dump,
+                                           int ld_dump, const float* gout, int ld_gout, const uint8_t* arg, float* gin, int ld_gin,
+                                           void* const* wsplit_t, void* work, size_t work_bytes, prcnn_stream_t stream) {
+    PRCNN_REQUIRE(wsplit_t, "prcnn_train_stack_bwd_wsplit: null split-image table");
+    return train_stack_bwd_run(src, L, nl, pool_ns, a_dump, ld_dump, gout, ld_gout, arg, gin, ld_gin, wsplit_t, true, work, work_bytes, stream);
 }
 
 PRCNN_API int prcnn_group_rows_grad(const float* G, int ldG, const int32_t* idx, int B, int M, int ns, int C, int N, float* dfeat,

@@ -196,9 +196,10 @@ def rpn_loss_rows(dev, B=16, N=16384, rounds=5):
 def train_split_rows(dev, B=16, rounds=5):
     """`train stack fwd+bwd`: one SharedMLPTrain forward + backward at two RPN training shapes -- an SA2-like padding-free stack
     (4096 -> 1024 centres, radius 2.5, nsample 32, [96 + 3, 64, 96, 128]) and an FP-like plain stack (B x 16 384 rows, [256, 128, 128]) -- with
-    train_mlp.TRAIN_SPLIT 0 (fp32 MFMA throughout) against 6 (split-bf16 forward / dgrad on the eligible layers), alternated in one
-    process; per setting the median, minimum and maximum over `rounds` windows of 20 calls.  `split_launches`: the per-call weight
-    split launches the setting adds."""
+    train_mlp.TRAIN_SPLIT 0 (fp32 MFMA throughout) against 6 (split-bf16 forward / dgrad on the eligible layers) against 6 with
+    train_mlp.TRAIN_SPLIT_WGRAD 6 as well (the wide layers' wgrad on train_wgrad_s_kernel), alternated in one process; per setting
+    the median, minimum and maximum over `rounds` windows of 20 calls.  `split_launches`: the per-call weight split launches the
+    setting adds; `split_wgrads`: the layers whose wgrad runs the split kernel."""
     from . import train_mlp
     g = torch.Generator().manual_seed(5)
     xyz = rpn.synthetic_clouds(B, 16384, device=dev)
@@ -220,24 +221,74 @@ def train_split_rows(dev, B=16, rounds=5):
         def step():
             x0.grad = None
             train_mlp.SharedMLPTrain.apply(src, bns, ns, x0, None, *params).backward(gout)
-        times = {0: [], 6: []}
-        keep = train_mlp.TRAIN_SPLIT
+        settings = ((0, 0, "fp32 MFMA"), (6, 0, "split-bf16 x 6"), (6, 6, "split-bf16 x 6 + split wgrad"))
+        times = {st[:2]: [] for st in settings}
+        keep = train_mlp.TRAIN_SPLIT, train_mlp.TRAIN_SPLIT_WGRAD
         try:
             for _ in range(rounds):
-                for terms in (0, 6):
-                    train_mlp.TRAIN_SPLIT = terms
-                    times[terms].append(timeit(step))
+                for terms, wterms, _ in settings:
+                    train_mlp.TRAIN_SPLIT, train_mlp.TRAIN_SPLIT_WGRAD = terms, wterms
+                    times[(terms, wterms)].append(timeit(step))
         finally:
-            train_mlp.TRAIN_SPLIT = keep
+            train_mlp.TRAIN_SPLIT, train_mlp.TRAIN_SPLIT_WGRAD = keep
         rows = int(gr.rows_dev.item()) if ns else groups
         fwd_split = sum(1 for l, k in enumerate(chans[:-1]) if k % 32 == 0 and (l > 0 or src.mode == "plain"))
         bwd_split = sum(1 for n in chans[1:] if n % 32 == 0)
-        for terms in (0, 6):
-            t = sorted(times[terms])
-            print(json.dumps({"op": "train stack fwd+bwd (%s)" % ("split-bf16 x 6" if terms else "fp32 MFMA"),
+        wide = sum(1 for k, n in zip(chans[:-1], chans[1:]) if k > 64 and n > 64)
+        for terms, wterms, label in settings:
+            t = sorted(times[(terms, wterms)])
+            print(json.dumps({"op": "train stack fwd+bwd (%s)" % label,
                               "shape": "%s: B%d, %d rows, %s" % (name, B, rows, chans), "median_us": round(t[len(t) // 2] * 1e6, 1),
                               "min_us": round(t[0] * 1e6, 1), "max_us": round(t[-1] * 1e6, 1),
-                              "split_launches": (fwd_split + bwd_split) if terms else 0}), flush=True)
+                              "split_launches": (fwd_split + bwd_split) if terms else 0, "split_wgrads": wide if wterms else 0}), flush=True)
+
+
+def train_wgrad_rows(dev, rounds=5):
+    """`train stack bwd`: the BACKWARD library call alone of stacks whose GEMM work is wide weight gradients, with the wgrad on
+    train_wgrad_lds_kernel (prcnn_train_stack_bwd) against train_wgrad_s_kernel (prcnn_train_stack_bwd_wsplit, every dgrad on fp32),
+    alternated in one process; per setting the median, minimum and maximum over `rounds` windows of 20 calls.  The first layer
+    takes no input gradient, so besides the wgrads a call holds the BatchNorm backward reductions, the partial-tile reductions and
+    the dgrads between the layers -- the same launches under both settings.  Shapes: 262 144 plain rows [128, 128, 128] (two
+    262 144 x 128 x 128 wgrads, the second with the prologue), the 515 -> 256 padding-free first layer, a 128 -> 196 layer."""
+    import ctypes
+    from . import _cabi, train_mlp
+    from .ops import _p, _stream
+    g = torch.Generator().manual_seed(9)
+    B = 16
+    xyz = rpn.synthetic_clouds(B, 16384, device=dev)
+    xyz1 = ops.gather_rows(xyz, ops.furthest_point_sample(xyz, 1024))
+    nx2 = ops.gather_rows(xyz1, ops.furthest_point_sample(xyz1, 256))
+    gr = train_mlp.GroupRows(ops.ball_query(4.0, 32, xyz1, nx2), nx2, 1024)
+    stacks = (("plain", train_mlp.Source("plain"), 0, torch.randn(262144, 128, generator=g).to(dev), [128, 128, 128], 262144),
+              ("padding-free first layer", train_mlp.Source("group", xyz=xyz1.reshape(1, -1, 3), rows=gr), 32,
+               torch.randn(B, 1024, 512, generator=g).to(dev), [515, 256], B * 256),
+              ("plain", train_mlp.Source("plain"), 0, torch.randn(262144, 128, generator=g).to(dev), [128, 196], 262144))
+    L = _cabi.lib()
+    for name, src, ns, x0, chans, groups in stacks:
+        bns = [torch.nn.BatchNorm1d(n).to(dev).train() for n in chans[1:]]
+        params = []
+        for k, n, bn in zip(chans[:-1], chans[1:], bns):
+            params += [(torch.randn(n, k, generator=g) / k ** 0.5).to(dev).requires_grad_(True), bn.weight, bn.bias]
+        gout = torch.randn(groups, chans[-1], generator=g).to(dev)
+        ctx = train_mlp.SharedMLPTrain.apply(src, bns, ns, x0, None, *params).grad_fn      # (x0 takes no gradient: no dgrad for layer 0)
+        st = ctx.st
+        work, nbytes = st.work(ctx.K0, True, dev)
+        nulls = (ctypes.c_void_p * st.nl)()
+        head = (ctypes.byref(ctx.S), st.layers, st.nl, ctx.ns, _p(ctx.a_dump), ctx.ld_dump, _p(gout), gout.stride(0), _p(ctx.arg), None, 0)
+        tail = (train_mlp._aligned_ptr(work), nbytes, _stream())
+        calls = {0: lambda: _cabi.check(L.prcnn_train_stack_bwd(*head, *tail), "prcnn_train_stack_bwd"),
+                 6: lambda: _cabi.check(L.prcnn_train_stack_bwd_wsplit(*head, nulls, *tail), "prcnn_train_stack_bwd_wsplit")}
+        times = {0: [], 6: []}
+        for _ in range(rounds):
+            for terms in (0, 6):
+                times[terms].append(timeit(calls[terms]))
+        rows = int(gr.rows_dev.item()) if ns else groups
+        flops = sum(2.0 * rows * k * n for k, n in zip(chans[:-1], chans[1:]) if k > 64 and n > 64)
+        for terms in (0, 6):
+            t = sorted(times[terms])
+            print(json.dumps({"op": "train stack bwd (%s)" % ("wgrad split-bf16 x 6" if terms else "wgrad fp32 LDS kernel"),
+                              "shape": "%s: %d rows, %s" % (name, rows, chans), "median_us": round(t[len(t) // 2] * 1e6, 1),
+                              "min_us": round(t[0] * 1e6, 1), "max_us": round(t[-1] * 1e6, 1), "wide_wgrad_GFLOP": round(flops / 1e9, 2)}), flush=True)
 
 
 def optimizer_rows(dev, rounds=5):
@@ -571,7 +622,7 @@ def eval_loop_rows(dev, B=16, nbatches=3, rounds=5):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
-    ap.add_argument("--only", default=None, help="run one row family only: eval_stats | optimizer | train_split | result_writer | eval_loop")
+    ap.add_argument("--only", default=None, help="run one row family only: eval_stats | optimizer | train_split | train_wgrad | result_writer | eval_loop")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     if args.only == "result_writer":
@@ -589,6 +640,9 @@ def main():
         return
     if args.only == "train_split":
         train_split_rows(dev)
+        return
+    if args.only == "train_wgrad":
+        train_wgrad_rows(dev)
         return
     B = 8 if args.quick else 32
     N = 16384
@@ -716,6 +770,7 @@ def main():
     rcnn_loss_rows(dev)
     # ---- a training stack forward + backward: fp32 MFMA against the opt-in split-bf16 forward / dgrad (csrc/mlp_train.h)
     train_split_rows(dev, B=4 if args.quick else 16)
+    train_wgrad_rows(dev)
     # ---- the adam_onecycle parameter update: composed torch against the two launches of csrc/optim.hip
     optimizer_rows(dev)
     # ---- TRAIN.OPTIMIZER adam and sgd: clip_grad_norm_ + torch's foreach step against the same two launches

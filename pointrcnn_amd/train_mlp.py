@@ -33,6 +33,13 @@ _TRAIN_SPLIT_ENV = os.environ.get("PRCNN_TRAIN_SPLIT", "")
 if _TRAIN_SPLIT_ENV not in ("", "0", "1", "6"):
     raise RuntimeError("PRCNN_TRAIN_SPLIT=%r: 1 or 6 = six split-bf16 terms, 0 / unset = fp32 MFMA" % _TRAIN_SPLIT_ENV)
 TRAIN_SPLIT = 6 if _TRAIN_SPLIT_ENV in ("1", "6") else 0
+# Arithmetic of the wide layers' wgrad (independent of TRAIN_SPLIT, read once like it): 0 (default) = fp32 MFMA; 6
+# (PRCNN_TRAIN_SPLIT_WGRAD=1 or 6) = every layer that gets the 128 x 128 LDS-staged wgrad kernel runs its split-bf16 x 6 twin
+# (csrc/mlp_train.h: train_wgrad_s_kernel, through prcnn_train_stack_bwd_wsplit); the narrow layers' wgrad stays on fp32 MFMA
+_TRAIN_SPLIT_WGRAD_ENV = os.environ.get("PRCNN_TRAIN_SPLIT_WGRAD", "")
+if _TRAIN_SPLIT_WGRAD_ENV not in ("", "0", "1", "6"):
+    raise RuntimeError("PRCNN_TRAIN_SPLIT_WGRAD=%r: 1 or 6 = six split-bf16 terms, 0 / unset = fp32 MFMA" % _TRAIN_SPLIT_WGRAD_ENV)
+TRAIN_SPLIT_WGRAD = 6 if _TRAIN_SPLIT_WGRAD_ENV in ("1", "6") else 0
 # bench.py's accounting: when a list, every stack forward appends (rows (int) or live-row counter (device tensor), [(K, N) per layer],
 # first layer takes an input gradient) -- nothing is read back here
 FLOP_LOG = None
@@ -311,7 +318,13 @@ class SharedMLPTrain(torch.autograd.Function):
             ld_gin = _up(ctx.kin0, 4)
             gin = torch.empty((rows, ld_gin), dtype=_F32, device=dev)
         work, nbytes = st.work(ctx.K0, True, dev)
-        if st.wsplit_t is not None:
+        if TRAIN_SPLIT_WGRAD:
+            # (a table of NULLs: every dgrad on the fp32 pipe)
+            table = st.wsplit_t if st.wsplit_t is not None else (ctypes.c_void_p * st.nl)()
+            _cabi.check(L.prcnn_train_stack_bwd_wsplit(ctypes.byref(ctx.S), st.layers, st.nl, ctx.ns, _p(ctx.a_dump), ctx.ld_dump, _p(G),
+                                                       G.stride(0), _p(ctx.arg), _p(gin), ld_gin, table, _aligned_ptr(work), nbytes,
+                                                       _stream()), "prcnn_train_stack_bwd_wsplit")
+        elif st.wsplit_t is not None:
             _cabi.check(L.prcnn_train_stack_bwd_split(ctypes.byref(ctx.S), st.layers, st.nl, ctx.ns, _p(ctx.a_dump), ctx.ld_dump, _p(G),
                                                       G.stride(0), _p(ctx.arg), _p(gin), ld_gin, st.wsplit_t, _aligned_ptr(work), nbytes,
                                                       _stream()), "prcnn_train_stack_bwd_split")
