@@ -73,6 +73,8 @@ int prcnn_abi_version(void);   /* 12: + prcnn_switches_reload, prcnn_switch_get 
                                  * prcnn_gt_database_fill (the GT-augmentation database built on the device);
                                  * still 12 (additive): + prcnn_rpn_loss_workspace_bytes, prcnn_rpn_loss_counts, prcnn_rpn_loss_forward,
                                  * prcnn_rpn_loss_backward (the RPN training loss and its gradient in device passes);
+                                 * still 12 (additive): + prcnn_rpn_loss_cls_sums, prcnn_rpn_loss_forward_kind, prcnn_rpn_loss_backward_kind
+                                 * (the same for RPN.LOSS_CLS = DiceLoss and BinaryCrossEntropy);
                                  * still 12 (additive): + prcnn_rcnn_loss_workspace_bytes, prcnn_rcnn_loss_forward, prcnn_rcnn_loss_finalize,
                                  * prcnn_rcnn_loss_backward (the RCNN training loss and its gradient in device passes);
                                  * 11: + prcnn_train_scene_workspace_bytes, prcnn_train_scene_prepare (the RPN training batch on the device);
@@ -933,7 +935,7 @@ typedef struct prcnn_rpn_loss_cfg {
     double gamma, alpha;            /* focal loss; has_alpha 0: alpha is None */
     double loss_weight[2];          /* RPN.LOSS_WEIGHT */
     int num_head_bin, xz_fine, y_by_bin, ry_fine;
-    int loss_cls;                   /* 0 SigmoidFocalLoss; the others have no kernel */
+    int loss_cls;                   /* 0 SigmoidFocalLoss, 1 DiceLoss, 2 BinaryCrossEntropy (1 and 2: the *_kind exports only) */
     int has_alpha;
 } prcnn_rpn_loss_cfg_t;
 size_t prcnn_rpn_loss_workspace_bytes(int64_t npts);
@@ -946,6 +948,28 @@ int prcnn_rpn_loss_backward(const float* rpn_cls, int64_t ld_cls, const float* r
                             int label_is_i64, const float* reg_label, int64_t npts, int C, const prcnn_rpn_loss_cfg_t* cfg,
                             const int32_t* counts, const float* norm, const float* grad_out, float* dcls, float* dreg,
                             prcnn_stream_t stream);
+/* All three RPN.LOSS_CLS kinds (cfg->loss_cls 0 SigmoidFocalLoss, 1 DiceLoss, 2 BinaryCrossEntropy); the three exports above keep
+ * answering PRCNN_EUNSUPPORTED for 1 and 2.  Arguments as above, and:
+ *   cls_sums  DiceLoss: the two doubles {A = sum min(p, t), B = sum max(p, t)} over the valid rows that prcnn_rpn_loss_cls_sums writes
+ *             (work as above; per-workgroup partials in double, added in a fixed order).  The loss is 1 - A / max(B, 1).  A
+ *             data-parallel caller all-reduces the two doubles in place between that call and the next two and passes
+ *             norm[0] = world: the value is the global loss, the gradient this rank's share x world.  NULL for the other kinds.
+ *   fg_weight BinaryCrossEntropy: RPN.FG_WEIGHT, the weight of a foreground row (rounded to float32 once); ignored otherwise.
+ *             norm[0] scales the sum of the valid rows' terms: 1 / max(valid, 1), data-parallel world / max(valid_global, 1).
+ *   norm      may be NULL for DiceLoss and BinaryCrossEntropy: the single-process normalisers {1 | 1 / max(counts[1], 1), 1},
+ *             read from counts on the device.  (prcnn_rpn_loss_counts writes SigmoidFocalLoss's.)
+ * terms[6] and terms[7] (cls_pos, cls_neg) are 0 for DiceLoss and BinaryCrossEntropy.  For loss_cls 0 these are the launches of
+ * prcnn_rpn_loss_forward / _backward. */
+int prcnn_rpn_loss_cls_sums(const float* rpn_cls, int64_t ld_cls, const void* cls_label, int label_is_i64, int64_t npts, double* cls_sums,
+                            void* work, size_t work_bytes, prcnn_stream_t stream);
+int prcnn_rpn_loss_forward_kind(const float* rpn_cls, int64_t ld_cls, const float* rpn_reg, int64_t ld_reg, const void* cls_label,
+                                int label_is_i64, const float* reg_label, int64_t npts, int C, const prcnn_rpn_loss_cfg_t* cfg,
+                                const int32_t* counts, const float* norm, float* terms, void* work, size_t work_bytes,
+                                const double* cls_sums, double fg_weight, prcnn_stream_t stream);
+int prcnn_rpn_loss_backward_kind(const float* rpn_cls, int64_t ld_cls, const float* rpn_reg, int64_t ld_reg, const void* cls_label,
+                                 int label_is_i64, const float* reg_label, int64_t npts, int C, const prcnn_rpn_loss_cfg_t* cfg,
+                                 const int32_t* counts, const float* norm, const float* grad_out, float* dcls, float* dreg,
+                                 const double* cls_sums, double fg_weight, prcnn_stream_t stream);
 
 /* ======================================================================================================
  * RCNN training loss and its gradient in device passes (csrc/rcnn_loss.hip, arithmetic: csrc/rcnn_loss_math.h) --

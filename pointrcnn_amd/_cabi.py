@@ -163,6 +163,9 @@ SIGNATURES = {
     "prcnn_rpn_loss_counts": (_I, [_P, _I, _L, _P, _P, _P, _Z, _P]),
     "prcnn_rpn_loss_forward": (_I, [_P, _L, _P, _L, _P, _I, _P, _L, _I, ctypes.POINTER(RpnLossCfg), _P, _P, _P, _P, _Z, _P]),
     "prcnn_rpn_loss_backward": (_I, [_P, _L, _P, _L, _P, _I, _P, _L, _I, ctypes.POINTER(RpnLossCfg), _P, _P, _P, _P, _P, _P]),
+    "prcnn_rpn_loss_cls_sums": (_I, [_P, _L, _P, _I, _L, _P, _P, _Z, _P]),
+    "prcnn_rpn_loss_forward_kind": (_I, [_P, _L, _P, _L, _P, _I, _P, _L, _I, ctypes.POINTER(RpnLossCfg), _P, _P, _P, _P, _Z, _P, _D, _P]),
+    "prcnn_rpn_loss_backward_kind": (_I, [_P, _L, _P, _L, _P, _I, _P, _L, _I, ctypes.POINTER(RpnLossCfg), _P, _P, _P, _P, _P, _P, _D, _P]),
     "prcnn_rcnn_loss_workspace_bytes": (_Z, [_L]),
     "prcnn_rcnn_loss_forward": (_I, [_P, _L, _P, _L, _P, _I, _P, _I, _P, _P, _L, _I, ctypes.POINTER(RcnnLossCfg), _I, _P, _P, _P, _Z, _P]),
     "prcnn_rcnn_loss_finalize": (_I, [_L, _I, ctypes.POINTER(RcnnLossCfg), _P, _P, _P, _P, _Z, _P]),

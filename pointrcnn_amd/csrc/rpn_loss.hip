@@ -1,5 +1,5 @@
-// rpn_loss.hip -- the RPN training loss (train_functions.get_rpn_loss, default configuration family) and its gradient on the
-// device: SigmoidFocalLoss classification + bin-based box regression over the foreground rows (arithmetic: rpn_loss_math.h).
+// rpn_loss.hip -- the RPN training loss (train_functions.get_rpn_loss) and its gradient on the device: SigmoidFocalLoss, DiceLoss
+// or BinaryCrossEntropy classification + bin-based box regression over the foreground rows (arithmetic: rpn_loss_math.h).
 //
 //   prcnn_rpn_loss_counts    pos = #(label > 0), valid = #(label >= 0), fg = pos as integers: per-workgroup partial counts, summed by one
 //                            workgroup in a fixed order.  It also writes the single-process normalisers {1 / max(pos, 1), 1}; a
@@ -11,6 +11,14 @@
 //                            empty selection gives 0), 3 x size, the data-parallel scale and LOSS_WEIGHT and writes 9 floats.
 //   prcnn_rpn_loss_backward  the same launch geometry with grad_output read from the device: d loss / d rpn_cls and d loss / d rpn_reg,
 //                            every entry written exactly once (no memset, no atomics).
+// The three exports above are SigmoidFocalLoss only.  All three RPN.LOSS_CLS kinds go through
+//   prcnn_rpn_loss_cls_sums       DiceLoss only: A = sum min(p, t), B = sum max(p, t) over the valid rows, per-workgroup partials in
+//                                 double, summed by one workgroup in a fixed order into two doubles on the device (a data-parallel
+//                                 caller all-reduces them in place before the next two calls)
+//   prcnn_rpn_loss_forward_kind   the forward launches with the kind's classification term: focal as above; BCE row terms summed into
+//                                 the same slot and scaled by norm[0] at the end; Dice formed as 1 - A / max(B, 1) from the two doubles
+//   prcnn_rpn_loss_backward_kind  the backward launch; Dice reads A and B from the device
+// with norm NULL (Dice, BCE) standing for the single-process normalisers {Dice 1 | BCE 1 / max(valid, 1), 1}.
 // The regression row of a row that is not foreground is never read: only foreground rows are staged (16-byte units, coalesced) into
 // LDS, where the row's lane works on them in place; the gradient tile leaves LDS in 16-byte units again, zeros for the other rows.
 // The grid is a function of the row count alone, and no result depends on anything but the rows in their flat order.
@@ -95,6 +103,61 @@ __global__ __launch_bounds__(RL_CNT_THREADS) void rpn_loss_count_sum_kernel(cons
     }
 }
 
+// ------------------------------------------------------------------------------------------------ Dice sums
+// A = sum min(p, t), B = sum max(p, t) over the valid rows: the geometry of the counts, float32 addends summed in double
+__global__ __launch_bounds__(RL_CNT_THREADS) void rpn_loss_dice_kernel(const float* __restrict__ cls, int64_t ld_cls,
+                                                                       const void* __restrict__ label, int is_i64, int64_t npts,
+                                                                       double* __restrict__ part) {
+    __shared__ double s_a[RL_CNT_THREADS], s_b[RL_CNT_THREADS];
+    double a = 0.0, b = 0.0;
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < npts; r += (int64_t)gridDim.x * blockDim.x) {
+        const int l = rl_label(label, is_i64, r);
+        if (l < 0) continue;
+        float lo, hi, dlo, dhi;
+        rl_dice(cls[r * ld_cls], (float)l, &lo, &hi, &dlo, &dhi);
+        a += (double)lo;
+        b += (double)hi;
+    }
+    s_a[threadIdx.x] = a;
+    s_b[threadIdx.x] = b;
+    __syncthreads();
+    for (int s = RL_CNT_THREADS / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            s_a[threadIdx.x] += s_a[threadIdx.x + s];
+            s_b[threadIdx.x] += s_b[threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        part[2 * blockIdx.x + 0] = s_a[0];
+        part[2 * blockIdx.x + 1] = s_b[0];
+    }
+}
+
+__global__ __launch_bounds__(RL_CNT_THREADS) void rpn_loss_dice_sum_kernel(const double* __restrict__ part, int blocks,
+                                                                           double* __restrict__ sums) {
+    __shared__ double s_a[RL_CNT_THREADS], s_b[RL_CNT_THREADS];
+    double a = 0.0, b = 0.0;
+    for (int i = threadIdx.x; i < blocks; i += RL_CNT_THREADS) {
+        a += part[2 * i + 0];
+        b += part[2 * i + 1];
+    }
+    s_a[threadIdx.x] = a;
+    s_b[threadIdx.x] = b;
+    __syncthreads();
+    for (int s = RL_CNT_THREADS / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            s_a[threadIdx.x] += s_a[threadIdx.x + s];
+            s_b[threadIdx.x] += s_b[threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        sums[0] = s_a[0];
+        sums[1] = s_b[0];
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ main pass
 struct RlParams {
     const float* cls;           // row r's logit at cls[r * ld_cls]
@@ -112,9 +175,20 @@ struct RlParams {
     float* dreg;                // backward: (npts, C) contiguous
     double* partial;            // forward: (blocks, RL_TERMS)
     RlConfig cfg;
+    const double* cls_sums;     // Dice: {A, B}
+    float fg_weight;            // BCE: the weight of a foreground row
 };
 
-template <bool BWD>
+// the classification (k = 0) or regression (k = 1) normaliser; Dice and BCE accept norm == NULL: the single-process values
+template <int KIND>
+__device__ __forceinline__ float rl_norm(const float* norm, const int32_t* counts, int k) {
+    if (KIND == RL_KIND_FOCAL || norm) return norm[k];
+    if (k == 1 || KIND == RL_KIND_DICE) return 1.0f;
+    const int valid = counts[1];
+    return 1.0f / (float)(valid > 1 ? valid : 1);
+}
+
+template <bool BWD, int KIND>
 __global__ __launch_bounds__(RL_THREADS) void rpn_loss_main_kernel(const RlParams P) {
     __shared__ __attribute__((aligned(16))) float s_row[RL_ROWS * RL_MAX_C];
     __shared__ float s_lab[RL_ROWS * 7];
@@ -153,26 +227,39 @@ __global__ __launch_bounds__(RL_THREADS) void rpn_loss_main_kernel(const RlParam
     for (int k = 0; k < RL_TERMS; ++k) acc[k] = 0.0;
     if (tid < rows) {
         const int l = s_cls[tid];
-        const float w = P.norm[0];
+        const float w = rl_norm<KIND>(P.norm, P.counts, 0);
         float g_cls = 0.0f, g_reg = 0.0f;
         if (BWD) {
             const double go = (double)P.grad_out[0];
             const int fg = P.counts[2];
             g_cls = (float)(go * P.cfg.w_cls);
-            g_reg = (float)(go * P.cfg.w_reg * (double)P.norm[1] / (double)(fg > 1 ? fg : 1));
+            g_reg = (float)(go * P.cfg.w_reg * (double)rl_norm<KIND>(P.norm, P.counts, 1) / (double)(fg > 1 ? fg : 1));
         }
-        if (l >= 0) {
-            float v, dx;
-            rl_focal(P.cls[(row0 + tid) * P.ld_cls], (float)l, w, P.cfg, &v, &dx);
-            if (BWD) {
-                P.dcls[row0 + tid] = g_cls * dx;
-            } else {
-                acc[RL_CLS] = (double)v;
-                if (l > 0) acc[RL_CLS_POS] = (double)v;
-                else acc[RL_CLS_NEG] = (double)v;
+        if (KIND == RL_KIND_FOCAL) {
+            if (l >= 0) {
+                float v, dx;
+                rl_focal(P.cls[(row0 + tid) * P.ld_cls], (float)l, w, P.cfg, &v, &dx);
+                if (BWD) {
+                    P.dcls[row0 + tid] = g_cls * dx;
+                } else {
+                    acc[RL_CLS] = (double)v;
+                    if (l > 0) acc[RL_CLS_POS] = (double)v;
+                    else acc[RL_CLS_NEG] = (double)v;
+                }
+            } else if (BWD) {
+                P.dcls[row0 + tid] = 0.0f;
             }
+        } else if (KIND == RL_KIND_BCE) {
+            // the row terms are summed unscaled; norm[0] multiplies the sum (finalize) and the upstream gradient
+            float v, dx;
+            rl_bce_row(P.cls[(row0 + tid) * P.ld_cls], l, P.fg_weight, &v, &dx);
+            if (BWD) P.dcls[row0 + tid] = l >= 0 ? (float)((double)g_cls * (double)w) * dx : 0.0f;
+            else acc[RL_CLS] = (double)v;
         } else if (BWD) {
-            P.dcls[row0 + tid] = 0.0f;
+            // Dice: the (global) sums of the sums pass give every row's derivative; the forward pass has no row term
+            float lo, hi, dlo, dhi;
+            rl_dice_row(P.cls[(row0 + tid) * P.ld_cls], l, &lo, &hi, &dlo, &dhi);
+            P.dcls[row0 + tid] = l >= 0 ? rl_dice_grad(dlo, dhi, P.cls_sums[0], P.cls_sums[1], (double)g_cls * (double)w) : 0.0f;
         }
         if (l > 0) rl_reg_row<BWD, double>(&s_row[tid * C], &s_lab[tid * 7], P.cfg, g_reg, acc);
     }
@@ -202,9 +289,11 @@ __global__ __launch_bounds__(RL_THREADS) void rpn_loss_main_kernel(const RlParam
 }
 
 // sums the per-workgroup partials in a fixed order and forms the named terms (doubles, rounded to float once at the end)
+template <int KIND>
 __global__ __launch_bounds__(RL_THREADS) void rpn_loss_finalize_kernel(const double* __restrict__ partial, int blocks,
                                                                        const int32_t* __restrict__ counts, const float* __restrict__ norm,
-                                                                       const RlConfig cfg, float* __restrict__ terms) {
+                                                                       const RlConfig cfg, const double* __restrict__ cls_sums,
+                                                                       float* __restrict__ terms) {
     __shared__ double s_sum[RL_THREADS][RL_TERMS];
     const int tid = threadIdx.x;
     double acc[RL_TERMS];
@@ -227,7 +316,7 @@ __global__ __launch_bounds__(RL_THREADS) void rpn_loss_finalize_kernel(const dou
         const double* t = s_sum[0];
         const int fg = counts[2];
         const double cnt = (double)(fg > 1 ? fg : 1);
-        const double scale = (double)norm[1];
+        const double scale = (double)rl_norm<KIND>(norm, counts, 1);
         double loc = t[RL_X_BIN] / cnt + t[RL_Z_BIN] / cnt + t[RL_Y_OFF] / cnt;
         if (cfg.xz_fine) loc += t[RL_X_RES] / cnt + t[RL_Z_RES] / cnt;
         double angle = t[RL_RY_BIN] / cnt + t[RL_RY_RES] / cnt;
@@ -236,7 +325,9 @@ __global__ __launch_bounds__(RL_THREADS) void rpn_loss_finalize_kernel(const dou
         angle *= scale;
         size *= scale;
         const double reg = loc + angle + size;
-        const double cls = t[RL_CLS];
+        double cls = t[RL_CLS];
+        if (KIND == RL_KIND_BCE) cls *= (double)rl_norm<KIND>(norm, counts, 0);
+        if (KIND == RL_KIND_DICE) cls = 1.0 - cls_sums[0] / (cls_sums[1] > 1.0 ? cls_sums[1] : 1.0);
         terms[0] = (float)(cls * cfg.w_cls + reg * cfg.w_reg);
         terms[1] = (float)cls;
         terms[2] = (float)reg;
@@ -250,11 +341,15 @@ __global__ __launch_bounds__(RL_THREADS) void rpn_loss_finalize_kernel(const dou
 }
 
 // ------------------------------------------------------------------------------------------------ exports
-static int rl_config(const char* who, const prcnn_rpn_loss_cfg_t* cfg, int C, RlConfig* out) {
+// all_kinds: the *_kind exports take every RPN.LOSS_CLS; the first three exports are SigmoidFocalLoss only and say so
+static int rl_config(const char* who, const prcnn_rpn_loss_cfg_t* cfg, int C, bool all_kinds, RlConfig* out) {
     if (!cfg) return prcnn_fail(PRCNN_EINVAL, "%s: null configuration", who);
-    if (cfg->loss_cls != 0) return prcnn_fail(PRCNN_EUNSUPPORTED, "%s: only SigmoidFocalLoss (loss_cls 0) has a kernel, got %d", who, cfg->loss_cls);
+    if (!all_kinds && cfg->loss_cls != 0)
+        return prcnn_fail(PRCNN_EUNSUPPORTED, "%s: only SigmoidFocalLoss (loss_cls 0) has a kernel, got %d", who, cfg->loss_cls);
+    if (cfg->loss_cls < RL_KIND_FOCAL || cfg->loss_cls > RL_KIND_BCE)
+        return prcnn_fail(PRCNN_EUNSUPPORTED, "%s: loss_cls %d is none of SigmoidFocalLoss (0), DiceLoss (1), BinaryCrossEntropy (2)", who, cfg->loss_cls);
     if (cfg->y_by_bin || cfg->ry_fine) return prcnn_fail(PRCNN_EUNSUPPORTED, "%s: get_y_by_bin / get_ry_fine have no kernel", who);
-    if (!(cfg->gamma >= 0.0)) return prcnn_fail(PRCNN_EINVAL, "%s: focal gamma must be >= 0, got %g", who, cfg->gamma);
+    if (cfg->loss_cls == RL_KIND_FOCAL && !(cfg->gamma >= 0.0)) return prcnn_fail(PRCNN_EINVAL, "%s: focal gamma must be >= 0, got %g", who, cfg->gamma);
     if (!(cfg->loc_scope > 0.0) || !(cfg->loc_bin_size > 0.0) || cfg->num_head_bin < 1)
         return prcnn_fail(PRCNN_EINVAL, "%s: bad bins: scope %g, bin size %g, head bins %d", who, cfg->loc_scope, cfg->loc_bin_size, cfg->num_head_bin);
     const RlConfig c = rl_make_config(cfg->loc_scope, cfg->loc_bin_size, cfg->num_head_bin, cfg->xz_fine != 0, cfg->mean_size, cfg->gamma,
@@ -270,12 +365,16 @@ static int rl_config(const char* who, const prcnn_rpn_loss_cfg_t* cfg, int C, Rl
 
 static int rl_params(const char* who, const float* rpn_cls, int64_t ld_cls, const float* rpn_reg, int64_t ld_reg, const void* cls_label,
                      int label_is_i64, const float* reg_label, int64_t npts, int C, const prcnn_rpn_loss_cfg_t* cfg, const int32_t* counts,
-                     const float* norm, RlParams* P) {
-    const int rc = rl_config(who, cfg, C, &P->cfg);
+                     const float* norm, bool all_kinds, const double* cls_sums, double fg_weight, RlParams* P) {
+    const int rc = rl_config(who, cfg, C, all_kinds, &P->cfg);
     if (rc != PRCNN_OK) return rc;
+    const int kind = cfg->loss_cls;
     PRCNN_REQUIRE(npts >= 0 && npts < ((int64_t)1 << 31) * RL_ROWS, "%s: bad row count %lld", who, (long long)npts);
     PRCNN_REQUIRE(ld_cls >= 1 && ld_reg >= C, "%s: bad row strides %lld / %lld for %d channels", who, (long long)ld_cls, (long long)ld_reg, C);
-    if (npts > 0) PRCNN_REQUIRE(rpn_cls && rpn_reg && cls_label && reg_label && counts && norm, "%s: null pointer", who);
+    if (npts > 0)
+        PRCNN_REQUIRE(rpn_cls && rpn_reg && cls_label && reg_label && counts && (norm || kind != RL_KIND_FOCAL), "%s: null pointer", who);
+    if (kind == RL_KIND_DICE) PRCNN_REQUIRE(cls_sums && (uintptr_t)cls_sums % 8 == 0, "%s: DiceLoss needs the two sums of prcnn_rpn_loss_cls_sums", who);
+    if (kind == RL_KIND_BCE) PRCNN_REQUIRE(std::isfinite(fg_weight), "%s: FG_WEIGHT must be finite, got %g", who, fg_weight);
     P->cls = rpn_cls;
     P->reg = rpn_reg;
     P->ld_cls = ld_cls;
@@ -291,12 +390,14 @@ static int rl_params(const char* who, const float* rpn_cls, int64_t ld_cls, cons
     P->dcls = nullptr;
     P->dreg = nullptr;
     P->partial = nullptr;
+    P->cls_sums = kind == RL_KIND_DICE ? cls_sums : nullptr;
+    P->fg_weight = (float)fg_weight;
     return PRCNN_OK;
 }
 
 PRCNN_API size_t prcnn_rpn_loss_workspace_bytes(int64_t npts) {
     if (npts < 0) return 0;
-    const size_t cnt = (size_t)rl_count_blocks(npts) * 2 * sizeof(int32_t);
+    const size_t cnt = (size_t)rl_count_blocks(npts) * 2 * sizeof(double);     // the Dice partials; the counts' are half of it
     const size_t sum = rl_partial_bytes(npts);
     return (cnt > sum ? cnt : sum) + 16;
 }
@@ -317,44 +418,106 @@ PRCNN_API int prcnn_rpn_loss_counts(const void* cls_label, int label_is_i64, int
     return PRCNN_OK;
 }
 
+PRCNN_API int prcnn_rpn_loss_cls_sums(const float* rpn_cls, int64_t ld_cls, const void* cls_label, int label_is_i64, int64_t npts,
+                                      double* cls_sums, void* work, size_t work_bytes, prcnn_stream_t stream) {
+    PRCNN_REQUIRE(npts >= 0 && ld_cls >= 1, "prcnn_rpn_loss_cls_sums: bad row count %lld / stride %lld", (long long)npts, (long long)ld_cls);
+    PRCNN_REQUIRE(cls_sums && work && ((rpn_cls && cls_label) || npts == 0), "prcnn_rpn_loss_cls_sums: null pointer");
+    PRCNN_REQUIRE((uintptr_t)cls_sums % 8 == 0, "prcnn_rpn_loss_cls_sums: the two sums must be 8-byte aligned");
+    PRCNN_REQUIRE(work_bytes >= prcnn_rpn_loss_workspace_bytes(npts) && (uintptr_t)work % 8 == 0,
+                  "prcnn_rpn_loss_cls_sums: workspace of %zu bytes, need %zu (8-byte aligned)", work_bytes, prcnn_rpn_loss_workspace_bytes(npts));
+    const int blocks = rl_count_blocks(npts);
+    hipLaunchKernelGGL(rpn_loss_dice_kernel, dim3(blocks), dim3(RL_CNT_THREADS), 0, (hipStream_t)stream, rpn_cls, ld_cls, cls_label,
+                       label_is_i64 != 0, npts, (double*)work);
+    PRCNN_LAUNCH_CHECK("prcnn_rpn_loss_cls_sums");
+    hipLaunchKernelGGL(rpn_loss_dice_sum_kernel, dim3(1), dim3(RL_CNT_THREADS), 0, (hipStream_t)stream, (const double*)work, blocks, cls_sums);
+    PRCNN_LAUNCH_CHECK("prcnn_rpn_loss_cls_sums");
+    return PRCNN_OK;
+}
+
+template <int KIND>
+static int rl_launch_forward(const char* who, const RlParams& P, const double* work, float* terms, hipStream_t stream) {
+    const int blocks = rl_main_blocks(P.npts);
+    if (blocks > 0) {
+        hipLaunchKernelGGL((rpn_loss_main_kernel<false, KIND>), dim3(blocks), dim3(RL_THREADS), 0, stream, P);
+        PRCNN_LAUNCH_CHECK(who);
+    }
+    hipLaunchKernelGGL(rpn_loss_finalize_kernel<KIND>, dim3(1), dim3(RL_THREADS), 0, stream, work, blocks, P.counts, P.norm, P.cfg, P.cls_sums,
+                       terms);
+    PRCNN_LAUNCH_CHECK(who);
+    return PRCNN_OK;
+}
+
+static int rl_forward(const char* who, const float* rpn_cls, int64_t ld_cls, const float* rpn_reg, int64_t ld_reg, const void* cls_label,
+                      int label_is_i64, const float* reg_label, int64_t npts, int C, const prcnn_rpn_loss_cfg_t* cfg, const int32_t* counts,
+                      const float* norm, float* terms, void* work, size_t work_bytes, bool all_kinds, const double* cls_sums, double fg_weight,
+                      prcnn_stream_t stream) {
+    RlParams P;
+    const int rc = rl_params(who, rpn_cls, ld_cls, rpn_reg, ld_reg, cls_label, label_is_i64, reg_label, npts, C, cfg, counts, norm, all_kinds,
+                             cls_sums, fg_weight, &P);
+    if (rc != PRCNN_OK) return rc;
+    PRCNN_REQUIRE(terms && work && counts && (norm || cfg->loss_cls != RL_KIND_FOCAL), "%s: null pointer", who);
+    PRCNN_REQUIRE(work_bytes >= prcnn_rpn_loss_workspace_bytes(npts) && (uintptr_t)work % 8 == 0,
+                  "%s: workspace of %zu bytes, need %zu (8-byte aligned)", who, work_bytes, prcnn_rpn_loss_workspace_bytes(npts));
+    P.partial = (double*)work;
+    if (cfg->loss_cls == RL_KIND_DICE) return rl_launch_forward<RL_KIND_DICE>(who, P, (const double*)work, terms, (hipStream_t)stream);
+    if (cfg->loss_cls == RL_KIND_BCE) return rl_launch_forward<RL_KIND_BCE>(who, P, (const double*)work, terms, (hipStream_t)stream);
+    return rl_launch_forward<RL_KIND_FOCAL>(who, P, (const double*)work, terms, (hipStream_t)stream);
+}
+
+static int rl_backward(const char* who, const float* rpn_cls, int64_t ld_cls, const float* rpn_reg, int64_t ld_reg, const void* cls_label,
+                       int label_is_i64, const float* reg_label, int64_t npts, int C, const prcnn_rpn_loss_cfg_t* cfg, const int32_t* counts,
+                       const float* norm, const float* grad_out, float* dcls, float* dreg, bool all_kinds, const double* cls_sums,
+                       double fg_weight, prcnn_stream_t stream) {
+    RlParams P;
+    const int rc = rl_params(who, rpn_cls, ld_cls, rpn_reg, ld_reg, cls_label, label_is_i64, reg_label, npts, C, cfg, counts, norm, all_kinds,
+                             cls_sums, fg_weight, &P);
+    if (rc != PRCNN_OK) return rc;
+    if (npts == 0) return PRCNN_OK;
+    PRCNN_REQUIRE(grad_out && dcls && dreg, "%s: null pointer", who);
+    PRCNN_REQUIRE((uintptr_t)dreg % 16 == 0, "%s: the rpn_reg gradient must be 16-byte aligned", who);
+    P.grad_out = grad_out;
+    P.dcls = dcls;
+    P.dreg = dreg;
+    const dim3 grid(rl_main_blocks(npts));
+    if (cfg->loss_cls == RL_KIND_DICE)
+        hipLaunchKernelGGL((rpn_loss_main_kernel<true, RL_KIND_DICE>), grid, dim3(RL_THREADS), 0, (hipStream_t)stream, P);
+    else if (cfg->loss_cls == RL_KIND_BCE)
+        hipLaunchKernelGGL((rpn_loss_main_kernel<true, RL_KIND_BCE>), grid, dim3(RL_THREADS), 0, (hipStream_t)stream, P);
+    else
+        hipLaunchKernelGGL((rpn_loss_main_kernel<true, RL_KIND_FOCAL>), grid, dim3(RL_THREADS), 0, (hipStream_t)stream, P);
+    PRCNN_LAUNCH_CHECK(who);
+    return PRCNN_OK;
+}
+
 PRCNN_API int prcnn_rpn_loss_forward(const float* rpn_cls, int64_t ld_cls, const float* rpn_reg, int64_t ld_reg, const void* cls_label,
                                      int label_is_i64, const float* reg_label, int64_t npts, int C, const prcnn_rpn_loss_cfg_t* cfg,
                                      const int32_t* counts, const float* norm, float* terms, void* work, size_t work_bytes,
                                      prcnn_stream_t stream) {
-    RlParams P;
-    const int rc = rl_params("prcnn_rpn_loss_forward", rpn_cls, ld_cls, rpn_reg, ld_reg, cls_label, label_is_i64, reg_label, npts, C, cfg,
-                             counts, norm, &P);
-    if (rc != PRCNN_OK) return rc;
-    PRCNN_REQUIRE(terms && work && counts && norm, "prcnn_rpn_loss_forward: null pointer");
-    PRCNN_REQUIRE(work_bytes >= prcnn_rpn_loss_workspace_bytes(npts) && (uintptr_t)work % 8 == 0,
-                  "prcnn_rpn_loss_forward: workspace of %zu bytes, need %zu (8-byte aligned)", work_bytes, prcnn_rpn_loss_workspace_bytes(npts));
-    P.partial = (double*)work;
-    const int blocks = rl_main_blocks(npts);
-    if (blocks > 0) {
-        hipLaunchKernelGGL(rpn_loss_main_kernel<false>, dim3(blocks), dim3(RL_THREADS), 0, (hipStream_t)stream, P);
-        PRCNN_LAUNCH_CHECK("prcnn_rpn_loss_forward");
-    }
-    hipLaunchKernelGGL(rpn_loss_finalize_kernel, dim3(1), dim3(RL_THREADS), 0, (hipStream_t)stream, (const double*)work, blocks, counts, norm,
-                       P.cfg, terms);
-    PRCNN_LAUNCH_CHECK("prcnn_rpn_loss_forward");
-    return PRCNN_OK;
+    return rl_forward("prcnn_rpn_loss_forward", rpn_cls, ld_cls, rpn_reg, ld_reg, cls_label, label_is_i64, reg_label, npts, C, cfg, counts, norm,
+                      terms, work, work_bytes, false, nullptr, 1.0, stream);
 }
 
 PRCNN_API int prcnn_rpn_loss_backward(const float* rpn_cls, int64_t ld_cls, const float* rpn_reg, int64_t ld_reg, const void* cls_label,
                                       int label_is_i64, const float* reg_label, int64_t npts, int C, const prcnn_rpn_loss_cfg_t* cfg,
                                       const int32_t* counts, const float* norm, const float* grad_out, float* dcls, float* dreg,
                                       prcnn_stream_t stream) {
-    RlParams P;
-    const int rc = rl_params("prcnn_rpn_loss_backward", rpn_cls, ld_cls, rpn_reg, ld_reg, cls_label, label_is_i64, reg_label, npts, C, cfg,
-                             counts, norm, &P);
-    if (rc != PRCNN_OK) return rc;
-    if (npts == 0) return PRCNN_OK;
-    PRCNN_REQUIRE(grad_out && dcls && dreg, "prcnn_rpn_loss_backward: null pointer");
-    PRCNN_REQUIRE((uintptr_t)dreg % 16 == 0, "prcnn_rpn_loss_backward: the rpn_reg gradient must be 16-byte aligned");
-    P.grad_out = grad_out;
-    P.dcls = dcls;
-    P.dreg = dreg;
-    hipLaunchKernelGGL(rpn_loss_main_kernel<true>, dim3(rl_main_blocks(npts)), dim3(RL_THREADS), 0, (hipStream_t)stream, P);
-    PRCNN_LAUNCH_CHECK("prcnn_rpn_loss_backward");
-    return PRCNN_OK;
+    return rl_backward("prcnn_rpn_loss_backward", rpn_cls, ld_cls, rpn_reg, ld_reg, cls_label, label_is_i64, reg_label, npts, C, cfg, counts, norm,
+                       grad_out, dcls, dreg, false, nullptr, 1.0, stream);
 }
+
+PRCNN_API int prcnn_rpn_loss_forward_kind(const float* rpn_cls, int64_t ld_cls, const float* rpn_reg, int64_t ld_reg, const void* cls_label,
+                                          int label_is_i64, const float* reg_label, int64_t npts, int C, const prcnn_rpn_loss_cfg_t* cfg,
+                                          const int32_t* counts, const float* norm, float* terms, void* work, size_t work_bytes,
+                                          const double* cls_sums, double fg_weight, prcnn_stream_t stream) {
+    return rl_forward("prcnn_rpn_loss_forward_kind", rpn_cls, ld_cls, rpn_reg, ld_reg, cls_label, label_is_i64, reg_label, npts, C, cfg, counts,
+                      norm, terms, work, work_bytes, true, cls_sums, fg_weight, stream);
+}
+
+PRCNN_API int prcnn_rpn_loss_backward_kind(const float* rpn_cls, int64_t ld_cls, const float* rpn_reg, int64_t ld_reg, const void* cls_label,
+                                           int label_is_i64, const float* reg_label, int64_t npts, int C, const prcnn_rpn_loss_cfg_t* cfg,
+                                           const int32_t* counts, const float* norm, const float* grad_out, float* dcls, float* dreg,
+                                           const double* cls_sums, double fg_weight, prcnn_stream_t stream) {
+    return rl_backward("prcnn_rpn_loss_backward_kind", rpn_cls, ld_cls, rpn_reg, ld_reg, cls_label, label_is_i64, reg_label, npts, C, cfg, counts,
+                       norm, grad_out, dcls, dreg, true, cls_sums, fg_weight, stream);
+}
+

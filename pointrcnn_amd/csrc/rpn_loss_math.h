@@ -23,6 +23,23 @@
 //               a = t*alpha + (1-t)*(1-alpha); term = mod * a * ce * w          d/dx = a * w * (dmod*ce + mod*(p - t))
 //   softmax CE: log(sum exp(z - max)) - (z[target] - max)                       d/dz_j = exp((z_j - max) - logsum) - [j == target]
 //   smooth-L1:  d = a - b; |d| < 1 ? 0.5*d*d : |d| - 0.5                        d/da = |d| < 1 ? d : sign(d)
+//
+// The other two RPN.LOSS_CLS kinds (train_functions.get_rpn_loss, lib/net/train_functions.py:66-90, lib/utils/loss_utils.py:7-21),
+// p = sigmoid(x) = 1 / (1 + exp(-x)) in float32, t = [label > 0]:
+//   BCE:   F.binary_cross_entropy(p, t, weight=w) with w = FG_WEIGHT (rounded to float32 once) for a foreground row, 1 otherwise:
+//               term = ((t-1) * max(log1p(-p), -100) - t * max(log(p), -100)) * w
+//               d/dx = ((p - t) / max((1-p)*p, 1e-12)) * w * (1-p) * p     (autograd: the BCE backward, then sigmoid's)
+//          the caller sums the terms of the valid rows and scales the sum by norm[0] (1 / max(valid, 1), or world / global valid)
+//   Dice:  lo = min(p, t), hi = max(p, t); with A = sum lo, B = sum hi over the valid rows (the caller's, in double) the loss is
+//          1 - A / max(B, 1) and d/dx = s * (-dlo / max(B, 1) + [B >= 1] * A / max(B, 1)^2 * dhi), where
+//               dlo = (1-p)*p for t = 1, else 0;      dhi = (1-p)*p for t = 0, else 0
+// Where float32 sigmoid saturates: from x ~ 17 on, 1 + exp(-x) rounds to 1 and p == 1; p == 0 only once exp(-x) overflows
+// (x < -88.7), but 1 - p == 1 already from x ~ -17 down.  With p == 1: (1-p)*p == 0, so both derivatives are exactly 0; the BCE
+// term is 100 w against t = 0 (log1p(-1) = -inf, clamped) and 0 against t = 1; Dice has lo = t, hi = 1.  With p == 0: the
+// derivatives are exactly 0 again (the BCE quotient is finite through its 1e-12 floor), the BCE term is 100 w against t = 1 and 0
+// against t = 0; Dice has lo = 0, hi = t.  In between (-88 < x < -17) the BCE term against t = 1 is -log(p) ~ -x, exact to float32,
+// and against t = 0 it is -log1p(-p) ~ p.  This is the composed float32 code's behaviour, value for value; float64 keeps
+// a non-zero derivative up to |x| ~ 37.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -33,6 +50,7 @@
 constexpr int RL_MAX_BINS = 16;           // nb and num_head_bin the kernels accept; ops.RPN_LOSS_MAX_BINS
 constexpr int RL_TERMS = 11;              // cls cls_pos cls_neg x_bin z_bin x_res z_res y_offset ry_bin ry_res size
 enum { RL_CLS = 0, RL_CLS_POS, RL_CLS_NEG, RL_X_BIN, RL_Z_BIN, RL_X_RES, RL_Z_RES, RL_Y_OFF, RL_RY_BIN, RL_RY_RES, RL_SIZE };
+constexpr int RL_KIND_FOCAL = 0, RL_KIND_DICE = 1, RL_KIND_BCE = 2;      // RPN.LOSS_CLS, ops.rpn_loss_cfg's numbering
 
 struct RlConfig {
     float scope, shift_hi, bin, half_bin;     // LOC_SCOPE, 2*LOC_SCOPE - 1e-3, LOC_BIN_SIZE, LOC_BIN_SIZE/2
@@ -121,6 +139,51 @@ RL_FN void rl_focal(float x, float t, float w, const RlConfig& c, float* val, fl
     const float a = c.has_alpha ? t * c.alpha + (1.0f - t) * (1.0f - c.alpha) : 1.0f;
     *val = mod * a * ce * w;
     *dx = a * w * (dmod * ce + mod * (p - t));
+}
+
+// BinaryCrossEntropy term of one point with target t in {0, 1} and weight w, and its derivative in the logit (the operation order
+// of F.binary_cross_entropy and of its and sigmoid's backward; the header comment says what saturation gives)
+RL_FN void rl_bce(float x, float t, float w, float* val, float* dx) {
+    const float p = 1.0f / (1.0f + expf(-x));
+    const float q = 1.0f - p;
+    const float v = (t - 1.0f) * fmaxf(log1pf(-p), -100.0f) - t * fmaxf(logf(p), -100.0f);
+    *val = v * w;
+    float d = (p - t) / fmaxf(q * p, 1e-12f);
+    d = d * w;
+    d = d * q;
+    *dx = d * p;
+}
+
+// DiceLoss addends of one point with target t in {0, 1}: min(p, t), max(p, t) and their derivatives in the logit (one of them is 0)
+RL_FN void rl_dice(float x, float t, float* lo, float* hi, float* dlo, float* dhi) {
+    const float p = 1.0f / (1.0f + expf(-x));
+    const float dp = (1.0f - p) * p;
+    *lo = fminf(p, t);
+    *hi = fmaxf(p, t);
+    *dlo = t > 0.0f ? dp : 0.0f;
+    *dhi = t > 0.0f ? 0.0f : dp;
+}
+
+// the same for a row by its label (rl_label's -1 ignored, 0 background, 1 foreground): an ignored row contributes zeros; a
+// foreground row of the BCE sum weighs fg_weight, a background row 1
+RL_FN void rl_bce_row(float x, int label, float fg_weight, float* val, float* dx) {
+    *val = 0.0f;
+    *dx = 0.0f;
+    if (label >= 0) rl_bce(x, (float)label, label > 0 ? fg_weight : 1.0f, val, dx);
+}
+
+RL_FN void rl_dice_row(float x, int label, float* lo, float* hi, float* dlo, float* dhi) {
+    *lo = *hi = *dlo = *dhi = 0.0f;
+    if (label >= 0) rl_dice(x, (float)label, lo, hi, dlo, dhi);
+}
+
+// d Dice / d logit of a row from its rl_dice_row derivatives, the sums A and B over all valid rows and k = upstream gradient x s:
+// k * (-dlo / max(B, 1) + [B >= 1] * A / max(B, 1)^2 * dhi); each coefficient is formed in double and rounded to float32 once
+RL_FN float rl_dice_grad(float dlo, float dhi, double A, double B, double k) {
+    const double Bc = B > 1.0 ? B : 1.0;
+    const float c_lo = (float)(-k / Bc);
+    const float c_hi = (float)(B >= 1.0 ? k * A / (Bc * Bc) : 0.0);
+    return c_lo * dlo + c_hi * dhi;
 }
 
 // n-way softmax cross-entropy of logits z[0..n) against `target`; max and log-sum are handed back for the derivative

@@ -193,6 +193,36 @@ def rpn_loss_rows(dev, B=16, N=16384, rounds=5):
         print(json.dumps(d), flush=True)
 
 
+def rpn_loss_kind_rows(dev, B=16, N=16384, rounds=5):
+    """`rpn_loss (dice|bce|focal) fwd+bwd`: the inputs of rpn_loss_rows under each RPN.LOSS_CLS, composed torch against the second level
+    of the fused route (get_rpn_loss(fused=2)), alternated in one process; per route the median, minimum and maximum over `rounds`
+    windows of 20 calls.  bench.py's training step always runs the default focal configuration: these rows are the only timing of
+    the other two kinds."""
+    from . import train_functions as tf
+    g = torch.Generator().manual_seed(7)
+    u = torch.rand(B, N, generator=g)
+    lab = torch.where(u < 0.03, 1, torch.where(u < 0.13, -1, 0)).to(dev)
+    reg_lab = (torch.rand(B, N, 7, generator=g) * torch.tensor([6., 2., 6., 1., 1., 2., 6.28]) + torch.tensor([-3., -1., -3., 1., 1., 3., -3.14])).to(dev)
+    cls = torch.randn(B, N, 1, generator=g).to(dev).requires_grad_(True)
+    reg = torch.randn(B, N, 76, generator=g).to(dev).requires_grad_(True)
+    n_fg = int((lab > 0).sum())
+    for kind, loss_cls in (("dice", "DiceLoss"), ("bce", "BinaryCrossEntropy"), ("focal", "SigmoidFocalLoss")):
+        cfg = type("Cfg", (tf.RPNLossConfig,), {"LOSS_CLS": loss_cls})
+
+        def step(fused):
+            cls.grad = reg.grad = None
+            tf.get_rpn_loss(cls, reg, lab, reg_lab, cfg, fused=fused).backward()
+        times = {False: [], 2: []}
+        for _ in range(rounds):
+            for fused in (False, 2):
+                times[fused].append(timeit(lambda: step(fused)))
+        for fused in (False, 2):
+            t = sorted(times[fused])
+            print(json.dumps({"op": "rpn_loss (%s) fwd+bwd (%s)" % (kind, "fused level 2" if fused else "composed"),
+                              "shape": "B%d N%d C76, %d foreground rows" % (B, N, n_fg), "median_us": round(t[len(t) // 2] * 1e6, 1),
+                              "min_us": round(t[0] * 1e6, 1), "max_us": round(t[-1] * 1e6, 1)}), flush=True)
+
+
 def train_split_rows(dev, B=16, rounds=5):
     """`train stack fwd+bwd`: one SharedMLPTrain forward + backward at two RPN training shapes -- an SA2-like padding-free stack
     (4096 -> 1024 centres, radius 2.5, nsample 32, [96 + 3, 64, 96, 128]) and an FP-like plain stack (B x 16 384 rows, [256, 128, 128]) -- with
@@ -622,7 +652,7 @@ def eval_loop_rows(dev, B=16, nbatches=3, rounds=5):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
-    ap.add_argument("--only", default=None, help="run one row family only: eval_stats | optimizer | train_split | train_wgrad | result_writer | eval_loop")
+    ap.add_argument("--only", default=None, help="run one row family only: eval_stats | optimizer | rpn_loss_kinds | train_split | train_wgrad | result_writer | eval_loop")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     if args.only == "result_writer":
@@ -637,6 +667,9 @@ def main():
     if args.only == "optimizer":
         optimizer_rows(dev)
         optimizer_mode_rows(dev)
+        return
+    if args.only == "rpn_loss_kinds":
+        rpn_loss_kind_rows(dev)
         return
     if args.only == "train_split":
         train_split_rows(dev)
@@ -766,6 +799,7 @@ def main():
 
     # ---- the RPN training loss and its gradient: composed torch against the one-pass kernels (csrc/rpn_loss.hip)
     rpn_loss_rows(dev)
+    rpn_loss_kind_rows(dev)
     # ---- the RCNN training loss and its gradient: composed torch against the device passes (csrc/rcnn_loss.hip)
     rcnn_loss_rows(dev)
     # ---- a training stack forward + backward: fp32 MFMA against the opt-in split-bf16 forward / dgrad (csrc/mlp_train.h)

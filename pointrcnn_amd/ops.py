@@ -719,7 +719,9 @@ def _rpn_loss_prelude(rpn_cls, rpn_reg, cls_label, reg_label, counts, norm):
     _chk(reg_label, "rpn_reg_label")
     if reg_label.numel() != npts * 7 or reg_label.shape[-1] != 7:
         raise ValueError("rpn_loss: rpn_reg_label must be (..., 7) with %d rows" % npts)
-    _chk(counts, "counts", _INT, 1); _chk(norm, "norm", _F32, 1)
+    _chk(counts, "counts", _INT, 1)
+    if norm is not None:                               # None: the *_kind exports' single-process normalisers, read from counts
+        _chk(norm, "norm", _F32, 1)
     label, is64 = _rpn_loss_label(cls_label)
     cls_rows, ld_cls = _uniform_rows(rpn_cls.reshape(rpn_cls.shape + (1,)) if rpn_cls.dim() == 1 else rpn_cls)
     reg_rows, ld_reg = _uniform_rows(rpn_reg)
@@ -751,6 +753,59 @@ def rpn_loss_backward(rpn_cls, rpn_reg, cls_label, reg_label, cfg, counts, norm,
     dreg = torch.empty(rpn_reg.shape, dtype=_F32, device=rpn_reg.device)
     _cabi.check(_cabi.lib().prcnn_rpn_loss_backward(*args, ctypes.byref(cfg), _p(counts), _p(norm), _p(grad_out), _p(dcls), _p(dreg),
                                                     _stream()), "prcnn_rpn_loss_backward")
+    return dcls, dreg
+
+
+def rpn_loss_cls_sums(rpn_cls, cls_label):
+    """DiceLoss: rpn_cls (B,N,1) f32, cls_label (B,N) i32 / i64 -> (2) f64 on the device: the sums of min(sigmoid(x), t) and of
+    max(sigmoid(x), t) over the rows with label >= 0.  Two launches, nothing read back; a data-parallel caller all-reduces the
+    result in place before rpn_loss_forward_kind / rpn_loss_backward_kind read it."""
+    if not (isinstance(rpn_cls, torch.Tensor) and rpn_cls.is_cuda and rpn_cls.dtype == _F32):
+        raise RuntimeError("rpn_loss: rpn_cls must be a float32 CUDA(HIP) tensor")
+    label, is64 = _rpn_loss_label(cls_label)
+    npts = label.numel()
+    if rpn_cls.numel() != npts:
+        raise ValueError("rpn_loss: rpn_cls / rpn_cls_label must have %d rows" % npts)
+    cls_rows, ld_cls = _uniform_rows(rpn_cls.reshape(rpn_cls.shape + (1,)) if rpn_cls.dim() == 1 else rpn_cls)
+    sums = torch.empty((2,), dtype=torch.float64, device=label.device)
+    work = _rpn_loss_work(npts, label.device)
+    _cabi.check(_cabi.lib().prcnn_rpn_loss_cls_sums(_p(cls_rows), ld_cls, _p(label), is64, npts, _p(sums), _p(work), work.numel() * 8,
+                                                    _stream()), "prcnn_rpn_loss_cls_sums")
+    return sums
+
+
+def _rpn_loss_kind_args(cfg, cls_sums, fg_weight):
+    if cfg.loss_cls == 1:
+        _chk(cls_sums, "cls_sums", torch.float64, 1)
+        if cls_sums.numel() != 2:
+            raise ValueError("rpn_loss: cls_sums must hold the two sums of rpn_loss_cls_sums")
+    return _p(cls_sums) if cfg.loss_cls == 1 else None, float(fg_weight)
+
+
+def rpn_loss_forward_kind(rpn_cls, rpn_reg, cls_label, reg_label, cfg, counts, norm, cls_sums=None, fg_weight=1.0):
+    """rpn_loss_forward for every RPN.LOSS_CLS (cfg.loss_cls 0 focal: the same launches; 1 DiceLoss; 2 BinaryCrossEntropy).
+    cls_sums: DiceLoss, the (2) f64 of rpn_loss_cls_sums; fg_weight: BinaryCrossEntropy, RPN.FG_WEIGHT.  norm None (DiceLoss,
+    BinaryCrossEntropy): the single-process normalisers, formed from counts on the device.  terms[6:8] are 0 for those two kinds."""
+    args, keep = _rpn_loss_prelude(rpn_cls, rpn_reg, cls_label, reg_label, counts, norm)
+    sums_p, fg_weight = _rpn_loss_kind_args(cfg, cls_sums, fg_weight)
+    terms = torch.empty((9,), dtype=_F32, device=rpn_reg.device)
+    work = _rpn_loss_work(args[7], rpn_reg.device)
+    _cabi.check(_cabi.lib().prcnn_rpn_loss_forward_kind(*args, ctypes.byref(cfg), _p(counts), _p(norm), _p(terms), _p(work),
+                                                        work.numel() * 8, sums_p, fg_weight, _stream()), "prcnn_rpn_loss_forward_kind")
+    return terms
+
+
+def rpn_loss_backward_kind(rpn_cls, rpn_reg, cls_label, reg_label, cfg, counts, norm, grad_out, cls_sums=None, fg_weight=1.0):
+    """rpn_loss_backward for every RPN.LOSS_CLS, arguments as rpn_loss_forward_kind; one launch that writes every entry once"""
+    args, keep = _rpn_loss_prelude(rpn_cls, rpn_reg, cls_label, reg_label, counts, norm)
+    sums_p, fg_weight = _rpn_loss_kind_args(cfg, cls_sums, fg_weight)
+    _chk(grad_out, "grad_out")
+    if grad_out.numel() != 1:
+        raise ValueError("rpn_loss_backward_kind: grad_out must be a scalar")
+    dcls = torch.empty(rpn_cls.shape, dtype=_F32, device=rpn_cls.device)
+    dreg = torch.empty(rpn_reg.shape, dtype=_F32, device=rpn_reg.device)
+    _cabi.check(_cabi.lib().prcnn_rpn_loss_backward_kind(*args, ctypes.byref(cfg), _p(counts), _p(norm), _p(grad_out), _p(dcls), _p(dreg),
+                                                         sums_p, fg_weight, _stream()), "prcnn_rpn_loss_backward_kind")
     return dcls, dreg
 
 
