@@ -346,6 +346,20 @@ int prcnn_mlp_chain_interp(const float* known_cl, int ld_known, const int32_t* i
                            const float* act_bias, int nlayers, const float* const* wpack, const float* const* bias, const int* nout, const int* relu,
                            float* out, int ld_out, int col_off, prcnn_stream_t stream);
 
+/* Up to four prcnn_mlp_chain_group problems in ONE launch (the grouped stacks of one set-abstraction level: both radii, flat and
+ * dense list).  Every field is prcnn_mlp_chain_group's argument of that name.  Each problem is decided as a call of its own
+ * would be; the launch exists when all of them resolve to the same kernel family (the SA-level-0 register kernel, the
+ * straight-line chain or the two-layer stack) and that combination is instantiated -- otherwise PRCNN_EUNSUPPORTED and nothing
+ * is launched: issue the problems one by one.  Same bits as the separate calls (same body on the same rows). */
+typedef struct prcnn_chain_group_problem {
+    const float* xyz; const float* new_xyz; const int32_t* idx; const float* feat_cl;
+    const float* act_wx; const float* act_bias;
+    const float* const* wpack; const float* const* bias; const int* nout; const int* relu;
+    float* out; const int32_t* groups_dev;
+    int ld_feat, B, N, M, nsample, C, nlayers, ld_out, col_off, pool_ns;
+} prcnn_chain_group_problem_t;
+int prcnn_mlp_chain_group_multi(int nprob, const prcnn_chain_group_problem_t* prob, prcnn_stream_t stream);
+
 /* out[r, col_off + c] = max over ns consecutive rows of in (generic nsample fallback for pooling) */
 int prcnn_maxpool_rows(const float* in, int ld_in, int64_t rows_out, int ns, int C, float* out, int ld_out,
                        int col_off, prcnn_stream_t stream);
@@ -596,6 +610,18 @@ int prcnn_segmax_scatter(const float* src, int ld_src, const int32_t* list, cons
 /* dst[list[r], col_off : col_off + C] = src[r, 0:C] for r < *count (count: device i32; max_rows sizes the launch) */
 int prcnn_scatter_rows(const float* src, int ld_src, const int32_t* list, const int32_t* count, int max_rows, int C, float* dst,
                        int ld_dst, int col_off, prcnn_stream_t stream);
+/* Both scales of an MSG level (one new_xyz, no valid_n) split by ONE counter clear and ONE launch: what two prcnn_group_compact
+ * calls give, as sets (list order is arbitrary).  lists_a / lists_b: host arrays of the eight list buffers in prcnn_group_compact's
+ * order (ridx, rnx, slist, soff, scnt, idxn, nxn, listn); counts (6 device i32): [0..2] scale a, [3..5] scale b. */
+int prcnn_group_compact_pair(const int32_t* idx_a, int ns_a, int T_a, const int32_t* idx_b, int ns_b, int T_b, const float* new_xyz,
+                             int B, int N, int M, void* const* lists_a, void* const* lists_b, int32_t* counts, prcnn_stream_t stream);
+/* The pooling launches of one level as ONE launch: nprob <= 4 problems into dst (ld_dst floats per row); host arrays over problems.
+ * off[q] != NULL: prcnn_segmax_scatter(src[q], ld_src[q], list[q], off[q], cnt[q], count[q], max_items[q], C[q], dst, ld_dst, col_off[q]);
+ * off[q] == NULL: prcnn_scatter_rows(src[q], ld_src[q], list[q], count[q], max_items[q], C[q], dst, ld_dst, col_off[q]).
+ * The problems must write disjoint cells. */
+int prcnn_level_pool(int nprob, const float* const* src, const int* ld_src, const int32_t* const* list, const int32_t* const* off,
+                     const int32_t* const* cnt, const int32_t* const* count, const int* max_items, const int* C, const int* col_off,
+                     float* dst, int ld_dst, prcnn_stream_t stream);
 
 /* ======================================================================================================
  * RPN input builder (scene.hip) -- SURVEY 8(f) rank 4.  Replaces the inference branch of

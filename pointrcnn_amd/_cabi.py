@@ -37,6 +37,14 @@ class TrainLayer(ctypes.Structure):
                 ("dW", _P), ("dgamma", _P), ("dbeta", _P)]
 
 
+class ChainGroupProblem(ctypes.Structure):
+    """prcnn_chain_group_problem_t (include/prcnn_pointops.h)"""
+    _fields_ = [("xyz", _P), ("new_xyz", _P), ("idx", _P), ("feat_cl", _P), ("act_wx", _P), ("act_bias", _P),
+                ("wpack", _P), ("bias", _P), ("nout", _P), ("relu", _P), ("out", _P), ("groups_dev", _P),
+                ("ld_feat", _I), ("B", _I), ("N", _I), ("M", _I), ("nsample", _I), ("C", _I), ("nlayers", _I), ("ld_out", _I),
+                ("col_off", _I), ("pool_ns", _I)]
+
+
 class RpnLossCfg(ctypes.Structure):
     """prcnn_rpn_loss_cfg_t (include/prcnn_pointops.h)"""
     _fields_ = [("loc_scope", _D), ("loc_bin_size", _D), ("mean_size", _D * 3), ("gamma", _D), ("alpha", _D), ("loss_weight", _D * 2),
@@ -99,6 +107,7 @@ SIGNATURES = {
     "prcnn_mlp_chain_rows": (_I, [_P, _I, _L, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P]),
     "prcnn_mlp_chain_group": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "prcnn_mlp_chain_interp": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P]),
+    "prcnn_mlp_chain_group_multi": (_I, [_I, _P, _P]),
     "prcnn_maxpool_rows": (_I, [_P, _I, _L, _I, _I, _P, _I, _I, _P]),
     "prcnn_roipool3d": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "prcnn_roipool3d_work_bytes": (_Z, [_I, _I]),
@@ -124,6 +133,8 @@ SIGNATURES = {
     "prcnn_group_compact": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "prcnn_segmax_scatter": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _P, _I, _I, _P]),
     "prcnn_scatter_rows": (_I, [_P, _I, _P, _P, _I, _I, _P, _I, _I, _P]),
+    "prcnn_group_compact_pair": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "prcnn_level_pool": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "prcnn_scene_workspace_bytes": (_Z, [_L, _I]),
     "prcnn_scene_prepare": (_I, [_P, _P, _I, _L, _I, _P, _P, _P, _I, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "prcnn_train_scene_workspace_bytes": (_Z, [_L, _I, _I, _I]),

@@ -44,9 +44,10 @@ constexpr int DEDUP_GRID_CAP = 8192;           // workgroups of the grid-stride 
 
 // NS > 0: nsample known at compile time (a multiple of 4) -- the group's index row is fetched with 16-byte loads, all in
 // flight at once, instead of a dependent scalar walk
+// (the body of group_compact_kernel; `block`: the workgroup's index among the problem's own, wsum / bbase: the workgroup's LDS)
 template <int NS>
-__global__ __launch_bounds__(COMPACT_THREADS) void group_compact_kernel(CompactParams P) {
-    const int g = blockIdx.x * COMPACT_THREADS + threadIdx.x;
+__device__ __forceinline__ void group_compact_body(const CompactParams& P, int block, int (*wsum)[3], int* bbase) {
+    const int g = block * COMPACT_THREADS + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const bool ok = g < P.G;
     const int ns = NS > 0 ? NS : P.ns;
@@ -93,8 +94,6 @@ __global__ __launch_bounds__(COMPACT_THREADS) void group_compact_kernel(CompactP
     const int total = __shfl(incl, 63);
     const unsigned long long bs = __ballot(sparse), bd = __ballot(dense);
     // one atomic per BLOCK and list (same-address atomics serialise in L2: per-wave appends made this kernel latency-bound)
-    __shared__ int wsum[COMPACT_THREADS / 64][3];
-    __shared__ int bbase[3];
     const int wave = threadIdx.x >> 6;
     if (lane == 0) { wsum[wave][0] = total; wsum[wave][1] = (int)__popcll(bd); wsum[wave][2] = (int)__popcll(bs); }
     __syncthreads();
@@ -130,6 +129,23 @@ __global__ __launch_bounds__(COMPACT_THREADS) void group_compact_kernel(CompactP
     }
 }
 
+template <int NS>
+__global__ __launch_bounds__(COMPACT_THREADS) void group_compact_kernel(CompactParams P) {
+    __shared__ int wsum[COMPACT_THREADS / 64][3];
+    __shared__ int bbase[3];
+    group_compact_body<NS>(P, blockIdx.x, wsum, bbase);
+}
+
+// both radii of an MSG level in one launch: blockIdx.y selects the scale, each half is group_compact_kernel's body on its own lists
+// and its own three counters (a workgroup past the end of its scale's groups appends nothing)
+template <int NSA, int NSB>
+__global__ __launch_bounds__(COMPACT_THREADS) void group_compact_pair_kernel(CompactParams A, CompactParams B) {
+    __shared__ int wsum[COMPACT_THREADS / 64][3];
+    __shared__ int bbase[3];
+    if (blockIdx.y == 0) group_compact_body<NSA>(A, blockIdx.x, wsum, bbase);
+    else group_compact_body<NSB>(B, blockIdx.x, wsum, bbase);
+}
+
 __global__ __launch_bounds__(256) void scatter_rows_kernel(const float* __restrict__ src, int ld_src, const int32_t* __restrict__ list,
                                                            const int32_t* __restrict__ count, int C, float* __restrict__ dst, int ld_dst,
                                                            int col_off) {
@@ -155,6 +171,117 @@ __global__ __launch_bounds__(256) void segmax_scatter_kernel(const float* __rest
         for (int r = 1; r < rows; r++) m = fmaxf(m, p[(size_t)r * ld_src]);
         dst[(size_t)list[j] * ld_dst + col_off + c] = m;
     }
+}
+
+// One pool launch per MSG level: blockIdx.y selects one of up to four problems, each segmax_scatter_kernel's loop (off != null:
+// a flat list) or scatter_rows_kernel's (a dense list) into its own column range of the level's output.
+#define LEVEL_POOL_MAX 4
+struct LevelPoolParams {
+    const float* src[LEVEL_POOL_MAX];
+    const int32_t* list[LEVEL_POOL_MAX];
+    const int32_t* off[LEVEL_POOL_MAX];
+    const int32_t* cnt[LEVEL_POOL_MAX];
+    const int32_t* count[LEVEL_POOL_MAX];
+    int ld_src[LEVEL_POOL_MAX], C[LEVEL_POOL_MAX], col_off[LEVEL_POOL_MAX];
+    float* dst;
+    int ld_dst;
+};
+
+__global__ __launch_bounds__(256) void level_pool_kernel(LevelPoolParams L) {
+    const int q = blockIdx.y;
+    const float* __restrict__ src = L.src[q];
+    const int32_t* __restrict__ list = L.list[q];
+    const int32_t* __restrict__ off = L.off[q];
+    const int32_t* __restrict__ cnt = L.cnt[q];
+    const int ld_src = L.ld_src[q], C = L.C[q], col_off = L.col_off[q], ld_dst = L.ld_dst;
+    float* __restrict__ dst = L.dst;
+    const long total = (long)(*L.count[q]) * C;
+    if (off) {
+        for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+            const long j = e / C;
+            const int c = (int)(e - j * C);
+            const float* p = src + (size_t)off[j] * ld_src + c;
+            const int rows = cnt[j];
+            float m = p[0];
+            for (int r = 1; r < rows; r++) m = fmaxf(m, p[(size_t)r * ld_src]);
+            dst[(size_t)list[j] * ld_dst + col_off + c] = m;
+        }
+    } else {
+        for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+            const long r = e / C;
+            const int c = (int)(e - r * C);
+            dst[(size_t)list[r] * ld_dst + col_off + c] = src[(size_t)r * ld_src + c];
+        }
+    }
+}
+
+static int compact_check(const char* who, int B, int N, int M, int nsample, int sparse_max) {
+    PRCNN_REQUIRE(B >= 0 && N > 0 && M >= 0 && nsample > 0, "%s: bad shape B=%d N=%d M=%d nsample=%d", who, B, N, M, nsample);
+    PRCNN_REQUIRE(sparse_max >= 1 && sparse_max <= nsample, "%s: sparse_max=%d (1..nsample)", who, sparse_max);
+    PRCNN_REQUIRE((long)B * N < 2147483647L && (long)B * M * sparse_max < 2147483647L, "%s: 32-bit row index overflow", who);
+    return PRCNN_OK;
+}
+
+// Both scales of an MSG level (shared new_xyz, no valid_n): ONE clear of counts[6] ([0..2] scale a, [3..5] scale b, each as
+// prcnn_group_compact's counts) and ONE launch.  lists_a / lists_b: the eight list buffers of prcnn_group_compact in its order
+// (ridx, rnx, slist, soff, scnt, idxn, nxn, listn).
+PRCNN_API int prcnn_group_compact_pair(const int32_t* idx_a, int ns_a, int T_a, const int32_t* idx_b, int ns_b, int T_b, const float* new_xyz,
+                                       int B, int N, int M, void* const* lists_a, void* const* lists_b, int32_t* counts, prcnn_stream_t stream) {
+    int rc = compact_check("prcnn_group_compact_pair", B, N, M, ns_a, T_a);
+    if (rc) return rc;
+    rc = compact_check("prcnn_group_compact_pair", B, N, M, ns_b, T_b);
+    if (rc) return rc;
+    PRCNN_REQUIRE(counts && lists_a && lists_b, "prcnn_group_compact_pair: null counts / list table");
+    hipStream_t s = (hipStream_t)stream;
+    if (prcnn_fill_words(counts, 0u, 6, s) != hipSuccess) return prcnn_fail(PRCNN_EHIP, "prcnn_group_compact_pair: clearing the counters failed");
+    if (B == 0 || M == 0) return PRCNN_OK;
+    PRCNN_REQUIRE(idx_a && idx_b && new_xyz, "prcnn_group_compact_pair: null pointer");
+    CompactParams P[2];
+    for (int q = 0; q < 2; q++) {
+        void* const* L = q ? lists_b : lists_a;
+        const int ns = q ? ns_b : ns_a, T = q ? T_b : T_a;
+        for (int i = 0; i < 5; i++) PRCNN_REQUIRE(L[i], "prcnn_group_compact_pair: null pointer");
+        PRCNN_REQUIRE(T == ns || (L[5] && L[6] && L[7]), "prcnn_group_compact_pair: null dense-list pointer");
+        P[q].idx = q ? idx_b : idx_a; P[q].new_xyz = new_xyz;
+        P[q].ridx = (int32_t*)L[0]; P[q].rnx = (float*)L[1]; P[q].slist = (int32_t*)L[2]; P[q].soff = (int32_t*)L[3]; P[q].scnt = (int32_t*)L[4];
+        P[q].idxn = (int32_t*)L[5]; P[q].nxn = (float*)L[6]; P[q].listn = (int32_t*)L[7];
+        P[q].counts = counts + 3 * q; P[q].valid_n = nullptr; P[q].G = B * M; P[q].N = N; P[q].M = M; P[q].ns = ns; P[q].T = T;
+    }
+    const dim3 grid(prcnn_divup(B * M, COMPACT_THREADS), 2);
+    const bool vec = ((uintptr_t)idx_a % 16) == 0 && ((uintptr_t)idx_b % 16) == 0;
+    if (vec && ns_a == 16 && ns_b == 32) hipLaunchKernelGGL((group_compact_pair_kernel<16, 32>), grid, dim3(COMPACT_THREADS), 0, s, P[0], P[1]);
+    else hipLaunchKernelGGL((group_compact_pair_kernel<0, 0>), grid, dim3(COMPACT_THREADS), 0, s, P[0], P[1]);
+    PRCNN_LAUNCH_CHECK("prcnn_group_compact_pair");
+    return PRCNN_OK;
+}
+
+// nprob <= 4 problems into one level output dst (ld_dst floats per row).  Problem q: off[q] != null -- prcnn_segmax_scatter of the
+// flat list (list, off, cnt)[q]; off[q] == null -- prcnn_scatter_rows of the dense list list[q]; count[q] the device-side length,
+// max_items[q] its bound (0: the problem is skipped), C[q] columns at col_off[q].  The problems' cells must be disjoint.
+PRCNN_API int prcnn_level_pool(int nprob, const float* const* src, const int* ld_src, const int32_t* const* list, const int32_t* const* off,
+                               const int32_t* const* cnt, const int32_t* const* count, const int* max_items, const int* C, const int* col_off,
+                               float* dst, int ld_dst, prcnn_stream_t stream) {
+    PRCNN_REQUIRE(nprob >= 1 && nprob <= LEVEL_POOL_MAX, "prcnn_level_pool: nprob=%d (1..%d)", nprob, LEVEL_POOL_MAX);
+    PRCNN_REQUIRE(src && ld_src && list && off && cnt && count && max_items && C && col_off, "prcnn_level_pool: null table");
+    LevelPoolParams L = {};
+    int n = 0;
+    long need = 0;
+    for (int q = 0; q < nprob; q++) {
+        PRCNN_REQUIRE(max_items[q] >= 0 && C[q] > 0 && ld_src[q] >= C[q] && ld_dst >= col_off[q] + C[q] && col_off[q] >= 0,
+                      "prcnn_level_pool: bad shape of problem %d", q);
+        if (max_items[q] == 0) continue;
+        PRCNN_REQUIRE(src[q] && list[q] && count[q] && dst && (!off[q] || cnt[q]), "prcnn_level_pool: null pointer in problem %d", q);
+        L.src[n] = src[q]; L.list[n] = list[q]; L.off[n] = off[q]; L.cnt[n] = cnt[q]; L.count[n] = count[q];
+        L.ld_src[n] = ld_src[q]; L.C[n] = C[q]; L.col_off[n] = col_off[q];
+        need = max(need, (long)prcnn_divup((long)max_items[q] * C[q], 256));
+        n++;
+    }
+    if (n == 0) return PRCNN_OK;
+    L.dst = dst; L.ld_dst = ld_dst;
+    // (the cap is per problem: the live problems of a level share the chip, the empty ones leave at once)
+    hipLaunchKernelGGL(level_pool_kernel, dim3((unsigned)min(need, (long)(DEDUP_GRID_CAP / 2)), n), dim3(256), 0, (hipStream_t)stream, L);
+    PRCNN_LAUNCH_CHECK("prcnn_level_pool");
+    return PRCNN_OK;
 }
 
 PRCNN_API int prcnn_group_compact(const int32_t* idx, const float* new_xyz, int B, int N, int M, int nsample, int sparse_max,

@@ -1593,15 +1593,14 @@ __device__ __forceinline__ void fchain_layer(const f32x16 (&in)[NBI], f32x16 (&o
 #define FAST_RING_INTERP 2
 #endif
 template <int MODE> struct FAST_RING { static constexpr int D = MODE == MODE_PLAIN ? FAST_RING_PLAIN : (MODE == MODE_GROUP ? FAST_RING_GROUP : FAST_RING_INTERP); };
+// (bid: the workgroup's index among the problem's own; the four LDS arrays are the workgroup's, declared by the kernel)
 template <int MODE, int NB0, int NB1, int NB2>
-// (the plain-row instances with a narrow second layer -- the heads -- are asked for three waves per SIMD: 164 registers without a spill where the compiler
-//  settles at 180 unprompted, -3 % per launch, and a wave still fits next to a resident FPS workgroup; the interpolating
-//  instance spills at that budget, 235 -> 277 us, and keeps two)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MODE == MODE_PLAIN && NB1 <= 3) ? 3 : 2, 8))) void mlp_chain_fast_kernel(const ChainParams Cin) {
+__device__ __forceinline__ void mlp_chain_fast_body(const ChainParams& Cin, long bid, float (*Ws)[CH_STAGE_TILES * 256], float* s_wx, float* s_b,
+                                                    float (*s_bias)[128]) {
     ChainParams C = Cin;
     C.a.rows = effective_rows(Cin.a);
     const MlpParams& P = C.a;
-    const long tile_id = tile_of_block(P, blockIdx.x);
+    const long tile_id = tile_of_block(P, bid);
     if (tile_id * 128 >= P.rows) return;
     if (tile_dead(P, tile_id * 128)) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1611,10 +1610,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MODE == MO
     RowMeta<MODE> meta;
     make_meta<MODE>(P, valid ? row : P.rows - 1, meta);
 
-    __shared__ __attribute__((aligned(16))) float Ws[2][CH_STAGE_TILES * 256];
-    __shared__ __attribute__((aligned(16))) float s_wx[(FAST_MAX_K + 16) * 3];
-    __shared__ __attribute__((aligned(16))) float s_b[FAST_MAX_K + 16];
-    __shared__ __attribute__((aligned(16))) float s_bias[3][128];      // layer biases: an LDS read at use instead of an L1/L2 trip
     if (MODE == MODE_GROUP)
         for (int t = threadIdx.x; t < P.K * 3; t += 256) s_wx[t] = P.act_wx[t];
     if (MODE != MODE_PLAIN)
@@ -1698,6 +1693,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MODE == MO
             chain_store<NB2>(C, a2, C.N2, row, valid, lane, h);
         }
     }
+}
+#define FAST_CHAIN_LDS                                                                                                          \
+    __shared__ __attribute__((aligned(16))) float Ws[2][CH_STAGE_TILES * 256];                                                  \
+    __shared__ __attribute__((aligned(16))) float s_wx[(FAST_MAX_K + 16) * 3];                                                  \
+    __shared__ __attribute__((aligned(16))) float s_b[FAST_MAX_K + 16];                                                         \
+    __shared__ __attribute__((aligned(16))) float s_bias[3][128]      /* layer biases: an LDS read at use instead of an L1/L2 trip */
+template <int MODE, int NB0, int NB1, int NB2>
+// (the plain-row instances with a narrow second layer -- the heads -- are asked for three waves per SIMD: 164 registers without a spill where the compiler
+//  settles at 180 unprompted, -3 % per launch, and a wave still fits next to a resident FPS workgroup; the interpolating
+//  instance spills at that budget, 235 -> 277 us, and keeps two)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MODE == MODE_PLAIN && NB1 <= 3) ? 3 : 2, 8))) void mlp_chain_fast_kernel(const ChainParams Cin) {
+    FAST_CHAIN_LDS;
+    mlp_chain_fast_body<MODE, NB0, NB1, NB2>(Cin, blockIdx.x, Ws, s_wx, s_b, s_bias);
 }
 
 // =====================================================================================================
@@ -2512,8 +2520,9 @@ __global__ __launch_bounds__(PERS_WAVES * 64) void mlp_chain_pers_kernel(const C
 // no LDS, no barriers -- and requests the next tile's neighbour index / coordinates while the current tile multiplies.
 // Same MFMA order, bias/ReLU arithmetic and pooling as mlp_chain_kernel: bit-identical results.
 // =====================================================================================================
+// (blk / nblk: the workgroup's index among, and the number of, the workgroups that walk THIS problem's tiles)
 template <int KB1, int KB2, int NB2, int NS>
-__global__ __launch_bounds__(256) void sa_xyz_chain_kernel(const ChainParams Cin) {
+__device__ __forceinline__ void sa_xyz_chain_body(const ChainParams& Cin, int blk, int nblk) {
     ChainParams C = Cin;
     C.a.rows = effective_rows(Cin.a);
     const MlpParams& P = C.a;
@@ -2536,8 +2545,8 @@ __global__ __launch_bounds__(256) void sa_xyz_chain_kernel(const ChainParams Cin
         for (int ob = 0; ob < NB2; ob++) b2[ob][q] = C.bias2 ? ld4(C.bias2 + ob * 32 + 8 * q + 4 * h) : zero4;
     }
     const long ntiles = (P.rows + 31) >> 5;
-    const long stride = (long)gridDim.x * 4;
-    long tile = (long)blockIdx.x * 4 + wave;
+    const long stride = (long)nblk * 4;
+    long tile = (long)blk * 4 + wave;
     if (tile >= ntiles) return;
     // neighbour index two tiles ahead, coordinates one tile ahead
     auto row_of = [&](long t) { long r = (t < ntiles ? t : ntiles - 1) * 32 + j; return r < P.rows ? r : P.rows - 1; };
@@ -2616,6 +2625,10 @@ __global__ __launch_bounds__(256) void sa_xyz_chain_kernel(const ChainParams Cin
         r_nxt = r_nn; p_nxt = p_nn;
     }
 }
+template <int KB1, int KB2, int NB2, int NS>
+__global__ __launch_bounds__(256) void sa_xyz_chain_kernel(const ChainParams Cin) {
+    sa_xyz_chain_body<KB1, KB2, NB2, NS>(Cin, blockIdx.x, gridDim.x);
+}
 
 __global__ void pack_weight_kernel(const float* __restrict__ w, int Nout, int K, int k_rot, int KB, int NB,
                                    float* __restrict__ wpack) {
@@ -2660,8 +2673,11 @@ __global__ void maxpool_rows_kernel(const float* __restrict__ in, int ld_in, lon
 #define ST_MAX_K0 256
 #define ST_MAX_NB0 12
 #define ST_RING 8                // k-blocks of weights in flight per wave (one wave per SIMD: registers are plentiful)
+// (blk / nblk: the workgroup's index among, and the number of, the workgroups that walk THIS problem's units; tiles_all: the live
+//  row tiles of every problem the launch carries, which the split is sized for -- negative: this problem's own; st_lds: the
+//  workgroup's dynamic LDS)
 template <int NBW0>
-__global__ __launch_bounds__(256, 1) void mlp_stack2_kernel(const ChainParams Cin) {
+__device__ __forceinline__ void mlp_stack2_body(const ChainParams& Cin, int blk, int nblk, int tiles_all, float* st_lds) {
     MlpParams P = Cin.a;
     P.rows = effective_rows(Cin.a);
     // layer-B column groups (4 blocks, one per wave) are dealt to `ysplit` workgroups per row tile: 1 when the list alone
@@ -2669,11 +2685,11 @@ __global__ __launch_bounds__(256, 1) void mlp_stack2_kernel(const ChainParams Ci
     // knows the padded bound: 8192 rows for the 2048 that SA4 really has).  The live workgroups are the FIRST tiles * ysplit
     // of the 1-D grid, so that the dispatcher spreads them over XCDs and CUs like any dense launch; the rest leave.
     const int tiles_eff = (int)((P.rows + ST_ROWS - 1) / ST_ROWS);
-    const int ysplit = min(Cin.stack_split, max(1, (256 + tiles_eff - 1) / max(tiles_eff, 1)));
-    extern __shared__ __attribute__((aligned(16))) float st_lds[];
+    const int tiles_split = tiles_all >= 0 ? tiles_all : tiles_eff;
+    const int ysplit = min(Cin.stack_split, max(1, (256 + tiles_split - 1) / max(tiles_split, 1)));
     // (the grid is capped: the padded bound can be 16 x the live list, and thousands of workgroups that only leave cost more than
     //  the loop does)
-    for (long unit = blockIdx.x; unit < (long)tiles_eff * ysplit; unit += gridDim.x) {
+    for (long unit = blk; unit < (long)tiles_eff * ysplit; unit += nblk) {
     const int tile = (int)(unit / ysplit), ysl = (int)(unit - (long)tile * ysplit);
     const long row0 = (long)tile * ST_ROWS;
     const int lda = P.K + 4;                               // row strides (floats): +4 keeps the ds_read_b128 of 16 rows conflict-free
@@ -2837,6 +2853,11 @@ __global__ __launch_bounds__(256, 1) void mlp_stack2_kernel(const ChainParams Ci
     __syncthreads();                                        // the LDS tiles are rebuilt by the next unit
     }
 }
+template <int NBW0>
+__global__ __launch_bounds__(256, 1) void mlp_stack2_kernel(const ChainParams Cin) {
+    extern __shared__ __attribute__((aligned(16))) float st_lds[];
+    mlp_stack2_body<NBW0>(Cin, blockIdx.x, gridDim.x, -1, st_lds);
+}
 
 // =====================================================================================================
 // SHORT plain layers (round 2): a long-K layer on a few thousand rows (FP3's hoisted 2048 x 1024 -> 512 product) gives the
@@ -2937,6 +2958,9 @@ __global__ __launch_bounds__(256, 1) void mlp_rows32_kernel(const MlpParams Pin,
 
 // parameter fills, launch decisions, the launch site and the exports (host code only)
 #include "mlp_host.h"
+
+// the grouped stacks of one set-abstraction level in one launch: the kernel bodies above, several problems per launch
+#include "mlp_multi.h"
 
 // training-mode SharedMLP (forward with batch statistics, dgrad, wgrad): shares the row fetchers and weight image above
 #include "mlp_train.h"

@@ -607,19 +607,28 @@ PRCNN_API int prcnn_mlp_chain_rows(const float* in, int ld_in, int64_t rows, int
     return dispatch_chain(MODE_PLAIN, C, (hipStream_t)stream);
 }
 
+// the checks and fills of prcnn_mlp_chain_group (prcnn_mlp_chain_group_multi runs them per problem, under the same messages)
+static int fill_chain_group(ChainParams& C, const float* xyz, const float* new_xyz, const int32_t* idx, const float* feat_cl, int ld_feat, int B, int N,
+                            int M, int nsample, int C_, const float* act_wx, const float* act_bias, int nlayers, const float* const* wpack,
+                            const float* const* bias, const int* nout, const int* relu, float* out, int ld_out, int col_off, int pool_ns,
+                            const int32_t* groups_dev) {
+    PRCNN_REQUIRE(xyz && idx && (C_ == 0 || feat_cl), "prcnn_mlp_chain_group: null pointer");
+    PRCNN_REQUIRE(B >= 0 && N > 0 && M > 0 && nsample > 0 && C_ >= 0 && (C_ == 0 || ld_feat >= C_), "prcnn_mlp_chain_group: bad shape");
+    int rc = fill_chain(C, nlayers, wpack, bias, nout, relu, out, ld_out, col_off, pool_ns);
+    if (rc) return rc;
+    PRCNN_REQUIRE(pool_ns == 0 || pool_ns == nsample, "prcnn_mlp_chain_group: pool_ns must equal nsample");
+    return fill_group(C.a, xyz, new_xyz, idx, feat_cl, ld_feat, B, N, M, nsample, C_, act_wx, act_bias, groups_dev);
+}
+
 PRCNN_API int prcnn_mlp_chain_group(const float* xyz, const float* new_xyz, const int32_t* idx, const float* feat_cl,
                                     int ld_feat, int B, int N, int M, int nsample, int C_, const float* act_wx,
                                     const float* act_bias, int nlayers,
                                     const float* const* wpack, const float* const* bias, const int* nout,
                                     const int* relu, float* out, int ld_out, int col_off, int pool_ns,
                                     const int32_t* groups_dev, prcnn_stream_t stream) {
-    PRCNN_REQUIRE(xyz && idx && (C_ == 0 || feat_cl), "prcnn_mlp_chain_group: null pointer");
-    PRCNN_REQUIRE(B >= 0 && N > 0 && M > 0 && nsample > 0 && C_ >= 0 && (C_ == 0 || ld_feat >= C_), "prcnn_mlp_chain_group: bad shape");
     ChainParams C = {};
-    int rc = fill_chain(C, nlayers, wpack, bias, nout, relu, out, ld_out, col_off, pool_ns);
-    if (rc) return rc;
-    PRCNN_REQUIRE(pool_ns == 0 || pool_ns == nsample, "prcnn_mlp_chain_group: pool_ns must equal nsample");
-    rc = fill_group(C.a, xyz, new_xyz, idx, feat_cl, ld_feat, B, N, M, nsample, C_, act_wx, act_bias, groups_dev);
+    const int rc = fill_chain_group(C, xyz, new_xyz, idx, feat_cl, ld_feat, B, N, M, nsample, C_, act_wx, act_bias, nlayers, wpack, bias, nout, relu, out,
+                                    ld_out, col_off, pool_ns, groups_dev);
     if (rc) return rc;
     return dispatch_chain(MODE_GROUP, C, (hipStream_t)stream);
 }

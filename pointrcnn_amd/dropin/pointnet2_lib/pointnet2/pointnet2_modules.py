@@ -32,6 +32,9 @@ GROUP_DEDUP = os.environ.get("PRCNN_GROUP_DEDUP", "1") != "0"       # padding-fr
 DEDUP_SPARSE_DIV = int(os.environ.get("PRCNN_DEDUP_SPARSE_DIV", "4"))  # groups with <= nsample/DIV hits run as flat rows
 STACK_ALL_FLAT = os.environ.get("PRCNN_STACK_ALL_FLAT", "1") != "0"      # A/B switch: stack-kernel scales keep a dense list when off
 STACK_ALL_FLAT_MAX_ROWS = 1 << 20
+# both radii of an MSG level through one split, one grouped-stack and one pool launch (_forward_merged); 0 = A/B switch: today's
+# per-radius launch sequence, same bits
+LEVEL_MERGE = os.environ.get("PRCNN_LEVEL_MERGE", "1") != "0"
 # largest layer-to-layer intermediate of a padding-free scale's dense list allocated at once (see _run_scale); 0 = never slice (A/B)
 DENSE_CHUNK_BYTES = int(float(os.environ.get("PRCNN_DENSE_CHUNK_MB", "2048")) * 2 ** 20) or (1 << 62)
 TRAIN_FUSED = os.environ.get("PRCNN_TRAIN_FUSED", "1") != "0"          # hand-written training-mode SharedMLP (train_mlp.py)
@@ -77,14 +80,19 @@ class _SliceCount:
         self.counts = counts
 
 
+def _one_launch(src, layers, act, ns, pool):
+    """True when _run_scale sends this scale's whole stack to ops.mlp_chain_group: one chain or stack launch"""
+    # layers wider than 128 channels: only the two-layer stack kernel takes them (hoisted form on a flat, un-pooled row list)
+    wide = any(l.nout > 128 for l in layers)
+    return (ns == 1 or (pool and ns in (16, 32))) and (not wide or (ns == 1 and _stack_scale(layers, act, src))) \
+        and ops.chain_supported(1, layers, ns if pool else 0)
+
+
 def _run_scale(xyz, ctr, idx, src, layers, act, out, ns, pool, groups_dev):
     """One grouping scale: gather + SharedMLP (+ max-pool over the nsample rows when `pool`), the register-resident chain
     kernel where an instance exists, LDS-tiled layer kernels otherwise.  groups_dev: device-side group count (dedup)."""
     pool_ns = ns if pool else 0
-    # layers wider than 128 channels: only the two-layer stack kernel takes them (hoisted form on a flat, un-pooled row list)
-    wide = any(l.nout > 128 for l in layers)
-    if (ns == 1 or (pool and ns in (16, 32))) and (not wide or (ns == 1 and _stack_scale(layers, act, src))) \
-            and ops.chain_supported(1, layers, pool_ns):
+    if _one_launch(src, layers, act, ns, pool):
         return ops.mlp_chain_group(xyz, ctr, idx, src, layers, out=out, pool_ns=pool_ns, act=act, groups_dev=groups_dev)
     if len(layers) == 1:
         return ops.mlp_group(xyz, ctr, idx, src, layers[0], out=out, pool_ns=pool_ns, act=act, groups_dev=groups_dev)
@@ -261,6 +269,10 @@ class _PointnetSAModuleBase(nn.Module):
                     hoist.append((z_all[..., zoff:zoff + p[0].shape[0]], (p[1], p[2])))
                     zoff += p[0].shape[0]
 
+        if LEVEL_MERGE and GROUP_DEDUP and valid_n is None and len(self.groupers) == 2 and len(qg) == 2 and new_xyz is not None \
+                and self._forward_merged(xyz, new_xyz, idxs, hoist, feat_cl, out_cl, c_outs):
+            return new_xyz, out_cl.transpose(1, 2)
+
         col = 0
         for i, (g, mlp) in enumerate(zip(self.groupers, self.mlps)):
             group_all = not isinstance(g, pointnet2_utils.QueryAndGroup)
@@ -307,6 +319,52 @@ class _PointnetSAModuleBase(nn.Module):
                     ops.maxpool_rows(x, ns, out=dst)
             col += c_outs[i]
         return new_xyz, out_cl.transpose(1, 2)
+
+    def _forward_merged(self, xyz, new_xyz, idxs, hoist, feat_cl, out_cl, c_outs):
+        """An MSG level of two padding-free scales whose stacks are one launch each: ONE split (both radii), ONE grouped-stack launch
+        (flat and dense list of both radii) and ONE pool launch instead of 2 x (clear, split, 1-2 stacks, 1-2 pools).  The same kernel
+        bodies on the same rows: same bits.  False, with nothing launched, when the level is not of that kind."""
+        B, N, _ = xyz.shape
+        M = new_xyz.shape[1]
+        scales = []
+        for i, mlp in enumerate(self.mlps):
+            ns = idxs[i].shape[2]
+            mods = mlp.layers()
+            if hoist is not None:
+                src, act = hoist[i]
+                layers = [m.packed() for m in mods[1:]]
+            else:
+                src, act = feat_cl, None
+                layers = [mods[0].packed(k_rot=3 if feat_cl is not None else 0)] + [m.packed() for m in mods[1:]]
+            all_flat = STACK_ALL_FLAT and B * M * ns <= STACK_ALL_FLAT_MAX_ROWS and _stack_scale(layers, act, src)
+            if ns not in _POOL_FUSED or not _one_launch(src, layers, act, 1, False) or not (all_flat or _one_launch(src, layers, act, ns, True)):
+                return False
+            scales.append((ns, src, act, layers, all_flat))
+        (ns_a, _, _, _, flat_a), (ns_b, _, _, _, flat_b) = scales
+        sps = ops.GroupSplit.pair(idxs[0], ns_a if flat_a else max(1, ns_a // DEDUP_SPARSE_DIV),
+                                  idxs[1], ns_b if flat_b else max(1, ns_b // DEDUP_SPARSE_DIV), new_xyz, N)
+        xyz_f = xyz.view(1, B * N, 3)
+        dst = out_cl.view(B * M, -1)
+        flat, dense, pools, col = [], [], [], 0
+        # heaviest first: the wider scale before the narrower one, the flat lists before the dense ones
+        order = sorted(range(2), key=lambda i: -sum(l.nout for l in scales[i][3]) * scales[i][0])
+        cols = [0, c_outs[0]]
+        for i in order:
+            (ns, src, act, layers, all_flat), sp, col = scales[i], sps[i], cols[i]
+            src_f = None if src is None else _flatten_frames(src)
+            t1 = torch.empty((sp.max_rows, c_outs[i]), dtype=torch.float32, device=xyz.device)      # (both scales' alive together)
+            flat.append(dict(xyz=xyz_f, new_xyz=sp.rnx, idx=sp.ridx, feat_cl=src_f, layers=layers, out=(t1, 0), pool_ns=0, act=act, groups_dev=sp.rows))
+            pools.append((t1, sp, col, "flat"))
+            if not all_flat:
+                tn = torch.empty((sp.G, c_outs[i]), dtype=torch.float32, device=xyz.device)
+                dense.append(dict(xyz=xyz_f, new_xyz=sp.nxn, idx=sp.idxn, feat_cl=src_f, layers=layers, out=(tn, 0), pool_ns=ns, act=act,
+                                  groups_dev=sp.count_dense))
+                pools.append((tn, sp, col, "dense"))
+        if not ops.mlp_chain_group_multi(flat + dense):
+            for pr in flat + dense:                           # (no kernel for this combination: the same launches one by one)
+                ops.mlp_chain_group(**pr)
+        ops.level_pool(pools, dst)
+        return True
 
 
 class PointnetSAModuleMSG(_PointnetSAModuleBase):

@@ -459,6 +459,30 @@ def mlp_chain_group(xyz, new_xyz, idx, feat_cl, layers, out=None, pool_ns=0, act
     return buf
 
 
+def mlp_chain_group_multi(problems):
+    """Up to four mlp_chain_group problems -- dicts of its arguments (xyz, new_xyz, idx, feat_cl, layers, out, pool_ns, act,
+    groups_dev; out is required) -- in ONE launch, heaviest first.  False, with nothing launched, when the library has no kernel
+    for the combination (PRCNN_EUNSUPPORTED): the caller issues them one by one."""
+    arr = (_cabi.ChainGroupProblem * len(problems))()
+    for q, pr in zip(arr, problems):
+        layers = pr["layers"]
+        B, N, M, ns, C, ld_feat, awx, ab, buf, ld_out, col_off = _group_prelude(pr["xyz"], pr["idx"], pr.get("feat_cl"), layers[-1], pr["out"],
+                                                                                pr.get("pool_ns", 0), pr.get("act"))
+        a = _chain_args(layers)
+        q.xyz, q.new_xyz, q.idx, q.feat_cl, q.act_wx, q.act_bias = (_p(pr["xyz"]), _p(pr.get("new_xyz")), _p(pr["idx"]), _p(pr.get("feat_cl")),
+                                                                    _p(awx), _p(ab))
+        q.wpack, q.bias = ctypes.cast(a.wpack, ctypes.c_void_p), ctypes.cast(a.bias, ctypes.c_void_p)
+        q.nout, q.relu = ctypes.cast(a.nout, ctypes.c_void_p), ctypes.cast(a.relu, ctypes.c_void_p)
+        q.out, q.groups_dev = _p(buf), _p(pr.get("groups_dev"))
+        q.ld_feat, q.B, q.N, q.M, q.nsample, q.C, q.nlayers = ld_feat, B, N, M, ns, C, a.n
+        q.ld_out, q.col_off, q.pool_ns = ld_out, col_off, pr.get("pool_ns", 0)
+    rc = _cabi.lib().prcnn_mlp_chain_group_multi(len(problems), arr, _stream())
+    if rc == _cabi.EUNSUPPORTED:
+        return False
+    _cabi.check(rc, "prcnn_mlp_chain_group_multi")
+    return True
+
+
 def mlp_chain_interp(known_cl, idx3, w3, skip_cl, layers, out=None, act_bias=None):
     B, n, m, C2, C1, ld_skip, buf, ld_out, col_off = _interp_prelude(known_cl, idx3, skip_cl, layers[-1], out)
     a = _chain_args(layers)
@@ -1324,26 +1348,46 @@ class GroupSplit:
     the sparse groups (at most sparse_max hits) and the list of dense groups.  All tensors are worst-case sized; counts
     (3,) int32 holds [flat rows, dense groups, sparse groups]."""
 
-    def __init__(self, idx, new_xyz, N, sparse_max, valid_n=None):
+    def __init__(self, idx, new_xyz, N, sparse_max, valid_n=None, counts=None):
+        """counts: a (3,) int32 view to use instead of a fresh tensor -- the lists are then allocated only and the caller splits
+        (GroupSplit.pair)"""
         _chk(idx, "idx", _INT, 3)
         _chk(new_xyz, "new_xyz", ndim=3)
         B, M, ns = idx.shape
         G, dev = B * M, idx.device
         T = max(1, min(int(sparse_max), ns))
-        self.G, self.ns, self.max_rows = G, ns, G * T
+        self.G, self.ns, self.T, self.max_rows = G, ns, T, G * T
         e = lambda shape, dt=_INT: torch.empty(shape, dtype=dt, device=dev)      # noqa: E731
         self.ridx, self.rnx = e((1, G * T, 1)), e((1, G * T, 3), _F32)
         self.slist, self.soff, self.scnt = e((G,)), e((G,)), e((G,))
         self.idxn, self.nxn, self.listn = e((1, G, ns)), e((1, G, 3), _F32), e((G,))
-        self.counts = e((3,))
+        self.counts = e((3,)) if counts is None else counts
         if valid_n is not None and (valid_n.dtype != _INT or valid_n.numel() != B or not valid_n.is_contiguous()):
             raise RuntimeError("valid_n must be a contiguous (B,) int32 tensor")
-        _cabi.check(_cabi.lib().prcnn_group_compact(_p(idx), _p(new_xyz), B, N, M, ns, T, _p(valid_n), _p(self.ridx), _p(self.rnx), _p(self.slist),
-                                                    _p(self.soff), _p(self.scnt), _p(self.idxn), _p(self.nxn), _p(self.listn),
-                                                    _p(self.counts), _stream()), "prcnn_group_compact")
+        if counts is None:
+            _cabi.check(_cabi.lib().prcnn_group_compact(_p(idx), _p(new_xyz), B, N, M, ns, T, _p(valid_n), _p(self.ridx), _p(self.rnx), _p(self.slist),
+                                                        _p(self.soff), _p(self.scnt), _p(self.idxn), _p(self.nxn), _p(self.listn),
+                                                        _p(self.counts), _stream()), "prcnn_group_compact")
         self.rows, self.count_dense, self.count_sparse = self.counts[0:1], self.counts[1:2], self.counts[2:3]
         if _split_log is not None:
             _split_log.append(self)
+
+    def _lists(self):
+        return (ctypes.c_void_p * 8)(*[_p(t) for t in (self.ridx, self.rnx, self.slist, self.soff, self.scnt, self.idxn, self.nxn, self.listn)])
+
+    @staticmethod
+    def pair(idx_a, sparse_max_a, idx_b, sparse_max_b, new_xyz, N):
+        """both scales of an MSG level split by one counter clear and one launch (prcnn_group_compact_pair): two GroupSplits whose
+        counts are the halves of one (6,) tensor"""
+        if idx_a.shape[:2] != idx_b.shape[:2]:
+            raise RuntimeError("GroupSplit.pair: the two index tensors must share (B, M)")
+        counts = torch.empty((6,), dtype=_INT, device=idx_a.device)
+        a = GroupSplit(idx_a, new_xyz, N, sparse_max_a, counts=counts[0:3])
+        b = GroupSplit(idx_b, new_xyz, N, sparse_max_b, counts=counts[3:6])
+        B, M, _ = idx_a.shape
+        _cabi.check(_cabi.lib().prcnn_group_compact_pair(_p(idx_a), a.ns, a.T, _p(idx_b), b.ns, b.T, _p(new_xyz), B, N, M, a._lists(), b._lists(),
+                                                         _p(counts), _stream()), "prcnn_group_compact_pair")
+        return a, b
 
 
 def segmax_scatter(src, sp, dst, col_off):
@@ -1358,6 +1402,21 @@ def scatter_rows(src, rows_list, count, dst, col_off):
     C = src.shape[-1]
     _cabi.check(_cabi.lib().prcnn_scatter_rows(_p(src), src.stride(-2), _p(rows_list), _p(count), rows_list.shape[0], C, _p(dst),
                                                dst.stride(-2), int(col_off), _stream()), "prcnn_scatter_rows")
+
+
+def level_pool(problems, dst):
+    """The pooling launches of one level as one (prcnn_level_pool).  problems: up to four of (src, sp, col_off, "flat") -- what
+    segmax_scatter(src, sp, dst, col_off) does -- or (src, sp, col_off, "dense") -- scatter_rows(src, sp.listn, sp.count_dense, dst,
+    col_off); they must write disjoint cells of dst."""
+    n = len(problems)
+    P, I = ctypes.c_void_p * n, ctypes.c_int * n
+    src, ld, lst, off, cnt, count, cap, C, col = P(), I(), P(), P(), P(), P(), I(), I(), I()
+    for q, (s, sp, c0, kind) in enumerate(problems):
+        flat = kind == "flat"
+        src[q], ld[q], C[q], col[q], cap[q] = _p(s), s.stride(-2), s.shape[-1], int(c0), sp.G
+        lst[q], count[q] = (_p(sp.slist), _p(sp.count_sparse)) if flat else (_p(sp.listn), _p(sp.count_dense))
+        off[q], cnt[q] = (_p(sp.soff), _p(sp.scnt)) if flat else (None, None)
+    _cabi.check(_cabi.lib().prcnn_level_pool(n, src, ld, lst, off, cnt, count, cap, C, col, _p(dst), dst.stride(-2), _stream()), "prcnn_level_pool")
 
 
 # what the wrappers of the passes over raw frames share (the native side of it is csrc/scene_common.h)
