@@ -1130,12 +1130,6 @@ __global__ __launch_bounds__(256, 2) void train_wgrad_lds_kernel(const TrainWgra
         }
 }
 
-template <int POOL, bool MULT>
-static void launch_wgrad_lds(const TrainWgrad& Wg, dim3 grid, hipStream_t s) {
-    if (Wg.pro_scale) hipLaunchKernelGGL((train_wgrad_lds_kernel<POOL, MULT, true>), grid, dim3(256), 0, s, Wg);
-    else hipLaunchKernelGGL((train_wgrad_lds_kernel<POOL, MULT, false>), grid, dim3(256), 0, s, Wg);
-}
-
 // Split-bf16 x 6 twin of train_wgrad_lds_kernel (OPT-IN: prcnn_train_stack_bwd_wsplit; the fp32 kernel above stays the default).
 // Same tile, grid, partial layout, loads and transform; BOTH operands are activations, so both are cut into three bf16 pieces
 // (split3) after the transform, on their way into LDS, and both reach the MFMA with the ROW index in the lane's eight fragment
@@ -1321,12 +1315,6 @@ __global__ __launch_bounds__(256, 2) void train_wgrad_s_kernel(const TrainWgrad 
                 if (ko < W.K) P[(long)no * W.K + ko] = acc[x][z][e];
             }
         }
-}
-
-template <int POOL, bool MULT>
-static void launch_wgrad_s(const TrainWgrad& Wg, dim3 grid, hipStream_t s) {
-    if (Wg.pro_scale) hipLaunchKernelGGL((train_wgrad_s_kernel<POOL, MULT, true>), grid, dim3(256), 0, s, Wg);
-    else hipLaunchKernelGGL((train_wgrad_s_kernel<POOL, MULT, false>), grid, dim3(256), 0, s, Wg);
 }
 
 // out[n, (k + k_unrot) % K] = sum over the partials, in a fixed order (deterministic).  Block = 16 elements x 16 lanes over the partial
@@ -1648,6 +1636,9 @@ __global__ void train_pack_kernel(const float* __restrict__ w, int Nout, int K, 
 }
 
 // ---- host side: one SharedMLP stack per call (include/prcnn_pointops.h, "training-mode SharedMLP") ---------------------------
+// A call checks its arguments, plans every layer (TrainLayerPlan: no HIP call), then per layer fills the parameter struct and
+// launches through train_launch_fwd / _wgrad / _dgrad.  The in-loop checks (gradient outputs, wpack_t, split-image alignment) stay
+// where they fire: after the launches of the layers before.
 static int train_fill_src(const prcnn_train_src_t* S, MlpParams& P) {
     PRCNN_REQUIRE(S, "prcnn_train: null source descriptor");
     PRCNN_REQUIRE(S->rows > 0 && S->K > 0, "prcnn_train: bad shape rows=%ld K=%d", (long)S->rows, S->K);
@@ -1701,18 +1692,47 @@ static WgradPlan wgrad_plan(long rows, int N, int K) {
     return p;
 }
 
+// What the host decided for one layer (as MlpLaunch, mlp_host.h): filled by the train_plan_* functions, which launch nothing, and
+// read by train_launch_fwd / _wgrad / _dgrad, the only places that name a GEMM instance.  A forward call fills the shape and the
+// forward part, a backward call the shape, wgrad and dgrad.
+enum TrainKernel { TK_GENERIC, TK_FAST, TK_SPLIT, TK_DIRECT, TK_LDS };
+struct TrainLayerPlan {
+    int K, N, kin_t;             // input / output channels; the input channels that take a gradient (a grouped layer 0: not its 3 dxyz)
+    bool group0, no_bn;          // layer 0 of a grouped source; Conv (+ bias in `beta`) -> ReLU, no normalisation
+    WgradPlan wg;
+    // forward: TK_SPLIT train_fwd_s_kernel<WNB>, TK_FAST train_fwd_kernel<MODE_PLAIN, WNB, true>, TK_GENERIC train_fwd_kernel<mode, WNB>
+    int fwd, mode;
+    bool fwd_wide;               // WNB = 2
+    dim3 fwd_grid, pack_grid, pack_s_grid;
+    // wgrad: TK_DIRECT train_wgrad_kernel<wg.KQ, wg.NQ, wg.WK, wg.WN>, TK_LDS train_wgrad_lds_kernel / TK_SPLIT train_wgrad_s_kernel
+    // <pool, mult, pro>; pool (dgrad's POOL too): 0 rows, 1 fixed groups, 2 padding-free groups
+    int wgrad, pool;
+    bool mult, pro;
+    dim3 wg_grid;
+    // dgrad: train_dgrad_s_kernel / train_dgrad_kernel<WNB, pool>
+    bool dgrad, dgrad_split, dgrad_wide;
+    int Kin, KB, NB;             // k-blocks over N, n-blocks over Kin
+    dim3 dgrad_grid, pack_t_grid;
+};
+struct TrainStackPlan { int nmax; size_t wg_floats; TrainLayerPlan l[8]; };          // the widest layer, the largest wgrad partial buffer
+
+static void train_plan_shape(TrainStackPlan& S, TrainLayerPlan& p, long rows, int K, int N, bool group0, bool no_bn) {
+    p.K = K; p.N = N; p.kin_t = group0 ? K - 3 : K; p.group0 = group0; p.no_bn = no_bn;
+    p.wg = wgrad_plan(rows, N, K);
+    p.wg_grid = dim3(p.wg.splits, p.wg.tiles_k, p.wg.tiles_n);
+    const size_t f = (size_t)p.wg.splits * p.wg.WR * N * K;
+    S.nmax = N > S.nmax ? N : S.nmax;
+    S.wg_floats = f > S.wg_floats ? f : S.wg_floats;
+}
+static void train_plan_shapes(TrainStackPlan& S, const prcnn_train_src_t* src, const prcnn_train_layer_t* L, int nl) {
+    S.nmax = 0; S.wg_floats = 0;
+    for (int l = 0; l < nl; l++)
+        train_plan_shape(S, S.l[l], src->rows, l == 0 ? src->K : L[l - 1].Nout, L[l].Nout, l == 0 && src->mode == MODE_GROUP, L[l].gamma == nullptr);
+}
+
 struct TrainWork { float* part; double* chunk; float* slab_w; float* wpart; float* G[2]; };
-static size_t train_work_layout(int64_t rows, int nl, const prcnn_train_layer_t* L, int K0, bool backward, char* base, TrainWork* w) {
-    int nmax = 0;
-    size_t wg = 0;
-    for (int l = 0; l < nl; l++) {
-        nmax = L[l].Nout > nmax ? L[l].Nout : nmax;
-        const int K = l == 0 ? K0 : L[l - 1].Nout;
-        const WgradPlan p = wgrad_plan(rows, L[l].Nout, K);
-        const size_t f = (size_t)p.splits * p.WR * L[l].Nout * K;
-        wg = f > wg ? f : wg;
-    }
-    const int ldp = (int)up_sz((size_t)nmax, 4);
+static size_t train_work_layout(int64_t rows, const TrainStackPlan& S, bool backward, char* base, TrainWork* w) {
+    const int nmax = S.nmax, ldp = (int)up_sz((size_t)nmax, 4);
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += up_sz(bytes, 256); return base ? base + o : (char*)nullptr; };
     char* part = take((size_t)((rows + 63) / 64) * 2 * ldp * sizeof(float));
@@ -1720,12 +1740,18 @@ static size_t train_work_layout(int64_t rows, int nl, const prcnn_train_layer_t*
     char* slabw = take((size_t)((rows + 63) / 64) * sizeof(float));
     char *wpart = nullptr, *g0 = nullptr, *g1 = nullptr;
     if (backward) {
-        wpart = take(wg * sizeof(float));
+        wpart = take(S.wg_floats * sizeof(float));
         g0 = take((size_t)rows * ldp * sizeof(float));
         g1 = take((size_t)rows * ldp * sizeof(float));
     }
     if (w) { w->part = (float*)part; w->chunk = (double*)chunk; w->slab_w = (float*)slabw; w->wpart = (float*)wpart; w->G[0] = (float*)g0; w->G[1] = (float*)g1; }
     return off;
+}
+// what forward and backward state identically: lays the workspace out
+static int train_take_work(const char* who, int64_t rows, const TrainStackPlan& S, bool backward, void* work, size_t work_bytes, TrainWork& W) {
+    const size_t need = train_work_layout(rows, S, backward, (char*)work, &W);
+    PRCNN_REQUIRE(work && work_bytes >= need && ((uintptr_t)work & 255) == 0, "%s: workspace too small or misaligned (%zu < %zu)", who, work_bytes, need);
+    return PRCNN_OK;
 }
 
 // Which layers the split-bf16 kernels take (decided here, per layer; everything else keeps its fp32 kernel):
@@ -1750,7 +1776,48 @@ static int train_check_layers(const prcnn_train_layer_t* L, int nl) {
 
 PRCNN_API size_t prcnn_train_stack_work_bytes(int64_t rows, const prcnn_train_layer_t* layers, int nl, int K0, int backward) {
     if (!layers || nl <= 0 || rows <= 0) return 0;
-    return train_work_layout(rows, nl, layers, K0, backward != 0, nullptr, nullptr);
+    TrainStackPlan S;                                      // (sizes only, so any number of layers: through one entry)
+    S.nmax = 0; S.wg_floats = 0;
+    for (int l = 0; l < nl; l++) train_plan_shape(S, S.l[0], rows, l == 0 ? K0 : layers[l - 1].Nout, layers[l].Nout, false, false);
+    return train_work_layout(rows, S, backward != 0, nullptr, nullptr);
+}
+
+// The rows a layer reads.  Layer l > 0: the raw output of the layer before, its BatchNorm + ReLU as a prologue (cst rows 0, 1)
+struct TrainInput { const float* a; int lda; const float *pro_scale, *pro_shift; };
+static TrainInput train_input(const prcnn_train_layer_t* L, int l) { return {L[l - 1].y, L[l - 1].Nout, L[l - 1].cst, L[l - 1].cst + L[l - 1].ld_c}; }
+
+// forward and dgrad tile alike: MLP_BM rows x two blocks of 32 output columns, or four ("wide") where that still fills the chip
+static dim3 train_tile_grid(long rows, int NB, bool& wide) {
+    const long tiles = prcnn_divup(rows, MLP_BM);
+    wide = NB >= 4 && tiles * prcnn_divup(NB, 4) >= 192;
+    return dim3((unsigned)tiles, prcnn_divup(NB, wide ? 4 : 2));
+}
+
+// first: layer 0, whose prologue (if any) is the caller's; pack_t: the transposed weights are packed too; ws: the split image offered
+static void train_plan_fwd(TrainLayerPlan& p, long rows, int mode, const TrainInput& in, bool vec_a, bool first, bool pack_t, const void* ws) {
+    const int K = p.K, N = p.N, NB = prcnn_divup(N, 32);
+    p.mode = mode;
+    p.pack_grid = dim3(prcnn_divup((long)NB * prcnn_divup(K, 8) * 256 + (pack_t ? (long)prcnn_divup(p.kin_t, 32) * prcnn_divup(N, 8) * 256 : 0), 256));
+    p.pack_s_grid = dim3(prcnn_divup((long)NB * (K / 16) * 64, 256));
+    p.fwd_grid = train_tile_grid(rows, NB, p.fwd_wide);
+    const bool fast = mode == MODE_PLAIN && vec_a && K % 4 == 0 && K >= 4 && in.lda % 4 == 0 && aligned16(in.a) && (!in.pro_scale || !first) &&
+                      !sw_present(SW_TRAIN_FWD_GENERIC);
+    p.fwd = (ws && train_fwd_split_ok(mode, K, in.a, in.lda, in.pro_scale, in.pro_shift)) ? TK_SPLIT : fast ? TK_FAST : TK_GENERIC;
+}
+
+// X(family, mode, kernel<.. W ..>): every forward instance, wide (W = 2) and narrow (W = 1)
+#define TRAIN_FWD_TABLE(X)                                                                                                    \
+    X(TK_SPLIT, MODE_PLAIN, train_fwd_s_kernel<W>) X(TK_FAST, MODE_PLAIN, train_fwd_kernel<MODE_PLAIN, W, true>)              \
+    X(TK_GENERIC, MODE_PLAIN, train_fwd_kernel<MODE_PLAIN, W>) X(TK_GENERIC, MODE_GROUP, train_fwd_kernel<MODE_GROUP, W>)    \
+    X(TK_GENERIC, MODE_INTERP, train_fwd_kernel<MODE_INTERP, W>)
+static int train_launch_fwd(const TrainLayerPlan& p, const TrainFwd& T, hipStream_t s) {
+#define GO(WNB, ...) { constexpr int W = WNB; hipLaunchKernelGGL((__VA_ARGS__), p.fwd_grid, dim3(MLP_THREADS), 0, s, T); }
+#define X(F, M, ...) if (p.fwd == F && p.mode == M && p.fwd_wide) GO(2, __VA_ARGS__) else if (p.fwd == F && p.mode == M) GO(1, __VA_ARGS__) else
+    TRAIN_FWD_TABLE(X)
+        return prcnn_fail(PRCNN_EINVAL, "prcnn_train_stack_fwd: no forward instance for family %d mode %d", p.fwd, p.mode);
+#undef X
+#undef GO
+    return PRCNN_OK;
 }
 
 // wsplit: NULL (prcnn_train_stack_fwd: every layer on the fp32 pipe, the launches of every release so far) or nl split-image
@@ -1776,64 +1843,41 @@ static int train_stack_fwd_run(const prcnn_train_src_t* src, const prcnn_train_l
     PRCNN_REQUIRE(!a_dump || (src->mode != MODE_PLAIN && ld_dump % 4 == 0 && ld_dump >= src->K && aligned16(a_dump)),
                   "prcnn_train_stack_fwd: a_dump needs a gathered source, 16-byte alignment and ld_dump %% 4 == 0, >= K");
     PRCNN_REQUIRE((src->pro_scale == nullptr) == (src->pro_shift == nullptr), "prcnn_train_stack_fwd: pro_scale and pro_shift go together");
+    const bool plain0 = src->mode == MODE_PLAIN;
+    const TrainInput in0 = {T0.P.in, T0.P.ld_in, plain0 ? src->pro_scale : nullptr, plain0 ? src->pro_shift : nullptr};
+    TrainStackPlan S;
+    train_plan_shapes(S, src, L, nl);
+    for (int l = 0; l < nl; l++)
+        train_plan_fwd(S.l[l], rows, l ? MODE_PLAIN : src->mode, l ? train_input(L, l) : in0, l ? true : T0.P.vec_a != 0, l == 0,
+                       L[l].wpack_t && S.l[l].kin_t > 0, wsplit ? wsplit[l] : nullptr);
     TrainWork W;
-    const size_t need = train_work_layout(rows, nl, L, src->K, false, (char*)work, &W);
-    PRCNN_REQUIRE(work && work_bytes >= need && ((uintptr_t)work & 255) == 0, "prcnn_train_stack_fwd: workspace too small or misaligned (%zu < %zu)", work_bytes, need);
+    rc = train_take_work("prcnn_train_stack_fwd", rows, S, false, work, work_bytes, W);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     for (int l = 0; l < nl; l++) {
-        const int K = l == 0 ? src->K : L[l - 1].Nout, N = L[l].Nout;
-        const bool group0 = l == 0 && src->mode == MODE_GROUP;
-        const int kin_t = group0 ? K - 3 : K;
-        float* wt = (L[l].wpack_t && kin_t > 0) ? L[l].wpack_t : nullptr;
-        const long tot = (long)prcnn_divup(N, 32) * prcnn_divup(K, 8) * 256 + (wt ? (long)prcnn_divup(kin_t, 32) * prcnn_divup(N, 8) * 256 : 0);
-        hipLaunchKernelGGL(train_pack_kernel, dim3(prcnn_divup(tot, 256)), dim3(256), 0, s, L[l].W, N, K, group0 ? 3 : 0, L[l].wpack, wt, kin_t,
-                           group0 ? 3 : 0);
+        const TrainLayerPlan& p = S.l[l];
+        const int K = p.K, N = p.N, rot = p.group0 ? 3 : 0;
+        hipLaunchKernelGGL(train_pack_kernel, p.pack_grid, dim3(256), 0, s, L[l].W, N, K, rot, L[l].wpack, (L[l].wpack_t && p.kin_t > 0) ? L[l].wpack_t : nullptr,
+                           p.kin_t, rot);
+        const TrainInput in = l ? train_input(L, l) : in0;
         TrainFwd T = {};
-        if (l == 0) {
-            T = T0;
-            T.pro_scale = src->mode == MODE_PLAIN ? src->pro_scale : nullptr;
-            T.pro_shift = src->mode == MODE_PLAIN ? src->pro_shift : nullptr;
-            T.a_dump = a_dump; T.ld_dump = ld_dump;
-            if (flat) { T.P.rows_dev = src->rows_dev; T.P.rows_unit = 1; }
-        } else {
-            T.P.rows = rows; T.P.K = K; T.P.in = L[l - 1].y; T.P.ld_in = L[l - 1].Nout; T.P.vec_a = 1;
-            T.pro_scale = L[l - 1].cst; T.pro_shift = L[l - 1].cst + L[l - 1].ld_c;
-            if (flat) { T.P.rows_dev = src->rows_dev; T.P.rows_unit = 1; }
-        }
-        if (flat) { T.mult = src->mult; T.slab_w = W.slab_w; }
+        if (l == 0) { T = T0; T.a_dump = a_dump; T.ld_dump = ld_dump; }
         MlpParams& P = T.P;
+        P.rows = rows; P.K = K; P.in = in.a; P.ld_in = in.lda; P.vec_a = l ? 1 : T0.P.vec_a;
+        T.pro_scale = in.pro_scale; T.pro_shift = in.pro_shift;
+        if (flat) { P.rows_dev = src->rows_dev; P.rows_unit = 1; T.mult = src->mult; T.slab_w = W.slab_w; }
         P.wpack = L[l].wpack; P.Nout = N; P.out = L[l].y; P.ld_out = N; P.col_off = 0;
         P.KB = (K + 7) / 8; P.NB = (N + 31) / 32;
-        const bool no_bn = L[l].gamma == nullptr;              // Conv (+ bias in `beta`) -> ReLU, no normalisation
-        T.part = no_bn ? nullptr : W.part; T.ld_part = N;
-        const long tiles = prcnn_divup(rows, MLP_BM);
-        const bool wide = P.NB >= 4 && tiles * prcnn_divup(P.NB, 4) >= 192;
-        const dim3 grid((unsigned)tiles, prcnn_divup(P.NB, wide ? 4 : 2));
-        const int mode = l == 0 ? src->mode : MODE_PLAIN;
-#define TRAIN_FWD(M)                                                                                            \
-    do {                                                                                                        \
-        if (wide) hipLaunchKernelGGL((train_fwd_kernel<M, 2>), grid, dim3(MLP_THREADS), 0, s, T);               \
-        else hipLaunchKernelGGL((train_fwd_kernel<M, 1>), grid, dim3(MLP_THREADS), 0, s, T);                    \
-    } while (0)
-        const bool fastp = mode == MODE_PLAIN && P.vec_a && K % 4 == 0 && K >= 4 && P.ld_in % 4 == 0 && aligned16(P.in) &&
-                           (!T.pro_scale || l > 0) && !sw_present(SW_TRAIN_FWD_GENERIC);
-        void* ws = wsplit ? wsplit[l] : nullptr;
-        if (ws && train_fwd_split_ok(mode, K, P.in, P.ld_in, T.pro_scale, T.pro_shift)) {
+        T.part = p.no_bn ? nullptr : W.part; T.ld_part = N;
+        if (p.fwd == TK_SPLIT) {
+            void* ws = wsplit[l];
             PRCNN_REQUIRE(aligned16(ws), "prcnn_train_stack_fwd_split: layer %d: split image not 16-byte aligned", l);
-            const int KS = K / 16;
-            hipLaunchKernelGGL(pack_weight_split_kernel, dim3(prcnn_divup((long)P.NB * KS * 64, 256)), dim3(256), 0, s, L[l].W, N, K, KS, P.NB, 0,
-                               reinterpret_cast<uint4*>(ws));
+            hipLaunchKernelGGL(pack_weight_split_kernel, p.pack_s_grid, dim3(256), 0, s, L[l].W, N, K, K / 16, P.NB, 0, reinterpret_cast<uint4*>(ws));
             P.wsplit = ws;
-            if (wide) hipLaunchKernelGGL((train_fwd_s_kernel<2>), grid, dim3(MLP_THREADS), 0, s, T);
-            else hipLaunchKernelGGL((train_fwd_s_kernel<1>), grid, dim3(MLP_THREADS), 0, s, T);
-        } else if (fastp) {
-            if (wide) hipLaunchKernelGGL((train_fwd_kernel<MODE_PLAIN, 2, true>), grid, dim3(MLP_THREADS), 0, s, T);
-            else hipLaunchKernelGGL((train_fwd_kernel<MODE_PLAIN, 1, true>), grid, dim3(MLP_THREADS), 0, s, T);
-        } else if (mode == MODE_PLAIN) TRAIN_FWD(MODE_PLAIN);
-        else if (mode == MODE_GROUP) TRAIN_FWD(MODE_GROUP);
-        else TRAIN_FWD(MODE_INTERP);
-#undef TRAIN_FWD
-        if (no_bn) {
+        }
+        rc = train_launch_fwd(p, T, s);
+        if (rc) return rc;
+        if (p.no_bn) {
             hipLaunchKernelGGL(nobn_cst_kernel, dim3(prcnn_divup(N, 64)), dim3(64), 0, s, L[l].beta, N, L[l].cst, L[l].ld_c);
         } else {
             hipLaunchKernelGGL(bn_chunk_kernel, dim3(prcnn_divup(N, 64), BN_CHUNKS), dim3(256), 0, s, W.part, N, rows, flat ? src->rows_dev : nullptr,
@@ -1863,9 +1907,54 @@ PRCNN_API int prcnn_train_stack_fwd_split(const prcnn_train_src_t* src, const pr
     return train_stack_fwd_run(src, L, nl, pool_ns, a_dump, ld_dump, out, ld_out, col_off, arg, wsplit, work, work_bytes, stream);
 }
 
-template <int KQ, int NQ, int WK, int WN>
-static void launch_wgrad(const TrainWgrad& W, const WgradPlan& p, hipStream_t s) {
-    hipLaunchKernelGGL((train_wgrad_kernel<KQ, NQ, WK, WN>), dim3(p.splits, p.tiles_k, p.tiles_n), dim3(256), 0, s, W);
+// pool_ns: the layer's (TrainBwd::pool_ns); a / lda: its input rows; split: prcnn_train_stack_bwd_wsplit.  The 128 x 128 tile is
+// staged through LDS where the rows take 16-byte loads, and that kernel alone has a split-bf16 twin
+static void train_plan_wgrad(TrainLayerPlan& p, int pool_ns, bool flat, const float* a, int lda, bool pro, bool split) {
+    p.pool = pool_ns == 0 ? 0 : pool_ns > 0 ? 1 : 2;
+    p.mult = p.pool == 0 ? flat : p.pool == 2;
+    p.pro = pro;
+    const bool tile128 = p.wg.KQ == 2 && p.wg.NQ == 2 && p.wg.WK == 2 && p.wg.WN == 2;
+    p.wgrad = (tile128 && lda % 4 == 0 && aligned16(a) && !sw_present(SW_WGRAD_DIRECT)) ? (split ? TK_SPLIT : TK_LDS) : TK_DIRECT;
+}
+// Kin: the input channels that take the gradient; wst: the split image of W^T offered
+static void train_plan_dgrad(TrainLayerPlan& p, long rows, int Kin, const void* wst) {
+    p.dgrad = true;
+    p.Kin = Kin; p.KB = (p.N + 7) / 8; p.NB = (Kin + 31) / 32;
+    p.dgrad_grid = train_tile_grid(rows, p.NB, p.dgrad_wide);
+    p.dgrad_split = wst && train_dgrad_split_ok(p.N, rows);
+    p.pack_t_grid = dim3(prcnn_divup((long)p.NB * (p.N / 16) * 64, 256));
+}
+
+// X(KQ, NQ, WK, WN): the tilings wgrad_plan can choose
+#define TRAIN_WGRAD_TILINGS(X) X(1, 1, 1, 1) X(1, 2, 1, 1) X(1, 2, 1, 2) X(2, 1, 1, 1) X(2, 2, 1, 1) X(2, 2, 1, 2) X(2, 1, 2, 1) X(2, 2, 2, 1) X(2, 2, 2, 2)
+// X(POOL, MULT): the forms of the LDS-staged kernels -- rows (plain, padding-free), fixed groups, padding-free groups; each with PRO off / on
+#define TRAIN_WGRAD_FORMS(X) X(0, false) X(0, true) X(1, false) X(2, true)
+static int train_launch_wgrad(const TrainLayerPlan& p, const TrainWgrad& W, hipStream_t s) {
+#define GO(...) hipLaunchKernelGGL((__VA_ARGS__), p.wg_grid, dim3(256), 0, s, W)
+#define X(A, B, C, D) if (p.wgrad == TK_DIRECT && p.wg.KQ == A && p.wg.NQ == B && p.wg.WK == C && p.wg.WN == D) GO(train_wgrad_kernel<A, B, C, D>); else
+    TRAIN_WGRAD_TILINGS(X)
+#undef X
+#define FORM(F, kernel, POOL, MULT, PRO) if (p.wgrad == F && p.pool == POOL && p.mult == MULT && p.pro == PRO) GO(kernel<POOL, MULT, PRO>); else
+#define X(POOL, MULT) FORM(TK_LDS, train_wgrad_lds_kernel, POOL, MULT, true) FORM(TK_LDS, train_wgrad_lds_kernel, POOL, MULT, false) \
+                      FORM(TK_SPLIT, train_wgrad_s_kernel, POOL, MULT, true) FORM(TK_SPLIT, train_wgrad_s_kernel, POOL, MULT, false)
+    TRAIN_WGRAD_FORMS(X)
+        return prcnn_fail(PRCNN_EINVAL, "prcnn_train_stack_bwd: no wgrad instance for family %d <%d,%d,%d,%d> form <%d,%d,%d>", p.wgrad, p.wg.KQ, p.wg.NQ,
+                          p.wg.WK, p.wg.WN, p.pool, (int)p.mult, (int)p.pro);
+#undef X
+#undef FORM
+#undef GO
+    return PRCNN_OK;
+}
+static int train_launch_dgrad(const TrainLayerPlan& p, const TrainDgradS& DS, hipStream_t s) {
+#define GO(arg, ...) hipLaunchKernelGGL((__VA_ARGS__), p.dgrad_grid, dim3(MLP_THREADS), 0, s, arg)
+#define FORM(SPLIT, arg, kernel, POOL) if (p.dgrad_split == SPLIT && p.pool == POOL && p.dgrad_wide) GO(arg, kernel<2, POOL>); else \
+                                       if (p.dgrad_split == SPLIT && p.pool == POOL) GO(arg, kernel<1, POOL>); else
+    FORM(true, DS, train_dgrad_s_kernel, 0) FORM(true, DS, train_dgrad_s_kernel, 1) FORM(true, DS, train_dgrad_s_kernel, 2)
+    FORM(false, DS.D, train_dgrad_kernel, 0) FORM(false, DS.D, train_dgrad_kernel, 1) FORM(false, DS.D, train_dgrad_kernel, 2)
+        return prcnn_fail(PRCNN_EINVAL, "prcnn_train_stack_bwd: no dgrad instance for split %d pool %d", (int)p.dgrad_split, p.pool);
+#undef FORM
+#undef GO
+    return PRCNN_OK;
 }
 
 // wsplit_t: NULL (prcnn_train_stack_bwd) or nl pointers to split images of W^T (prcnn_train_stack_bwd_split); a layer whose dgrad is
@@ -1884,20 +1973,28 @@ static int train_stack_bwd_run(const prcnn_train_src_t* src, const prcnn_train_l
     const int ns = flat ? -1 : (pool_ns > 1 ? pool_ns : 0);
     const long norm_rows = flat ? src->norm_rows : rows;
     PRCNN_REQUIRE(rows > 0 && ld_gout % 4 == 0 && aligned16(gout) && (ns <= 0 || (arg && rows % ns == 0)), "prcnn_train_stack_bwd: bad gradient / pooling arguments");
-    const float* a0 = src->mode == MODE_PLAIN ? src->in : a_dump;
-    const int lda0 = src->mode == MODE_PLAIN ? src->ld_in : ld_dump;
-    PRCNN_REQUIRE(a0 && lda0 % 2 == 0 && ((uintptr_t)a0 & 7) == 0 && lda0 >= src->K,
+    const TrainInput in0 = {src->mode == MODE_PLAIN ? src->in : a_dump, src->mode == MODE_PLAIN ? src->ld_in : ld_dump, nullptr, nullptr};
+    PRCNN_REQUIRE(in0.a && in0.lda % 2 == 0 && ((uintptr_t)in0.a & 7) == 0 && in0.lda >= src->K,
                   "prcnn_train_stack_bwd: the first layer's input rows (plain `in` or a_dump) need an even row stride and 8-byte alignment");
     const int kin0 = src->mode == MODE_GROUP ? src->K - 3 : src->K;
     PRCNN_REQUIRE(!gin || (kin0 > 0 && ld_gin >= kin0 && L[0].wpack_t), "prcnn_train_stack_bwd: gin needs ld_gin >= %d and layer 0's wpack_t", kin0);
+    TrainStackPlan S;
+    train_plan_shapes(S, src, L, nl);
+    for (int l = 0; l < nl; l++) {
+        const TrainInput in = l ? train_input(L, l) : in0;
+        train_plan_wgrad(S.l[l], l == nl - 1 ? ns : 0, flat, in.a, in.lda, in.pro_scale != nullptr, wgrad_split);
+        S.l[l].dgrad = false;
+        if (l > 0 || gin) train_plan_dgrad(S.l[l], rows, l ? S.l[l].K : kin0, wsplit_t ? wsplit_t[l] : nullptr);
+    }
     TrainWork W;
-    const size_t need = train_work_layout(rows, nl, L, src->K, true, (char*)work, &W);
-    PRCNN_REQUIRE(work && work_bytes >= need && ((uintptr_t)work & 255) == 0, "prcnn_train_stack_bwd: workspace too small or misaligned (%zu < %zu)", work_bytes, need);
+    rc = train_take_work("prcnn_train_stack_bwd", rows, S, true, work, work_bytes, W);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     const float* G = gout;
     int ldG = ld_gout;
     for (int l = nl - 1; l >= 0; l--) {
-        const int N = L[l].Nout, K = l == 0 ? src->K : L[l - 1].Nout;
+        const TrainLayerPlan& p = S.l[l];
+        const int N = p.N, K = p.K;
         PRCNN_REQUIRE(L[l].dW && (L[l].gamma == nullptr || L[l].dgamma) && (L[l].beta == nullptr || L[l].dbeta),
                       "prcnn_train_stack_bwd: layer %d: null gradient outputs", l);
         TrainBwd T;
@@ -1912,71 +2009,35 @@ static int train_stack_bwd_run(const prcnn_train_src_t* src, const prcnn_train_l
         hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3((unsigned)tiles, prcnn_divup(N, 64)), dim3(256), 0, s, T, W.part, ldp);
         hipLaunchKernelGGL(bn_bwd_chunk_kernel, dim3(prcnn_divup(N, 64), BN_CHUNKS), dim3(256), 0, s, W.part, ldp, tiles, T.rows_dev, N, W.chunk);
         hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(prcnn_divup(N, 64)), dim3(64), 0, s, W.chunk, norm_rows, N, L[l].cst, L[l].ld_c, L[l].dgamma,
-                           L[l].dbeta, L[l].gamma == nullptr ? 1 : 0);
+                           L[l].dbeta, p.no_bn ? 1 : 0);
         // wgrad
+        const TrainInput in = l ? train_input(L, l) : in0;
         TrainWgrad Wg = {};
         Wg.B = T; Wg.K = K; Wg.part = W.wpart;
-        if (l > 0) { Wg.a = L[l - 1].y; Wg.lda = L[l - 1].Nout; Wg.pro_scale = L[l - 1].cst; Wg.pro_shift = L[l - 1].cst + L[l - 1].ld_c; }
-        else { Wg.a = a0; Wg.lda = lda0; }
-        const WgradPlan p = wgrad_plan(rows, N, K);
-        Wg.rows_per_split = p.rows_per_split;
-        if (p.KQ == 1 && p.NQ == 1) launch_wgrad<1, 1, 1, 1>(Wg, p, s);
-        else if (p.KQ == 1 && p.NQ == 2 && p.WN == 1) launch_wgrad<1, 2, 1, 1>(Wg, p, s);
-        else if (p.KQ == 1 && p.NQ == 2) launch_wgrad<1, 2, 1, 2>(Wg, p, s);
-        else if (p.KQ == 2 && p.WK == 1 && p.NQ == 1) launch_wgrad<2, 1, 1, 1>(Wg, p, s);
-        else if (p.KQ == 2 && p.WK == 1 && p.WN == 1) launch_wgrad<2, 2, 1, 1>(Wg, p, s);
-        else if (p.KQ == 2 && p.WK == 1) launch_wgrad<2, 2, 1, 2>(Wg, p, s);
-        else if (p.NQ == 1) launch_wgrad<2, 1, 2, 1>(Wg, p, s);
-        else if (p.WN == 1) launch_wgrad<2, 2, 2, 1>(Wg, p, s);
-        else if (Wg.lda % 4 == 0 && aligned16(Wg.a) && !sw_present(SW_WGRAD_DIRECT)) {
-            const dim3 wg(p.splits, p.tiles_k, p.tiles_n);
-            if (wgrad_split) {
-                if (Wg.B.pool_ns == 0) { if (Wg.B.mult) launch_wgrad_s<0, true>(Wg, wg, s); else launch_wgrad_s<0, false>(Wg, wg, s); }
-                else if (Wg.B.pool_ns > 0) launch_wgrad_s<1, false>(Wg, wg, s);
-                else launch_wgrad_s<2, true>(Wg, wg, s);
-            } else if (Wg.B.pool_ns == 0) { if (Wg.B.mult) launch_wgrad_lds<0, true>(Wg, wg, s); else launch_wgrad_lds<0, false>(Wg, wg, s); }
-            else if (Wg.B.pool_ns > 0) launch_wgrad_lds<1, false>(Wg, wg, s);
-            else launch_wgrad_lds<2, true>(Wg, wg, s);
-        } else launch_wgrad<2, 2, 2, 2>(Wg, p, s);
+        Wg.a = in.a; Wg.lda = in.lda; Wg.pro_scale = in.pro_scale; Wg.pro_shift = in.pro_shift;
+        Wg.rows_per_split = p.wg.rows_per_split;
+        rc = train_launch_wgrad(p, Wg, s);
+        if (rc) return rc;
         const long count = (long)N * K;
-        hipLaunchKernelGGL(train_wgrad_reduce_kernel, dim3(prcnn_divup(count, WRED_E)), dim3(256), 0, s, W.wpart, p.splits * p.WR, count, K,
-                           (l == 0 && src->mode == MODE_GROUP && K > 3) ? 3 : 0, L[l].dW);
+        hipLaunchKernelGGL(train_wgrad_reduce_kernel, dim3(prcnn_divup(count, WRED_E)), dim3(256), 0, s, W.wpart, p.wg.splits * p.wg.WR, count, K,
+                           (p.group0 && K > 3) ? 3 : 0, L[l].dW);
         // dgrad
-        if (l == 0 && !gin) break;
+        if (!p.dgrad) break;
         PRCNN_REQUIRE(L[l].wpack_t, "prcnn_train_stack_bwd: layer %d needs wpack_t (its input takes a gradient)", l);
-        TrainDgrad D = {};
+        TrainDgradS DS = {};
+        TrainDgrad& D = DS.D;
         D.B = T; D.wpack = L[l].wpack_t;
-        D.Kin = l == 0 ? kin0 : K;
-        D.KB = (N + 7) / 8; D.NB = (D.Kin + 31) / 32;
+        D.Kin = p.Kin; D.KB = p.KB; D.NB = p.NB;
         D.out = l == 0 ? gin : W.G[l & 1]; D.ld_out = l == 0 ? ld_gin : K;
-        const long dt = prcnn_divup(rows, MLP_BM);
-        const bool wide = D.NB >= 4 && dt * prcnn_divup(D.NB, 4) >= 192;
-        const dim3 grid((unsigned)dt, prcnn_divup(D.NB, wide ? 4 : 2));
-#define TRAIN_DGRAD(POOL)                                                                                        \
-    do {                                                                                                         \
-        if (wide) hipLaunchKernelGGL((train_dgrad_kernel<2, POOL>), grid, dim3(MLP_THREADS), 0, s, D);           \
-        else hipLaunchKernelGGL((train_dgrad_kernel<1, POOL>), grid, dim3(MLP_THREADS), 0, s, D);                \
-    } while (0)
-#define TRAIN_DGRAD_S(POOL)                                                                                      \
-    do {                                                                                                         \
-        if (wide) hipLaunchKernelGGL((train_dgrad_s_kernel<2, POOL>), grid, dim3(MLP_THREADS), 0, s, DS);        \
-        else hipLaunchKernelGGL((train_dgrad_s_kernel<1, POOL>), grid, dim3(MLP_THREADS), 0, s, DS);             \
-    } while (0)
-        void* wst = wsplit_t ? wsplit_t[l] : nullptr;
-        if (wst && train_dgrad_split_ok(N, rows)) {
+        if (p.dgrad_split) {
+            void* wst = wsplit_t[l];
             PRCNN_REQUIRE(aligned16(wst), "prcnn_train_stack_bwd_split: layer %d: split image not 16-byte aligned", l);
-            const int KS = N / 16;
-            hipLaunchKernelGGL(train_pack_split_t_kernel, dim3(prcnn_divup((long)D.NB * KS * 64, 256)), dim3(256), 0, s, L[l].W, N, K, D.Kin,
-                               K - D.Kin, KS, D.NB, reinterpret_cast<uint4*>(wst));
-            TrainDgradS DS = {D, reinterpret_cast<const uint4*>(wst)};
-            if (T.pool_ns == 0) TRAIN_DGRAD_S(0);
-            else if (T.pool_ns > 0) TRAIN_DGRAD_S(1);
-            else TRAIN_DGRAD_S(2);
-        } else if (T.pool_ns == 0) TRAIN_DGRAD(0);
-        else if (T.pool_ns > 0) TRAIN_DGRAD(1);
-        else TRAIN_DGRAD(2);
-#undef TRAIN_DGRAD_S
-#undef TRAIN_DGRAD
+            hipLaunchKernelGGL(train_pack_split_t_kernel, p.pack_t_grid, dim3(256), 0, s, L[l].W, N, K, D.Kin, K - D.Kin, N / 16, D.NB,
+                               reinterpret_cast<uint4*>(wst));
+            DS.wsplit = reinterpret_cast<const uint4*>(wst);
+        }
+        rc = train_launch_dgrad(p, DS, s);
+        if (rc) return rc;
         G = D.out; ldG = D.ld_out;
     }
     PRCNN_LAUNCH_CHECK("prcnn_train_stack_bwd");

@@ -45,10 +45,13 @@ int prcnn_fail(int code, const char* fmt, ...) {
 
 // names a kernel by its instantiation: the mangled name of KName<&kernel<args>> spells the template arguments out
 template <auto K> struct KName {
-    static std::string get() {
-        std::string s = typeid(KName<K>).name();
-        for (size_t i; (i = s.find("__device_stub__")) != std::string::npos;) s.erase(i, strlen("__device_stub__"));
-        return s;
+    static const std::string& get() {
+        static const std::string name = [] {
+            std::string s = typeid(KName<K>).name();
+            for (size_t i; (i = s.find("__device_stub__")) != std::string::npos;) s.erase(i, strlen("__device_stub__"));
+            return s;
+        }();
+        return name;
     }
 };
 struct MlpParams;

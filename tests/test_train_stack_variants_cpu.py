@@ -6,7 +6,16 @@ prcnn_train_stack_fwd / _bwd over rows 1 .. 2 M, widths 3 .. 512, all sources, p
 gradient wanted / not and both native switches: the universe of reachable instantiations.  `--case` records one case of the table.
 The union over the table must EQUAL the universe, so a variant added to the dispatch without a case fails here, before any GPU
 time is spent; the direct wgrad kernel's run-time forms (unpooled / pooled / padding-free pooled x operand prologue on / off)
-must all be there too.  Built and run once plain and once with -fsanitize=address,undefined, as tests/test_mlp_host_cpu.py does."""
+must all be there too.  Built and run once plain and once with -fsanitize=address,undefined, as tests/test_mlp_host_cpu.py does.
+
+`--digest` is the full record: the five stack exports and prcnn_train_stack_work_bytes over the union of the three training
+recorders' sweeps, the four settings of PRCNN_TRAIN_FWD_GENERIC x PRCNN_WGRAD_DIRECT, operand variants that flip every
+alignment-dependent choice and an invalid call per check of the host code; per call the return code, the message, and per launch
+the instantiation, grid, block, dynamic LDS and every argument (parameter structs field by field).  Its per-(switch setting, export,
+source) digests must equal tests/golden/train_launch_digests.txt, recorded from the sources before the host code was given a
+per-layer plan and one launch table each for forward, wgrad and dgrad: this recorder built with -I on a checkout of that commit's
+pointrcnn_amd/csrc (the parameter structs and the exports are the same), `train_launch_record --digest > the golden file`.  A
+change that means to alter a launch re-records the file the same way and says so; `--digest-dump` prints the records to compare."""
 import os
 import subprocess
 
@@ -57,6 +66,25 @@ def test_the_case_table_reaches_every_variant(tmp_path, sanitize):
     # nsample 256 does not fit the uint8 pooling slot: refused before anything is launched
     rc, names, err = record(["--case", "group", "1024", "256", "1", "1", "0", "0", "3", "4"])
     assert rc == 1 and not names and "bad pooling arguments" in err, (rc, names, err)
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc absent")
+@pytest.mark.parametrize("sanitize", [False, True])
+def test_every_call_launches_what_it_launched(tmp_path, sanitize):
+    exe = str(tmp_path / "train_launch_record")
+    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
+    subprocess.run([HIPCC, "-x", "hip", "--cuda-host-only", "--offload-arch=gfx950", "-std=c++17", "-O1", "-Wno-unused-function", "-Wno-unused-value",
+                    "-Wl,--unresolved-symbols=ignore-all"] + flags + ["-I", CSRC, os.path.join(ROOT, "tests", "train_launch_record.cpp"), "-o", exe],
+                   check=True)
+    run = subprocess.run([exe, "--digest"], capture_output=True, text=True)
+    assert run.returncode == 0, run.stderr[-2000:]
+    got = run.stdout.splitlines()
+    with open(os.path.join(ROOT, "tests", "golden", "train_launch_digests.txt")) as f:
+        want = f.read().splitlines()
+    assert [g.rsplit(" ", 2)[0] for g in got[:-1]] == [w.rsplit(" ", 2)[0] for w in want[:-1]]          # the same groups, in order
+    changed = [g.rsplit(" ", 2)[0] for g, w in zip(got, want) if g != w]
+    assert not changed, "calls that no longer launch (or refuse) what they did: %s" % changed
+    assert got[-1] == want[-1] and len(got) == len(want)
 
 
 def test_seeded_cases_stay_out_of_the_decision_bands():
