@@ -65,6 +65,8 @@ int prcnn_abi_version(void);   /* 12: + prcnn_switches_reload, prcnn_switch_get 
                                  * parameter update: clip, decay and Adam over all tensors in two launches);
                                  * still 12 (additive): + prcnn_optim_step_adam, prcnn_optim_step_sgd (TRAIN.OPTIMIZER adam and sgd on the
                                  * same tables and launches);
+                                 * still 12 (additive): + prcnn_head_tail_fwd, prcnn_head_tail_work_bytes, prcnn_head_tail_bwd,
+                                 * prcnn_dropout_rows (the training heads' Dropout + output layer, the mask keyed by a counter);
                                  * still 12 (additive): + prcnn_eval_gt_max_iou, prcnn_eval_stats_accumulate, prcnn_eval_stats_workspace_bytes
                                  * (recall, segmentation IoU and RCNN accuracy of the evaluation loops counted on the device);
                                  * still 12 (additive): + prcnn_rcnn_offline_sample, prcnn_rcnn_offline_finish (RCNN offline training batches);
@@ -1129,6 +1131,35 @@ int prcnn_optim_step_adam(const prcnn_optim_tensor_t* tensors, const prcnn_optim
 int prcnn_optim_step_sgd(const prcnn_optim_tensor_t* tensors, const prcnn_optim_chunk_t* chunks, int64_t num_chunks, const double* partial,
                          float max_norm, const float* coef, float* state, float weight_decay, float momentum, float neg_lr,
                          prcnn_stream_t stream);
+
+/* ======================================================================================================
+ * Tail of a training head on channels-last rows (csrc/head_tail.hip, the mask: csrc/head_tail_math.h) -- Dropout keyed by a counter
+ * and the output layer, forward and backward (pointnet2 pytorch_utils._HeadTail, switch PRCNN_HEAD_TAIL).
+ *   keep(r, k) = scene_u01f(scene_rand(seed, stream_id, call, r * K + k)) >= p,  scale = 1.0f / (1.0f - p),
+ *   drop(x)[r, k] = keep ? x[r, k] * scale : 0.  The dropped entry is SELECTED to zero: an Inf / NaN there contributes nothing.
+ *   p == 0 keeps everything with scale 1: the tail is then the plain linear layer.
+ * Domain: float32; K % 32 == 0, 32 <= K <= 256; 1 <= N <= 96; R >= 1; R * K <= 2^32; 0 <= p < 1; x (R, K) and w (N, K) contiguous
+ * and 16-byte aligned.  Anything else: PRCNN_EINVAL, nothing is launched (prcnn_head_tail_work_bytes: 0).
+ *   prcnn_head_tail_fwd         out (R, N) = drop(x) w^T + b (b null: no bias).  fp32 MFMA; the K order of a sum depends on (K, N)
+ *                               alone: a row's output bits depend on r, its own row and the weights, not on R.
+ *   prcnn_head_tail_work_bytes  bytes of the backward's workspace: one (N K + N) float tile per 512 rows.  Never cleared by anyone.
+ *   prcnn_head_tail_bwd         g (R, N) with row stride ldg >= N floats (any alignment; columns past N are not read).  One pass over
+ *                               x and g writes gx (R, K) = keep ? scale * (g w) : 0 -- exactly zero at every dropped entry -- and
+ *                               per-workgroup partial tiles of gw (N, K) = g^T drop(x) and gb (N) = the column sums of g; a second
+ *                               launch adds the partials in a fixed order.  Every output element is written exactly once, no
+ *                               atomics, no memset: the same state gives the same bytes.  gx, gw, gb may each be null and its work
+ *                               is skipped (all null: nothing is launched); work is needed for gw or gb, x for gw, w for gx.
+ *   prcnn_dropout_rows          out (R, K) = drop(x); K % 4 == 0 suffices here.  Backward is the same call on the gradient.
+ * No host synchronisation, no allocation.
+ * ====================================================================================================== */
+int prcnn_head_tail_fwd(const float* x, const float* w, const float* b, float* out, int64_t R, int K, int N, uint32_t seed,
+                        uint32_t stream_id, uint32_t call, float p, prcnn_stream_t stream);
+size_t prcnn_head_tail_work_bytes(int64_t R, int K, int N);
+int prcnn_head_tail_bwd(const float* x, const float* w, const float* g, int64_t ldg, float* gx, float* gw, float* gb, void* work,
+                        size_t work_bytes, int64_t R, int K, int N, uint32_t seed, uint32_t stream_id, uint32_t call, float p,
+                        prcnn_stream_t stream);
+int prcnn_dropout_rows(const float* x, float* out, int64_t R, int K, uint32_t seed, uint32_t stream_id, uint32_t call, float p,
+                       prcnn_stream_t stream);
 
 /* ======================================================================================================
  * KITTI result files formatted on the device (csrc/kitti_text.hip, per-box arithmetic and the "%.4f" conversion:

@@ -16,6 +16,7 @@ _F = ctypes.c_float
 _L = ctypes.c_int64
 _Z = ctypes.c_size_t
 _D = ctypes.c_double
+_U = ctypes.c_uint32
 
 
 
@@ -190,6 +191,10 @@ SIGNATURES = {
     "prcnn_optim_step_adam": (_I, [_P, _P, _L, _P, _F, _P, _P, _F, _F, _F, _F, _F, _F, _F, _P]),
     "prcnn_optim_step_sgd": (_I, [_P, _P, _L, _P, _F, _P, _P, _F, _F, _F, _P]),
     "prcnn_kitti_result_text": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, ctypes.c_char_p, _P, _P, _P, _P, _P, _P]),
+    "prcnn_head_tail_fwd": (_I, [_P, _P, _P, _P, _L, _I, _I, _U, _U, _U, _F, _P]),
+    "prcnn_head_tail_work_bytes": (_Z, [_L, _I, _I]),
+    "prcnn_head_tail_bwd": (_I, [_P, _P, _P, _L, _P, _P, _P, _P, _Z, _L, _I, _I, _U, _U, _U, _F, _P]),
+    "prcnn_dropout_rows": (_I, [_P, _P, _L, _I, _U, _U, _U, _F, _P]),
 }
 
 _lib = None

@@ -33,6 +33,8 @@
 //   40, 42, 43, 50   rcnn_offline.hip (offline RoI sampling and noise; 41 left free); 51-53 its per-RoI augmentation (enable, angle, scale)
 //   60     aug_scene.hip: extra_gt_num = randint(10, 15) (tools/generate_aug_scene.py:157), position 0 -- 10 + below(r, 5)
 //   61     aug_scene.hip: per try t, randint(0, D - 1) (:175), position t -- below(r, D - 1); frame = the new sample id
+//   70 + ordinal   head_tail.hip: the training heads' Dropout masks (head_tail_math.h), ordinal = the nn.Dropout module's place in
+//          the model's named_modules(); frame = the module's call counter, position r * K + k -- keep iff the float32 u01(r) >= p
 //   with u01(r) = fp32(r >> 8) * 2^-24 widened to double, below(r, n) = (r * n) >> 32.
 //   train_scene.hip also uses streams 0-2 for its own draw; there the position is the candidate's identity: the raw index
 //   for a scene point, n_raw + j for the j-th pasted point.

@@ -8,11 +8,24 @@ with BN folded into the packed weights; activations stay channels-last between l
 caller as transposed VIEWS, so a chain of these modules never pays a layout change.  Otherwise (training,
 CPU construction) the modules behave as plain torch Conv/BN/ReLU stacks.
 """
+import os
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from pointrcnn_amd import ops
+
+# Training heads: Dropout + output layer as one device tail whose mask is a pure function of (seed, stream, call, position)
+# (csrc/head_tail.hip; _HeadTail below).  PRCNN_HEAD_TAIL=1, read once at import like PRCNN_TRAIN_SPLIT; unset / 0 (default) = the
+# composed path (F.dropout on torch's generator + _LinearRows).  PRCNN_HEAD_TAIL_SEED: the seed of Dropout modules nobody keyed.
+_HEAD_TAIL_ENV = os.environ.get("PRCNN_HEAD_TAIL", "")
+if _HEAD_TAIL_ENV not in ("", "0", "1"):
+    raise RuntimeError("PRCNN_HEAD_TAIL=%r: 1 = the device tail of the training heads, 0 / unset = the composed path" % _HEAD_TAIL_ENV)
+HEAD_TAIL = _HEAD_TAIL_ENV == "1"
+HEAD_TAIL_SEED = int(os.environ.get("PRCNN_HEAD_TAIL_SEED", "0")) & 0xFFFFFFFF
+HEAD_STREAM0 = 70                 # train_mlp.HEAD_STREAM0: Dropout `ordinal` draws from stream 70 + ordinal
+_next_ordinal = 0                 # the ordinal the next Dropout met un-keyed receives
 
 
 def _fold_bn(conv, bn):
@@ -125,21 +138,93 @@ class _LinearRows(torch.autograd.Function):
         return gx, gw, gb
 
 
-def _train_rows_sequential(seq, x):
-    """Training: a Sequential of 1 x 1 Conv1d layers and Dropout on (B, C, L) (the RPN / RCNN heads, lib/net/rpn.py:20-46) computed
-    on channels-last ROWS from end to end: runs of Conv -> BatchNorm -> ReLU are one hand-written autograd node each
-    (train_mlp.SharedMLPTrain), Dropout is elementwise on the rows, a bare Conv (bias, no norm: the output layer) is F.linear on the
-    rows.  Module by module the Sequential would transpose (B, C, L) <-> rows around every fused layer and run the output layer as
-    an MIOpen convolution forward + backward: four full-size copies and 1.2 ms of a 15 ms step for a 128 -> 76 product.
-    The result is returned as a (B, C_out, L) VIEW of the (B, L, C_out) rows, so the caller's `.transpose(1, 2).contiguous()` is
-    free.  None: some member is not covered (the caller runs seq(x))."""
+def key_dropouts(model, seed, rank=0):
+    """Key every nn.Dropout of `model`, in named_modules() order: stream 70 + ordinal, effective seed (seed + rank) mod 2^32 (DDP
+    ranks draw different masks), calls = 0.  -> {module name: stream}.  A Dropout met un-keyed later takes the next ordinal."""
+    global _next_ordinal
+    streams = {}
+    ordinal = 0
+    for name, m in model.named_modules():
+        if isinstance(m, nn.Dropout):
+            m._prcnn_stream = HEAD_STREAM0 + ordinal
+            m._prcnn_seed = (int(seed) + int(rank)) & 0xFFFFFFFF
+            m._prcnn_calls = 0
+            streams[name] = m._prcnn_stream
+            ordinal += 1
+    _next_ordinal = max(_next_ordinal, ordinal)
+    return streams
+
+
+def _take_key(m):
+    """(seed, stream, call, p) of this training forward through Dropout m; the module's call counter moves on"""
+    global _next_ordinal
+    if not hasattr(m, "_prcnn_stream"):
+        m._prcnn_stream = HEAD_STREAM0 + _next_ordinal
+        m._prcnn_seed = HEAD_TAIL_SEED
+        _next_ordinal += 1
+    call = getattr(m, "_prcnn_calls", 0)
+    m._prcnn_calls = call + 1
+    return (m._prcnn_seed, m._prcnn_stream, call & 0xFFFFFFFF, float(m.p))
+
+
+def dropout_state(model):
+    """{module name: calls} of every nn.Dropout: with the keys (key_dropouts), all that the masks of the steps to come depend on"""
+    return {name: int(getattr(m, "_prcnn_calls", 0)) for name, m in model.named_modules() if isinstance(m, nn.Dropout)}
+
+
+def load_dropout_state(model, state):
+    mods = {name: m for name, m in model.named_modules() if isinstance(m, nn.Dropout)}
+    unknown = sorted(set(state) - set(mods))
+    if unknown:
+        raise ValueError("load_dropout_state: the model has no Dropout named %s" % ", ".join(unknown))
+    for name, calls in state.items():
+        mods[name]._prcnn_calls = int(calls)
+
+
+class _HeadTail(torch.autograd.Function):
+    """out = drop(x) W^T + b on (R, K) rows in one launch, backward in two (ops.head_tail_forward / head_tail_backward).  Saved for
+    backward: x, W and the key (seed, stream, call, p) -- no mask and no dropped copy of x; backward rebuilds the mask from the key."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, key):
+        x, w = x.contiguous(), w.contiguous()
+        ctx.save_for_backward(x, w)
+        ctx.key = key
+        ctx.has_bias = b is not None
+        return ops.head_tail_forward(x, w, None if b is None else b.contiguous(), key)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        gx, gw, gb = ops.head_tail_backward(x, w, g, ctx.key, ctx.needs_input_grad[0], ctx.needs_input_grad[1],
+                                            ctx.has_bias and ctx.needs_input_grad[2])
+        return gx, gw, gb, None
+
+
+class _DropoutRows(torch.autograd.Function):
+    """drop(x) on rows with the counter mask (a Dropout that no output layer follows); backward is the same call on the gradient"""
+
+    @staticmethod
+    def forward(ctx, x, key):
+        ctx.key = key
+        return ops.dropout_rows(x.contiguous(), key)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ops.dropout_rows(g.contiguous(), ctx.key), None
+
+
+def _head_plan(seq, head_tail):
+    """The steps a head Sequential runs as on rows, or None when a member is not covered.  Switch off: ("stack", [layers]),
+    ("dropout", m), ("linear", m) -- one step per Dropout and per bare Conv.  Switch on: a Dropout with p == 0 or in eval mode is the
+    identity and leaves the plan (the layers around it form ONE stack); Dropout + linear is ("tail", dropout, m), a lone linear
+    ("tail", None, m) (p = 0), a lone Dropout ("dropout_dev", m)."""
     from pointrcnn_amd import train_mlp
-    from . import pointnet2_modules
-    if not pointnet2_modules.TRAIN_FUSED:
-        return None
     plan, run = [], []
     for m in seq:
         if isinstance(m, nn.Dropout):
+            if head_tail and (m.p == 0 or not m.training):
+                continue
             if run:
                 plan.append(("stack", run))
                 run = []
@@ -158,20 +243,79 @@ def _train_rows_sequential(seq, x):
             return None
     if run:
         plan.append(("stack", run))
-    if not any(k == "stack" for k, _ in plan):
+    if not head_tail:
+        return plan
+    out, i = [], 0
+    while i < len(plan):
+        step = plan[i]
+        if step[0] == "dropout" and i + 1 < len(plan) and plan[i + 1][0] == "linear":
+            out.append(("tail", step[1], plan[i + 1][1]))
+            i += 2
+            continue
+        if step[0] == "dropout":
+            out.append(("dropout_dev", step[1]))
+        elif step[0] == "linear":
+            out.append(("tail", None, step[1]))
+        else:
+            out.append(step)
+        i += 1
+    return out
+
+
+def _linear_rows(rows, m):
+    conv, _, act = m._parts()
+    rows = _LinearRows.apply(rows, conv.weight.view(conv.out_channels, conv.in_channels), conv.bias)
+    if act is not None:
+        rows = F.relu(rows) if isinstance(act, nn.ReLU) else act(rows)
+    return rows
+
+
+def _train_rows_sequential(seq, x):
+    """Training: a Sequential of 1 x 1 Conv1d layers and Dropout on (B, C, L) (the RPN / RCNN heads, lib/net/rpn.py:20-46) computed
+    on channels-last ROWS from end to end: runs of Conv -> BatchNorm -> ReLU are one hand-written autograd node each
+    (train_mlp.SharedMLPTrain), Dropout is elementwise on the rows, a bare Conv (bias, no norm: the output layer) is F.linear on the
+    rows.  Module by module the Sequential would transpose (B, C, L) <-> rows around every fused layer and run the output layer as
+    an MIOpen convolution forward + backward: four full-size copies and 1.2 ms of a 15 ms step for a 128 -> 76 product.
+    With HEAD_TAIL the Dropout and the output layer are one device tail (_HeadTail), the mask keyed by a counter; shapes outside the
+    tail's domain take the composed pieces.
+    The result is returned as a (B, C_out, L) VIEW of the (B, L, C_out) rows, so the caller's `.transpose(1, 2).contiguous()` is
+    free.  None: some member is not covered (the caller runs seq(x))."""
+    from pointrcnn_amd import train_mlp
+    from . import pointnet2_modules
+    if not pointnet2_modules.TRAIN_FUSED:
+        return None
+    plan = _head_plan(seq, HEAD_TAIL)
+    if plan is None or not any(step[0] == "stack" for step in plan):
         return None
     B, C, L = x.shape
     rows = _rows_view(x.permute(0, 2, 1)).reshape(B * L, C)
-    for kind, m in plan:
+    for step in plan:
+        kind, m = step[0], step[-1]
         if kind == "stack":
             rows = train_mlp.run_stack(m, train_mlp.Source("plain"), rows)
         elif kind == "dropout":
             rows = F.dropout(rows, m.p, m.training, False)
+        elif kind == "linear":
+            rows = _linear_rows(rows, m)
+        elif kind == "dropout_dev":
+            R, K = rows.shape
+            if K % 4 == 0 and R * K <= 2 ** 32 and m.p < 1:
+                rows = _DropoutRows.apply(rows, _take_key(m))
+            else:
+                rows = F.dropout(rows, m.p, m.training, False)
         else:
+            drop = step[1]
             conv, _, act = m._parts()
-            rows = _LinearRows.apply(rows, conv.weight.view(conv.out_channels, conv.in_channels), conv.bias)
-            if act is not None:
-                rows = F.relu(rows) if isinstance(act, nn.ReLU) else act(rows)
+            p = 0.0 if drop is None else float(drop.p)
+            if ops.head_tail_supported(rows.shape[0], conv.in_channels, conv.out_channels, p):
+                key = (0, HEAD_STREAM0, 0, 0.0) if drop is None else _take_key(drop)
+                rows = _HeadTail.apply(rows, conv.weight.view(conv.out_channels, conv.in_channels), conv.bias, key)
+                if act is not None:
+                    rows = F.relu(rows) if isinstance(act, nn.ReLU) else act(rows)
+            else:
+                if drop is not None:
+                    rows = F.dropout(rows, drop.p, drop.training, False)
+                rows = _linear_rows(rows, m)
     return rows.view(B, L, -1).permute(0, 2, 1)
 
 

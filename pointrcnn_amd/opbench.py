@@ -321,6 +321,88 @@ def train_wgrad_rows(dev, rounds=5):
                               "min_us": round(t[0] * 1e6, 1), "max_us": round(t[-1] * 1e6, 1), "wide_wgrad_GFLOP": round(flops / 1e9, 2)}), flush=True)
 
 
+def head_tail_rows(dev, R=262144, K=128, rounds=5):
+    """`head_tail fwd+bwd`: the tail of an RPN training head -- Dropout(0.5) and the output layer (N = 76 and N = 1) on R rows, forward
+    and backward with all three gradients -- as the composed pieces (F.dropout on torch's generator + pytorch_utils._LinearRows) against
+    the device tail (pytorch_utils._HeadTail: csrc/head_tail.hip), alternated in one process; per route the median, minimum and maximum
+    over `rounds` windows of 20 calls.  Traffic floors, each tensor once: composed = what the ops read and write one by one, device =
+    x, out / x, g, gx.  peak_MB: torch.cuda.max_memory_allocated over one forward + backward above what was allocated before it."""
+    import torch.nn.functional as F
+    import pointnet2_lib.pointnet2.pytorch_utils as pt_utils
+    g = torch.Generator().manual_seed(13)
+    x = torch.randn(R, K, generator=g).to(dev).requires_grad_(True)
+    for N in (76, 1):
+        w = (torch.randn(N, K, generator=g) / K ** 0.5).to(dev).requires_grad_(True)
+        b = torch.zeros(N, device=dev, requires_grad=True)
+        gout = torch.randn(R, N, generator=g).to(dev)
+        call = [0]
+
+        def composed():
+            torch.autograd.grad(pt_utils._LinearRows.apply(F.dropout(x, 0.5, True, False), w, b), (x, w, b), gout)
+
+        def device():
+            call[0] += 1
+            torch.autograd.grad(pt_utils._HeadTail.apply(x, w, b, (0, 70, call[0], 0.5)), (x, w, b), gout)
+        routes = (("composed", composed), ("device", device))
+        peak = {}
+        for name, fn in routes:
+            fn()
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            fn()
+            torch.cuda.synchronize()
+            peak[name] = (torch.cuda.max_memory_allocated() - base) / 1e6
+        times = {name: [] for name, _ in routes}
+        for _ in range(rounds):
+            for name, fn in routes:
+                times[name].append(timeit(fn))
+        xb, ob = 4 * R * K, 4 * R * N
+        floor = {"composed": (xb + xb + xb // 4 + xb + ob) + (ob + xb + ob + xb + ob + xb + xb // 4 + xb), "device": (xb + ob) + (xb + ob + xb)}
+        for name, _ in routes:
+            t = sorted(times[name])
+            print(json.dumps({"op": "head_tail fwd+bwd (%s)" % name, "shape": "R%d K%d N%d p0.5" % (R, K, N),
+                              "median_us": round(t[len(t) // 2] * 1e6, 1), "min_us": round(t[0] * 1e6, 1), "max_us": round(t[-1] * 1e6, 1),
+                              "traffic_floor_MB": round(floor[name] / 1e6, 1), "floor_GBps_at_median": round(floor[name] / t[len(t) // 2] / 1e9, 1),
+                              "peak_MB": round(peak[name], 1)}), flush=True)
+
+
+def head_tail_step_memory(dev, B=16, N=16384, steps=3):
+    """`rpn train step memory`: torch.cuda.max_memory_allocated over RPNTrainer steps at the training shape (bs16 x 16 384 points,
+    12 synthetic boxes per frame) with the heads on the composed path and on the device tail (pytorch_utils.HEAD_TAIL), one model each,
+    in one process; the peak is reset after a first step of each setting"""
+    import pointnet2_lib.pointnet2.pytorch_utils as pt_utils
+    from . import train_functions as tf
+    g = torch.Generator().manual_seed(99)
+    pts = rpn.synthetic_clouds(B, N, device=dev)
+    pick = torch.randint(0, N, (B, 12), generator=g).to(dev)
+    ctr = torch.gather(pts, 1, pick[..., None].expand(-1, -1, 3))
+    hwl = torch.tensor([1.56, 1.6, 3.9], device=dev) * 2.0
+    ry = (torch.rand((B, 12, 1), generator=g) * 6.283 - 3.1416).to(dev)
+    gt = torch.cat([ctr[..., 0:1], ctr[..., 1:2] + hwl[0] / 2, ctr[..., 2:3], hwl.expand(B, 12, 3), ry], 2).contiguous()
+    cls, reg = ops.rpn_labels(pts, gt)
+    batch = {"pts_input": pts, "rpn_cls_label": cls.long(), "rpn_reg_label": reg}
+    was = pt_utils.HEAD_TAIL
+    try:
+        for on in (False, True):
+            pt_utils.HEAD_TAIL = on
+            torch.manual_seed(1234)
+            model = tf.init_rpn_head_weights(rpn.randomize_bn_stats(rpn.RPN(), seed=7)).to(dev)
+            trainer = tf.RPNTrainer(model)
+            trainer.step(batch)
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            for _ in range(steps):
+                trainer.step(batch)
+            torch.cuda.synchronize()
+            print(json.dumps({"op": "rpn train step memory (%s)" % ("device tail" if on else "composed heads"), "shape": "B%d N%d" % (B, N),
+                              "max_memory_allocated_MB": round(torch.cuda.max_memory_allocated() / 1e6, 1)}), flush=True)
+            del trainer, model
+            torch.cuda.empty_cache()
+    finally:
+        pt_utils.HEAD_TAIL = was
+
+
 def optimizer_rows(dev, rounds=5):
     """`optimizer step`: one optim.OneCycleAdam.step() -- gradient-norm clip, decoupled decay, Adam, schedule -- over the parameter
     lists of rpn.RPN() and of the RCNN net, the composed torch route against the two launches of csrc/optim.hip, alternated in one
@@ -652,7 +734,7 @@ def eval_loop_rows(dev, B=16, nbatches=3, rounds=5):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
-    ap.add_argument("--only", default=None, help="run one row family only: eval_stats | optimizer | rpn_loss_kinds | train_split | train_wgrad | result_writer | eval_loop")
+    ap.add_argument("--only", default=None, help="run one row family only: eval_stats | optimizer | rpn_loss_kinds | train_split | train_wgrad | head_tail | result_writer | eval_loop")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     if args.only == "result_writer":
@@ -676,6 +758,10 @@ def main():
         return
     if args.only == "train_wgrad":
         train_wgrad_rows(dev)
+        return
+    if args.only == "head_tail":
+        head_tail_rows(dev)
+        head_tail_step_memory(dev)
         return
     B = 8 if args.quick else 32
     N = 16384

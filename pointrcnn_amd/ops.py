@@ -1838,3 +1838,67 @@ def kitti_result_text(boxes, scores, P2, img_hw, keep=None, num=None, class_name
     _cabi.check(_cabi.lib().prcnn_kitti_result_text(_p(boxes), _p(scores), _p(keep), _p(num), B, M, _p(P2), _p(img_hw), name, _p(text),
                                                     _p(text_len), _p(status), _p(rows), _p(valid), _stream()), "prcnn_kitti_result_text")
     return (text, text_len, status, rows, valid) if want_rows else (text, text_len, status)
+
+
+# ---- training heads: Dropout keyed by a counter + the output layer (csrc/head_tail.hip) ----------------------------------------
+HEAD_TAIL_PART_ROWS = 512      # rows per partial tile of head_tail_backward (csrc/head_tail.hip HT_BWD_ROWS)
+
+
+def head_tail_supported(R, K, N, p):
+    """the domain of prcnn_head_tail_fwd / _bwd (include/prcnn_pointops.h); outside it the caller takes the composed path"""
+    return R >= 1 and K % 32 == 0 and 32 <= K <= 256 and 1 <= N <= 96 and R * K <= 2 ** 32 and 0.0 <= p < 1.0
+
+
+def _head_tail_key(key):
+    seed, stream, call, p = key
+    return int(seed) & 0xFFFFFFFF, int(stream) & 0xFFFFFFFF, int(call) & 0xFFFFFFFF, float(p)
+
+
+def head_tail_forward(x, w, b, key):
+    """out (R, N) = drop(x) w^T + b, the mask a pure function of key = (seed, stream, call, p) and the entry's position
+    (train_mlp.head_keep_mask).  x (R, K), w (N, K), b (N,) or None.  One launch."""
+    _chk(x, "x", ndim=2); _chk(w, "w", ndim=2)
+    R, K = x.shape
+    N = w.shape[0]
+    if w.shape[1] != K or (b is not None and tuple(_chk(b, "b", ndim=1).shape) != (N,)):
+        raise ValueError("head_tail_forward: x (R, K), w (N, K), b (N,); got %s, %s, %s" % (tuple(x.shape), tuple(w.shape), None if b is None else tuple(b.shape)))
+    seed, stream, call, p = _head_tail_key(key)
+    out = torch.empty((R, N), dtype=_F32, device=x.device)
+    _cabi.check(_cabi.lib().prcnn_head_tail_fwd(_p(x), _p(w), _p(b), _p(out), R, K, N, seed, stream, call, p, _stream()), "prcnn_head_tail_fwd")
+    return out
+
+
+def head_tail_backward(x, w, g, key, want_gx=True, want_gw=True, want_gb=True):
+    """-> (gx (R, K), gw (N, K), gb (N,)), None where not wanted, from one pass over x and g plus a fixed-order reduce of the partial
+    tiles.  g (R, N) is taken as it is when its rows are uniformly strided (a column slice of a wider buffer)."""
+    _chk(x, "x", ndim=2); _chk(w, "w", ndim=2)
+    R, K = x.shape
+    N = w.shape[0]
+    if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == _F32 and tuple(g.shape) == (R, N)) or w.shape[1] != K:
+        raise ValueError("head_tail_backward: x (R, K), w (N, K) and a float32 device g (R, N) expected")
+    if (N > 1 and g.stride(1) != 1) or (R > 1 and g.stride(0) < N):
+        g = g.contiguous()
+    ldg = g.stride(0) if R > 1 else N
+    seed, stream, call, p = _head_tail_key(key)
+    L = _cabi.lib()
+    dev = x.device
+    gx = torch.empty((R, K), dtype=_F32, device=dev) if want_gx else None
+    gw = torch.empty((N, K), dtype=_F32, device=dev) if want_gw else None
+    gb = torch.empty((N,), dtype=_F32, device=dev) if want_gb else None
+    work, nbytes = None, 0
+    if want_gw or want_gb:
+        nbytes = L.prcnn_head_tail_work_bytes(R, K, N)
+        work = torch.empty((max(nbytes, 4) // 4,), dtype=_F32, device=dev)
+    _cabi.check(L.prcnn_head_tail_bwd(_p(x), _p(w), _p(g), ldg, _p(gx), _p(gw), _p(gb), _p(work), nbytes, R, K, N, seed, stream, call, p,
+                                      _stream()), "prcnn_head_tail_bwd")
+    return gx, gw, gb
+
+
+def dropout_rows(x, key):
+    """drop(x) on (R, K) rows with the mask of key = (seed, stream, call, p); its backward is the same call on the gradient"""
+    _chk(x, "x", ndim=2)
+    R, K = x.shape
+    seed, stream, call, p = _head_tail_key(key)
+    out = torch.empty_like(x)
+    _cabi.check(_cabi.lib().prcnn_dropout_rows(_p(x), _p(out), R, K, seed, stream, call, p, _stream()), "prcnn_dropout_rows")
+    return out

@@ -200,7 +200,19 @@ def checkpoint_state(model=None, optimizer=None, epoch=None, it=None, optimizer_
             optim_state = _reference_onecycle_state(model, optimizer, optimizer.iteration if it is None else it)
         else:
             optim_state = optimizer.state_dict()
-    return {"epoch": epoch, "it": it, "model_state": None if model is None else _unwrap(model).state_dict(), "optimizer_state": optim_state}
+    state = {"epoch": epoch, "it": it, "model_state": None if model is None else _unwrap(model).state_dict(), "optimizer_state": optim_state}
+    pt_utils = _head_tail_utils()
+    if pt_utils is not None and model is not None:      # PRCNN_HEAD_TAIL: the Dropout call counters, so that a resumed run replays the masks
+        state["dropout_calls"] = pt_utils.dropout_state(_unwrap(model))
+    return state
+
+
+def _head_tail_utils():
+    """pytorch_utils when the training heads' device tail is switched on (its masks are keyed by per-module call counters), else None"""
+    import pointrcnn_amd
+    pointrcnn_amd.install()
+    import pointnet2_lib.pointnet2.pytorch_utils as pt_utils
+    return pt_utils if pt_utils.HEAD_TAIL else None
 
 
 def save_checkpoint(state, filename="checkpoint"):
@@ -239,6 +251,9 @@ def load_checkpoint(model=None, optimizer=None, filename="checkpoint", logger=_L
     it = ckpt.get("it", 0.0)
     if model is not None and ckpt["model_state"] is not None:
         _unwrap(model).load_state_dict(ckpt["model_state"])
+    pt_utils = _head_tail_utils()
+    if pt_utils is not None and model is not None and ckpt.get("dropout_calls") is not None:
+        pt_utils.load_dropout_state(_unwrap(model), ckpt["dropout_calls"])
     sd = ckpt["optimizer_state"]
     if optimizer is not None and sd is not None:
         if isinstance(optimizer, optim.OneCycleAdam) and len(sd["param_groups"]) == 2:

@@ -55,6 +55,18 @@ def logged_flops(log):
             total += 2.0 * r * k * n * (3.0 if (li > 0 or need_x) else 2.0)
     return total
 MODE = {"plain": 0, "group": 1, "interp": 2}
+HEAD_STREAM0 = 70       # Dropout module `ordinal` draws from stream 70 + ordinal (csrc/scene.hip lists the ids in use)
+
+
+def head_keep_mask(seed, stream, call, R, K, p):
+    """csrc/head_tail_math.h's keep(seed, stream, call, r, k) on the host -> (R, K) bool ndarray: the float32 draw of counter
+    r * K + k (mod 2^32, `call` in the generator's frame slot) compared with float32 p"""
+    import numpy as np
+    from .kitti_input import counter_rand
+    i = np.arange(int(R) * int(K), dtype=np.uint64) & np.uint64(0xFFFFFFFF)
+    r = counter_rand(int(seed) & 0xFFFFFFFF, int(stream), int(call), i)
+    u = (r >> np.uint64(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+    return (u >= np.float32(p)).reshape(int(R), int(K))
 
 
 def _up(x, m):
