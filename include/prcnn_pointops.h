@@ -361,6 +361,13 @@ typedef struct prcnn_chain_group_problem {
     int ld_feat, B, N, M, nsample, C, nlayers, ld_out, col_off, pool_ns;
 } prcnn_chain_group_problem_t;
 int prcnn_mlp_chain_group_multi(int nprob, const prcnn_chain_group_problem_t* prob, prcnn_stream_t stream);
+/* The same launch, storing by destination: dst (host array over the problems; NULL, or NULL entries: that problem stores to its
+ * own out as above) names where problem q's result rows go in the level output out2 (ld_out2 floats per row, problem q's columns
+ * at col_off2[q]).  Un-pooled problem: dst[q][row] >= 0 -> row dst[q][row] of out2, < 0 -> row `row` of the problem's out
+ * (prcnn_group_compact_pair_dst's rdst).  Pooled problem: group g -> row dst[q][g] of out2 (the dense list's listn); its out is
+ * not written.  Same kernels, grids and arithmetic as prcnn_mlp_chain_group_multi. */
+int prcnn_mlp_chain_group_multi_dst(int nprob, const prcnn_chain_group_problem_t* prob, const int32_t* const* dst, float* out2, int ld_out2,
+                                    const int* col_off2, prcnn_stream_t stream);
 
 /* out[r, col_off + c] = max over ns consecutive rows of in (generic nsample fallback for pooling) */
 int prcnn_maxpool_rows(const float* in, int ld_in, int64_t rows_out, int ns, int C, float* out, int ld_out,
@@ -624,6 +631,17 @@ int prcnn_group_compact_pair(const int32_t* idx_a, int ns_a, int T_a, const int3
 int prcnn_level_pool(int nprob, const float* const* src, const int* ld_src, const int32_t* const* list, const int32_t* const* off,
                      const int32_t* const* cnt, const int32_t* const* count, const int* max_items, const int* C, const int* col_off,
                      float* dst, int ld_dst, prcnn_stream_t stream);
+/* prcnn_group_compact_pair, and per flat row where its result belongs: rdst_a / rdst_b (B*M*T_a / B*M*T_b i32) hold the group id
+ * for the only real row of a one-row group (its result IS the group's row of the level output) and -1 for the rows of a group
+ * that has more to pool. */
+int prcnn_group_compact_pair_dst(const int32_t* idx_a, int ns_a, int T_a, const int32_t* idx_b, int ns_b, int T_b, const float* new_xyz,
+                                 int B, int N, int M, void* const* lists_a, void* const* lists_b, int32_t* rdst_a, int32_t* rdst_b,
+                                 int32_t* counts, prcnn_stream_t stream);
+/* What is left of prcnn_level_pool after prcnn_mlp_chain_group_multi_dst: every problem a flat list (off[q], cnt[q] non-NULL),
+ * only groups with cnt >= 2 are pooled and stored; the cells of one-row groups are not touched. */
+int prcnn_level_pool_residual(int nprob, const float* const* src, const int* ld_src, const int32_t* const* list, const int32_t* const* off,
+                              const int32_t* const* cnt, const int32_t* const* count, const int* max_items, const int* C, const int* col_off,
+                              float* dst, int ld_dst, prcnn_stream_t stream);
 
 /* ======================================================================================================
  * RPN input builder (scene.hip) -- SURVEY 8(f) rank 4.  Replaces the inference branch of

@@ -109,6 +109,7 @@ SIGNATURES = {
     "prcnn_mlp_chain_group": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "prcnn_mlp_chain_interp": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P]),
     "prcnn_mlp_chain_group_multi": (_I, [_I, _P, _P]),
+    "prcnn_mlp_chain_group_multi_dst": (_I, [_I, _P, _P, _P, _I, _P, _P]),
     "prcnn_maxpool_rows": (_I, [_P, _I, _L, _I, _I, _P, _I, _I, _P]),
     "prcnn_roipool3d": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "prcnn_roipool3d_work_bytes": (_Z, [_I, _I]),
@@ -136,6 +137,8 @@ SIGNATURES = {
     "prcnn_scatter_rows": (_I, [_P, _I, _P, _P, _I, _I, _P, _I, _I, _P]),
     "prcnn_group_compact_pair": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P]),
     "prcnn_level_pool": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "prcnn_group_compact_pair_dst": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "prcnn_level_pool_residual": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "prcnn_scene_workspace_bytes": (_Z, [_L, _I]),
     "prcnn_scene_prepare": (_I, [_P, _P, _I, _L, _I, _P, _P, _P, _I, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "prcnn_train_scene_workspace_bytes": (_Z, [_L, _I, _I, _I]),

@@ -37,6 +37,8 @@ struct CompactParams {
     int32_t* counts;         // [0] flat rows, [1] dense groups, [2] sparse groups (zeroed by the launcher)
     const int32_t* valid_n;  // (B) or NULL: points >= valid_n[b] of frame b are wrap-copies of earlier points (roipool3d)
     int G, N, M, ns, T;
+    int32_t* rdst;           // (G*T) or NULL: per flat row, where its result belongs -- the group id when the row is its group's only
+                             // one (it IS the group's row of the level output), -1 when the group's rows have to be pooled
 };
 
 constexpr int COMPACT_THREADS = 1024;
@@ -116,6 +118,7 @@ __device__ __forceinline__ void group_compact_body(const CompactParams& P, int b
         P.slist[j] = g; P.soff[j] = r0; P.scnt[j] = cnt;
         for (int s = 0; s < cnt; s++) {
             P.ridx[r0 + s] = b * P.N + row[s];
+            if (P.rdst) P.rdst[r0 + s] = cnt == 1 ? g : -1;
 #pragma unroll
             for (int c = 0; c < 3; c++) P.rnx[(size_t)(r0 + s) * 3 + c] = c3[c];
         }
@@ -215,6 +218,54 @@ __global__ __launch_bounds__(256) void level_pool_kernel(LevelPoolParams L) {
     }
 }
 
+// The pool that is left once the stacks store by destination (CompactParams::rdst, MlpParams::row_dst / grp_dst): one-row groups and
+// dense groups are in the level output already, so every problem is a flat list and only its groups with TWO OR MORE rows are
+// pooled -- none on uniform clouds, where the launch is a walk over cnt[].  A group is taken by `lanes` (8-64, by C) adjacent lanes,
+// each with 16-byte pieces of the row (VEC) or single columns; fmaxf over the rows in ascending order, as level_pool_kernel.
+struct ResidualPoolParams {
+    const float* src[LEVEL_POOL_MAX];
+    const int32_t* list[LEVEL_POOL_MAX];
+    const int32_t* off[LEVEL_POOL_MAX];
+    const int32_t* cnt[LEVEL_POOL_MAX];
+    const int32_t* count[LEVEL_POOL_MAX];
+    int ld_src[LEVEL_POOL_MAX], C[LEVEL_POOL_MAX], col_off[LEVEL_POOL_MAX], lane_shift[LEVEL_POOL_MAX];
+    float* dst;
+    int ld_dst;
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void residual_pool_kernel(ResidualPoolParams L) {
+    const int q = blockIdx.y;
+    const float* __restrict__ src = L.src[q];
+    const int32_t* __restrict__ list = L.list[q];
+    const int32_t* __restrict__ off = L.off[q];
+    const int32_t* __restrict__ cnt = L.cnt[q];
+    const int ld_src = L.ld_src[q], C = L.C[q], sh = L.lane_shift[q];
+    const int groups = *L.count[q];
+    const int per_block = 256 >> sh, l = (int)threadIdx.x & ((1 << sh) - 1);
+    constexpr int W = VEC ? 4 : 1;
+    for (int j = (int)blockIdx.x * per_block + ((int)threadIdx.x >> sh); j < groups; j += (int)gridDim.x * per_block) {
+        const int rows = cnt[j];
+        if (rows < 2) continue;                                // stored by the stack
+        const float* p = src + (size_t)off[j] * ld_src;
+        float* o = L.dst + (size_t)list[j] * L.ld_dst + L.col_off[q];
+        for (int c = l * W; c < C; c += W << sh) {
+            if constexpr (VEC) {
+                float4 m = *reinterpret_cast<const float4*>(p + c);
+                for (int r = 1; r < rows; r++) {
+                    const float4 v = *reinterpret_cast<const float4*>(p + r * ld_src + c);
+                    m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+                }
+                *reinterpret_cast<float4*>(o + c) = m;
+            } else {
+                float m = p[c];
+                for (int r = 1; r < rows; r++) m = fmaxf(m, p[r * ld_src + c]);
+                o[c] = m;
+            }
+        }
+    }
+}
+
 static int compact_check(const char* who, int B, int N, int M, int nsample, int sparse_max) {
     PRCNN_REQUIRE(B >= 0 && N > 0 && M >= 0 && nsample > 0, "%s: bad shape B=%d N=%d M=%d nsample=%d", who, B, N, M, nsample);
     PRCNN_REQUIRE(sparse_max >= 1 && sparse_max <= nsample, "%s: sparse_max=%d (1..nsample)", who, sparse_max);
@@ -225,8 +276,9 @@ static int compact_check(const char* who, int B, int N, int M, int nsample, int 
 // Both scales of an MSG level (shared new_xyz, no valid_n): ONE clear of counts[6] ([0..2] scale a, [3..5] scale b, each as
 // prcnn_group_compact's counts) and ONE launch.  lists_a / lists_b: the eight list buffers of prcnn_group_compact in its order
 // (ridx, rnx, slist, soff, scnt, idxn, nxn, listn).
-PRCNN_API int prcnn_group_compact_pair(const int32_t* idx_a, int ns_a, int T_a, const int32_t* idx_b, int ns_b, int T_b, const float* new_xyz,
-                                       int B, int N, int M, void* const* lists_a, void* const* lists_b, int32_t* counts, prcnn_stream_t stream) {
+// (rdst_a / rdst_b: CompactParams::rdst of the two scales, NULL for prcnn_group_compact_pair)
+static int compact_pair(const int32_t* idx_a, int ns_a, int T_a, const int32_t* idx_b, int ns_b, int T_b, const float* new_xyz, int B, int N, int M,
+                        void* const* lists_a, void* const* lists_b, int32_t* rdst_a, int32_t* rdst_b, int32_t* counts, prcnn_stream_t stream) {
     int rc = compact_check("prcnn_group_compact_pair", B, N, M, ns_a, T_a);
     if (rc) return rc;
     rc = compact_check("prcnn_group_compact_pair", B, N, M, ns_b, T_b);
@@ -246,6 +298,7 @@ PRCNN_API int prcnn_group_compact_pair(const int32_t* idx_a, int ns_a, int T_a, 
         P[q].ridx = (int32_t*)L[0]; P[q].rnx = (float*)L[1]; P[q].slist = (int32_t*)L[2]; P[q].soff = (int32_t*)L[3]; P[q].scnt = (int32_t*)L[4];
         P[q].idxn = (int32_t*)L[5]; P[q].nxn = (float*)L[6]; P[q].listn = (int32_t*)L[7];
         P[q].counts = counts + 3 * q; P[q].valid_n = nullptr; P[q].G = B * M; P[q].N = N; P[q].M = M; P[q].ns = ns; P[q].T = T;
+        P[q].rdst = q ? rdst_b : rdst_a;
     }
     const dim3 grid(prcnn_divup(B * M, COMPACT_THREADS), 2);
     const bool vec = ((uintptr_t)idx_a % 16) == 0 && ((uintptr_t)idx_b % 16) == 0;
@@ -253,6 +306,20 @@ PRCNN_API int prcnn_group_compact_pair(const int32_t* idx_a, int ns_a, int T_a, 
     else hipLaunchKernelGGL((group_compact_pair_kernel<0, 0>), grid, dim3(COMPACT_THREADS), 0, s, P[0], P[1]);
     PRCNN_LAUNCH_CHECK("prcnn_group_compact_pair");
     return PRCNN_OK;
+}
+
+PRCNN_API int prcnn_group_compact_pair(const int32_t* idx_a, int ns_a, int T_a, const int32_t* idx_b, int ns_b, int T_b, const float* new_xyz,
+                                       int B, int N, int M, void* const* lists_a, void* const* lists_b, int32_t* counts, prcnn_stream_t stream) {
+    return compact_pair(idx_a, ns_a, T_a, idx_b, ns_b, T_b, new_xyz, B, N, M, lists_a, lists_b, nullptr, nullptr, counts, stream);
+}
+
+// ... and every flat row's destination: rdst_a / rdst_b (B*M*T_a / B*M*T_b device i32), per flat row the group id when the row is its
+// group's only real row -- its result is that group's row of the level output -- and -1 when the group has more rows to pool.
+PRCNN_API int prcnn_group_compact_pair_dst(const int32_t* idx_a, int ns_a, int T_a, const int32_t* idx_b, int ns_b, int T_b, const float* new_xyz,
+                                           int B, int N, int M, void* const* lists_a, void* const* lists_b, int32_t* rdst_a, int32_t* rdst_b,
+                                           int32_t* counts, prcnn_stream_t stream) {
+    PRCNN_REQUIRE(rdst_a && rdst_b, "prcnn_group_compact_pair_dst: null destination list");
+    return compact_pair(idx_a, ns_a, T_a, idx_b, ns_b, T_b, new_xyz, B, N, M, lists_a, lists_b, rdst_a, rdst_b, counts, stream);
 }
 
 // nprob <= 4 problems into one level output dst (ld_dst floats per row).  Problem q: off[q] != null -- prcnn_segmax_scatter of the
@@ -284,6 +351,40 @@ PRCNN_API int prcnn_level_pool(int nprob, const float* const* src, const int* ld
     return PRCNN_OK;
 }
 
+// prcnn_level_pool's arguments, every problem a flat list (off[q] and cnt[q] non-null): only the groups with cnt >= 2 are pooled and
+// stored, the one-row groups' cells are left to whoever stored them (prcnn_mlp_chain_group_multi_dst).
+PRCNN_API int prcnn_level_pool_residual(int nprob, const float* const* src, const int* ld_src, const int32_t* const* list, const int32_t* const* off,
+                                        const int32_t* const* cnt, const int32_t* const* count, const int* max_items, const int* C, const int* col_off,
+                                        float* dst, int ld_dst, prcnn_stream_t stream) {
+    PRCNN_REQUIRE(nprob >= 1 && nprob <= LEVEL_POOL_MAX, "prcnn_level_pool_residual: nprob=%d (1..%d)", nprob, LEVEL_POOL_MAX);
+    PRCNN_REQUIRE(src && ld_src && list && off && cnt && count && max_items && C && col_off, "prcnn_level_pool_residual: null table");
+    ResidualPoolParams L = {};
+    int n = 0;
+    long need = 0;
+    bool vec = ((uintptr_t)dst % 16) == 0 && ld_dst % 4 == 0;
+    for (int q = 0; q < nprob; q++) {
+        PRCNN_REQUIRE(max_items[q] >= 0 && C[q] > 0 && ld_src[q] >= C[q] && ld_dst >= col_off[q] + C[q] && col_off[q] >= 0,
+                      "prcnn_level_pool_residual: bad shape of problem %d", q);
+        if (max_items[q] == 0) continue;
+        PRCNN_REQUIRE(src[q] && list[q] && off[q] && cnt[q] && count[q] && dst, "prcnn_level_pool_residual: null pointer in problem %d", q);
+        L.src[n] = src[q]; L.list[n] = list[q]; L.off[n] = off[q]; L.cnt[n] = cnt[q]; L.count[n] = count[q];
+        L.ld_src[n] = ld_src[q]; L.C[n] = C[q]; L.col_off[n] = col_off[q];
+        vec = vec && ((uintptr_t)src[q] % 16) == 0 && (ld_src[q] | C[q] | col_off[q]) % 4 == 0;
+        int sh = 3;                                            // 8 lanes take up to 32 columns, 64 lanes 256 a pass
+        while (sh < 6 && (4 << sh) < C[q]) sh++;
+        L.lane_shift[n] = sh;
+        need = max(need, (long)prcnn_divup((long)max_items[q], 256 >> sh));
+        n++;
+    }
+    if (n == 0) return PRCNN_OK;
+    L.dst = dst; L.ld_dst = ld_dst;
+    const dim3 grid((unsigned)min(need, (long)(DEDUP_GRID_CAP / 4)), n);
+    if (vec) hipLaunchKernelGGL(residual_pool_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, L);
+    else hipLaunchKernelGGL(residual_pool_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, L);
+    PRCNN_LAUNCH_CHECK("prcnn_level_pool_residual");
+    return PRCNN_OK;
+}
+
 PRCNN_API int prcnn_group_compact(const int32_t* idx, const float* new_xyz, int B, int N, int M, int nsample, int sparse_max,
                                   const int32_t* valid_n, int32_t* ridx, float* rnx, int32_t* slist, int32_t* soff, int32_t* scnt,
                                   int32_t* idxn, float* nxn, int32_t* listn, int32_t* counts, prcnn_stream_t stream) {
@@ -298,7 +399,7 @@ PRCNN_API int prcnn_group_compact(const int32_t* idx, const float* new_xyz, int 
     PRCNN_REQUIRE(sparse_max == nsample || (idxn && nxn && listn), "prcnn_group_compact: null dense-list pointer");
     CompactParams P;
     P.idx = idx; P.new_xyz = new_xyz; P.ridx = ridx; P.rnx = rnx; P.slist = slist; P.soff = soff; P.scnt = scnt;
-    P.idxn = idxn; P.nxn = nxn; P.listn = listn;
+    P.idxn = idxn; P.nxn = nxn; P.listn = listn; P.rdst = nullptr;
     P.counts = counts; P.valid_n = valid_n; P.G = B * M; P.N = N; P.M = M; P.ns = nsample; P.T = sparse_max;
     const dim3 grid(prcnn_divup(P.G, COMPACT_THREADS));
     const bool vec = ((uintptr_t)idx % 16) == 0;

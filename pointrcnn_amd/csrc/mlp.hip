@@ -86,7 +86,19 @@ struct MlpParams {
     // split-bf16 variant (mlp_layer_s_kernel): the pre-split weight image (prcnn_pack_weight_split) and the number of terms (3 / 6)
     const void* wsplit;
     int split_terms;
+    // store by destination (the grouped stacks of an SA level, prcnn_mlp_chain_group_multi_dst): a result row that already IS its
+    // group's row of the level output goes there instead of through `out` and a pooling pass.  All zero / NULL: off.
+    const int32_t* row_dst;  // pool_ns == 0, per flat row: >= 0 -> row of out2; < 0 -> row `row` of out, as without it
+    const int32_t* grp_dst;  // pool_ns > 0: pooled group g goes to row grp_dst[g] of out2
+    float* out2;
+    int ld_out2, col_off2;
 };
+
+// base of result row `row` under MlpParams::row_dst (callers have checked that row_dst is set and the row exists)
+__device__ __forceinline__ float* row_dst_base(const MlpParams& P, long row) {
+    const int d = P.row_dst[row];
+    return d >= 0 ? P.out2 + (long)d * P.ld_out2 + P.col_off2 : P.out + row * P.ld_out + P.col_off;
+}
 
 // With live-row segments the 128-row tile a workgroup works on is NOT blockIdx.x: the live tiles are the first one or two
 // of every segment, i.e. blockIdx.x = 0 mod (seg_rows / 128), and consecutive workgroups go round-robin over the 8 XCDs --
@@ -1328,10 +1340,13 @@ template <int NB>
 __device__ __forceinline__ void chain_store(const ChainParams& C, f32x16 (&acc)[NB], int Nlast, long row, bool valid,
                                             int lane, int h) {
     const MlpParams& P = C.a;
-    const bool vec = ((P.ld_out | P.col_off) % 4 == 0) && aligned16(P.out);
+    // (16-byte stores only where every base in use allows them)
+    const bool remap = P.pool_ns == 0 ? P.row_dst != nullptr : P.grp_dst != nullptr;
+    const bool vec = ((P.ld_out | P.col_off) % 4 == 0) && aligned16(P.out) && (!remap || (((P.ld_out2 | P.col_off2) % 4 == 0) && aligned16(P.out2)));
     if (P.pool_ns == 0) {
         if (!valid) return;
-        float* o = P.out + row * P.ld_out + P.col_off;
+        // the destination is fetched HERE, after the last layer: a lane is a row, the store base a per-lane select
+        float* o = remap ? row_dst_base(P, row) : P.out + row * P.ld_out + P.col_off;
 #pragma unroll
         for (int ob = 0; ob < NB; ob++)
 #pragma unroll
@@ -1355,6 +1370,7 @@ __device__ __forceinline__ void chain_store(const ChainParams& C, f32x16 (&acc)[
     const long group = P.pool_ns == 16 ? (row / 16) : (row / 32);
     const long groups = P.rows / P.pool_ns;
     float* o = P.out + group * P.ld_out + P.col_off;
+    if (remap && writer && valid && group < groups) o = P.out2 + (long)P.grp_dst[group] * P.ld_out2 + P.col_off2;
 #pragma unroll
     for (int ob = 0; ob < NB; ob++)
 #pragma unroll
@@ -2828,7 +2844,29 @@ __device__ __forceinline__ void mlp_stack2_body(const ChainParams& Cin, int blk,
         const int n = nb * 32 + j;
         const bool n_ok = n < Cin.N1;
         const float bias = (Cin.bias1 && n_ok) ? Cin.bias1[n] : 0.f;
-        if (row0 + 32 <= P.rows && nb * 32 + 32 <= Cin.N1) {
+        if (P.row_dst) {
+            // store by destination (MlpParams::row_dst): the 16 rows' destinations first, all in flight together, then the stores
+            // (the pointer is made opaque per pass: the destinations do not depend on the column group, and hoisted out of this loop
+            //  they would stay live across the MFMA loops -- 16 registers that cost stack2<2> its second wave per SIMD)
+            const int32_t* rd = P.row_dst;
+            asm volatile("" : "+s"(rd));
+            int d[16];
+#pragma unroll
+            for (int r = 0; r < 16; r++) d[r] = rd[min(row0 + (r & 3) + 8 * (r >> 2) + 4 * h, P.rows - 1)];
+            auto store_rows = [&](auto guarded) {
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const long g = row0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    float v = acc[0][r] + bias;
+                    v = Cin.relu1 ? fmaxf(v, 0.f) : v;
+                    float* o = d[r] >= 0 ? P.out2 + (long)d[r] * P.ld_out2 + P.col_off2 : P.out + g * P.ld_out + P.col_off;
+                    if (!decltype(guarded)::value || (n_ok && g < P.rows)) o[n] = v;
+                }
+            };
+            // (whole block inside the output: unguarded stores, as below)
+            if (row0 + 32 <= P.rows && nb * 32 + 32 <= Cin.N1) store_rows(std::false_type{});
+            else store_rows(std::true_type{});
+        } else if (row0 + 32 <= P.rows && nb * 32 + 32 <= Cin.N1) {
             // whole block inside the output: unguarded stores, issued back to back (a bounds branch per element makes the compiler
             // open every store with s_waitcnt vmcnt(0) -- the counter includes stores on gfx9: one round trip per store)
             float* o = P.out + (row0 + 4 * h) * P.ld_out + P.col_off + n;
@@ -2854,7 +2892,8 @@ __device__ __forceinline__ void mlp_stack2_body(const ChainParams& Cin, int blk,
     }
 }
 template <int NBW0>
-__global__ __launch_bounds__(256, 1) void mlp_stack2_kernel(const ChainParams Cin) {
+// (two workgroups per CU fit the registers of the instances up to NBW0 = 2, and are asked for so that they keep fitting)
+__global__ __launch_bounds__(256, (NBW0 <= 2 ? 2 : 1)) void mlp_stack2_kernel(const ChainParams Cin) {
     extern __shared__ __attribute__((aligned(16))) float st_lds[];
     mlp_stack2_body<NBW0>(Cin, blockIdx.x, gridDim.x, -1, st_lds);
 }

@@ -51,8 +51,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) voi
 }
 
 // (dynamic LDS: the larger of the problems' tiles; the layer-B split aims at ~256 live workgroups over the WHOLE launch)
+// (waves per SIMD: the <2, 2> instance sits at the 256 registers of two and is held there; the wider one has never fitted them)
 template <int NBWA, int NBWB>
-__global__ __launch_bounds__(256, 1) void stack2_multi_kernel(const MultiParams M) {
+__global__ __launch_bounds__(256, (NBWA <= 2 ? 2 : 1)) void stack2_multi_kernel(const MultiParams M) {
     extern __shared__ __attribute__((aligned(16))) float st_lds[];
     int prob, local, count;
     level_units_find(M.U, blockIdx.x, prob, local, count);
@@ -64,9 +65,12 @@ __global__ __launch_bounds__(256, 1) void stack2_multi_kernel(const MultiParams 
 
 #define STACK_MULTI_GRID_CAP 2048L          // the single launch's cap, for the whole launch
 
-PRCNN_API int prcnn_mlp_chain_group_multi(int nprob, const prcnn_chain_group_problem_t* prob, prcnn_stream_t stream) {
+// dst / out2 / ld_out2 / col_off2: prcnn_mlp_chain_group_multi_dst's arguments (dst == NULL: every problem stores as it always has)
+static int chain_group_multi(int nprob, const prcnn_chain_group_problem_t* prob, const int32_t* const* dst, float* out2, int ld_out2,
+                             const int* col_off2, prcnn_stream_t stream) {
     PRCNN_REQUIRE(nprob >= 1 && nprob <= LEVEL_MAX_PROBLEMS && prob, "prcnn_mlp_chain_group_multi: nprob=%d (1..%d) or a null table", nprob,
                   LEVEL_MAX_PROBLEMS);
+    PRCNN_REQUIRE(!dst || (out2 && col_off2 && ld_out2 > 0), "prcnn_mlp_chain_group_multi_dst: destination lists without an output to store to");
     MultiParams M = {};
     MlpLaunch L[LEVEL_MAX_PROBLEMS];
     int n = 0, family = K_NONE;
@@ -77,6 +81,12 @@ PRCNN_API int prcnn_mlp_chain_group_multi(int nprob, const prcnn_chain_group_pro
         int rc = fill_chain_group(C, a.xyz, a.new_xyz, a.idx, a.feat_cl, a.ld_feat, a.B, a.N, a.M, a.nsample, a.C, a.act_wx, a.act_bias, a.nlayers, a.wpack,
                                   a.bias, a.nout, a.relu, a.out, a.ld_out, a.col_off, a.pool_ns, a.groups_dev);
         if (rc) return rc;
+        if (dst && dst[q]) {
+            PRCNN_REQUIRE(col_off2[q] >= 0 && ld_out2 >= col_off2[q] + a.nout[a.nlayers - 1], "prcnn_mlp_chain_group_multi_dst: ld_out2=%d < col_off2+Nout of problem %d",
+                          ld_out2, q);
+            (a.pool_ns ? C.a.grp_dst : C.a.row_dst) = dst[q];
+            C.a.out2 = out2; C.a.ld_out2 = ld_out2; C.a.col_off2 = col_off2[q];
+        }
         L[n] = MlpLaunch();
         rc = decide_chain(MODE_GROUP, C, L[n]);
         if (rc) return rc;
@@ -147,4 +157,17 @@ PRCNN_API int prcnn_mlp_chain_group_multi(int nprob, const prcnn_chain_group_pro
     STACK_MULTI_TABLE(X)
 #undef X
     return PRCNN_EUNSUPPORTED;
+}
+
+PRCNN_API int prcnn_mlp_chain_group_multi(int nprob, const prcnn_chain_group_problem_t* prob, prcnn_stream_t stream) {
+    return chain_group_multi(nprob, prob, nullptr, nullptr, 0, nullptr, stream);
+}
+
+// ... storing by destination: dst[q] (host array over the problems, entries may be NULL) names where problem q's results go in
+// the level output out2 (ld_out2 floats per row, problem q's columns at col_off2[q]) -- for an un-pooled problem per flat row
+// (MlpParams::row_dst: prcnn_group_compact_pair_dst's rdst), for a pooled one per group (MlpParams::grp_dst: the dense list's
+// listn).  Same kernels, grids and arithmetic; only the address of a stored row changes.
+PRCNN_API int prcnn_mlp_chain_group_multi_dst(int nprob, const prcnn_chain_group_problem_t* prob, const int32_t* const* dst, float* out2,
+                                              int ld_out2, const int* col_off2, prcnn_stream_t stream) {
+    return chain_group_multi(nprob, prob, dst, out2, ld_out2, col_off2, stream);
 }

@@ -35,6 +35,9 @@ STACK_ALL_FLAT_MAX_ROWS = 1 << 20
 # both radii of an MSG level through one split, one grouped-stack and one pool launch (_forward_merged); 0 = A/B switch: today's
 # per-radius launch sequence, same bits
 LEVEL_MERGE = os.environ.get("PRCNN_LEVEL_MERGE", "1") != "0"
+# ... whose stacks store one-row groups and pooled dense groups straight into the level output, leaving the pool launch the groups of
+# two or more flat rows; 0 = A/B switch: every row through the flat buffer and the full pool, same bits
+POOL_DIRECT = os.environ.get("PRCNN_POOL_DIRECT", "1") != "0"
 # largest layer-to-layer intermediate of a padding-free scale's dense list allocated at once (see _run_scale); 0 = never slice (A/B)
 DENSE_CHUNK_BYTES = int(float(os.environ.get("PRCNN_DENSE_CHUNK_MB", "2048")) * 2 ** 20) or (1 << 62)
 TRAIN_FUSED = os.environ.get("PRCNN_TRAIN_FUSED", "1") != "0"          # hand-written training-mode SharedMLP (train_mlp.py)
@@ -342,27 +345,44 @@ class _PointnetSAModuleBase(nn.Module):
             scales.append((ns, src, act, layers, all_flat))
         (ns_a, _, _, _, flat_a), (ns_b, _, _, _, flat_b) = scales
         sps = ops.GroupSplit.pair(idxs[0], ns_a if flat_a else max(1, ns_a // DEDUP_SPARSE_DIV),
-                                  idxs[1], ns_b if flat_b else max(1, ns_b // DEDUP_SPARSE_DIV), new_xyz, N)
+                                  idxs[1], ns_b if flat_b else max(1, ns_b // DEDUP_SPARSE_DIV), new_xyz, N, rdst=POOL_DIRECT)
         xyz_f = xyz.view(1, B * N, 3)
         dst = out_cl.view(B * M, -1)
-        flat, dense, pools, col = [], [], [], 0
         # heaviest first: the wider scale before the narrower one, the flat lists before the dense ones
         order = sorted(range(2), key=lambda i: -sum(l.nout for l in scales[i][3]) * scales[i][0])
         cols = [0, c_outs[0]]
-        for i in order:
-            (ns, src, act, layers, all_flat), sp, col = scales[i], sps[i], cols[i]
-            src_f = None if src is None else _flatten_frames(src)
-            t1 = torch.empty((sp.max_rows, c_outs[i]), dtype=torch.float32, device=xyz.device)      # (both scales' alive together)
-            flat.append(dict(xyz=xyz_f, new_xyz=sp.rnx, idx=sp.ridx, feat_cl=src_f, layers=layers, out=(t1, 0), pool_ns=0, act=act, groups_dev=sp.rows))
-            pools.append((t1, sp, col, "flat"))
-            if not all_flat:
-                tn = torch.empty((sp.G, c_outs[i]), dtype=torch.float32, device=xyz.device)
-                dense.append(dict(xyz=xyz_f, new_xyz=sp.nxn, idx=sp.idxn, feat_cl=src_f, layers=layers, out=(tn, 0), pool_ns=ns, act=act,
-                                  groups_dev=sp.count_dense))
-                pools.append((tn, sp, col, "dense"))
-        if not ops.mlp_chain_group_multi(flat + dense):
-            for pr in flat + dense:                           # (no kernel for this combination: the same launches one by one)
-                ops.mlp_chain_group(**pr)
+
+        def problems(direct):
+            flat, dense, pools = [], [], []
+            for i in order:
+                (ns, src, act, layers, all_flat), sp, col = scales[i], sps[i], cols[i]
+                src_f = None if src is None else _flatten_frames(src)
+                t1 = torch.empty((sp.max_rows, c_outs[i]), dtype=torch.float32, device=xyz.device)      # (both scales' alive together)
+                flat.append(dict(xyz=xyz_f, new_xyz=sp.rnx, idx=sp.ridx, feat_cl=src_f, layers=layers, out=(t1, 0), pool_ns=0, act=act, groups_dev=sp.rows))
+                pools.append((t1, sp, col, "flat"))
+                if not all_flat:
+                    # (direct: the pooled rows go to their groups' rows of dst, no buffer and no scatter of its rows)
+                    tn = None if direct else torch.empty((sp.G, c_outs[i]), dtype=torch.float32, device=xyz.device)
+                    dense.append(dict(xyz=xyz_f, new_xyz=sp.nxn, idx=sp.idxn, feat_cl=src_f, layers=layers, out=(dst, col) if direct else (tn, 0), pool_ns=ns,
+                                      act=act, groups_dev=sp.count_dense))
+                    if direct:
+                        dense[-1]["dst"] = (sp.listn, dst, col)
+                    else:
+                        pools.append((tn, sp, col, "dense"))
+                if direct:
+                    flat[-1]["dst"] = (sp.rdst, dst, col)
+            return flat + dense, pools
+
+        # POOL_DIRECT, store by destination: a flat row that is its group's only one, and a dense group's pooled row, leave the stack's
+        # epilogue for their row of dst; the pool launch is left the groups of two or more flat rows
+        stacks, pools = problems(POOL_DIRECT)
+        if ops.mlp_chain_group_multi(stacks):
+            ops.level_pool(pools, dst, residual=POOL_DIRECT)
+            return True
+        if POOL_DIRECT:
+            stacks, pools = problems(False)
+        for pr in stacks:                                     # (no kernel for this combination: the same launches one by one)
+            ops.mlp_chain_group(**pr)
         ops.level_pool(pools, dst)
         return True
 

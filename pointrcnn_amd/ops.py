@@ -462,7 +462,14 @@ def mlp_chain_group(xyz, new_xyz, idx, feat_cl, layers, out=None, pool_ns=0, act
 def mlp_chain_group_multi(problems):
     """Up to four mlp_chain_group problems -- dicts of its arguments (xyz, new_xyz, idx, feat_cl, layers, out, pool_ns, act,
     groups_dev; out is required) -- in ONE launch, heaviest first.  False, with nothing launched, when the library has no kernel
-    for the combination (PRCNN_EUNSUPPORTED): the caller issues them one by one."""
+    for the combination (PRCNN_EUNSUPPORTED): the caller issues them one by one.
+    A problem that also has the key dst = (int32 device list, out2, col_off2) stores by destination (prcnn_mlp_chain_group_multi_dst;
+    out2, the level's output rows, is one tensor for all of them): an un-pooled problem row r to row list[r] of out2 where
+    list[r] >= 0 and to its own out otherwise, a pooled one group g to row list[g]."""
+    by_dst = [pr["dst"] for pr in problems if pr.get("dst") is not None]
+    out2 = by_dst[0][1] if by_dst else None
+    if any(d[1] is not out2 for d in by_dst):
+        raise RuntimeError("mlp_chain_group_multi: the problems that store by destination must share one output")
     arr = (_cabi.ChainGroupProblem * len(problems))()
     for q, pr in zip(arr, problems):
         layers = pr["layers"]
@@ -476,10 +483,15 @@ def mlp_chain_group_multi(problems):
         q.out, q.groups_dev = _p(buf), _p(pr.get("groups_dev"))
         q.ld_feat, q.B, q.N, q.M, q.nsample, q.C, q.nlayers = ld_feat, B, N, M, ns, C, a.n
         q.ld_out, q.col_off, q.pool_ns = ld_out, col_off, pr.get("pool_ns", 0)
-    rc = _cabi.lib().prcnn_mlp_chain_group_multi(len(problems), arr, _stream())
+    if out2 is None:
+        rc = _cabi.lib().prcnn_mlp_chain_group_multi(len(problems), arr, _stream())
+    else:
+        dst = (ctypes.c_void_p * len(problems))(*[_p(pr["dst"][0]) if pr.get("dst") is not None else None for pr in problems])
+        col2 = (ctypes.c_int * len(problems))(*[int(pr["dst"][2]) if pr.get("dst") is not None else 0 for pr in problems])
+        rc = _cabi.lib().prcnn_mlp_chain_group_multi_dst(len(problems), arr, dst, _p(out2), _row_stride(out2), col2, _stream())
     if rc == _cabi.EUNSUPPORTED:
         return False
-    _cabi.check(rc, "prcnn_mlp_chain_group_multi")
+    _cabi.check(rc, "prcnn_mlp_chain_group_multi_dst" if out2 is not None else "prcnn_mlp_chain_group_multi")
     return True
 
 
@@ -1376,15 +1388,21 @@ class GroupSplit:
         return (ctypes.c_void_p * 8)(*[_p(t) for t in (self.ridx, self.rnx, self.slist, self.soff, self.scnt, self.idxn, self.nxn, self.listn)])
 
     @staticmethod
-    def pair(idx_a, sparse_max_a, idx_b, sparse_max_b, new_xyz, N):
+    def pair(idx_a, sparse_max_a, idx_b, sparse_max_b, new_xyz, N, rdst=False):
         """both scales of an MSG level split by one counter clear and one launch (prcnn_group_compact_pair): two GroupSplits whose
-        counts are the halves of one (6,) tensor"""
+        counts are the halves of one (6,) tensor.  rdst: each also gets .rdst, sized like ridx -- per flat row the group id when the
+        row is its group's only one, else -1 (prcnn_group_compact_pair_dst)"""
         if idx_a.shape[:2] != idx_b.shape[:2]:
             raise RuntimeError("GroupSplit.pair: the two index tensors must share (B, M)")
         counts = torch.empty((6,), dtype=_INT, device=idx_a.device)
         a = GroupSplit(idx_a, new_xyz, N, sparse_max_a, counts=counts[0:3])
         b = GroupSplit(idx_b, new_xyz, N, sparse_max_b, counts=counts[3:6])
         B, M, _ = idx_a.shape
+        if rdst:
+            a.rdst, b.rdst = torch.empty_like(a.ridx), torch.empty_like(b.ridx)
+            _cabi.check(_cabi.lib().prcnn_group_compact_pair_dst(_p(idx_a), a.ns, a.T, _p(idx_b), b.ns, b.T, _p(new_xyz), B, N, M, a._lists(), b._lists(),
+                                                                 _p(a.rdst), _p(b.rdst), _p(counts), _stream()), "prcnn_group_compact_pair_dst")
+            return a, b
         _cabi.check(_cabi.lib().prcnn_group_compact_pair(_p(idx_a), a.ns, a.T, _p(idx_b), b.ns, b.T, _p(new_xyz), B, N, M, a._lists(), b._lists(),
                                                          _p(counts), _stream()), "prcnn_group_compact_pair")
         return a, b
@@ -1404,10 +1422,11 @@ def scatter_rows(src, rows_list, count, dst, col_off):
                                                dst.stride(-2), int(col_off), _stream()), "prcnn_scatter_rows")
 
 
-def level_pool(problems, dst):
+def level_pool(problems, dst, residual=False):
     """The pooling launches of one level as one (prcnn_level_pool).  problems: up to four of (src, sp, col_off, "flat") -- what
     segmax_scatter(src, sp, dst, col_off) does -- or (src, sp, col_off, "dense") -- scatter_rows(src, sp.listn, sp.count_dense, dst,
-    col_off); they must write disjoint cells of dst."""
+    col_off); they must write disjoint cells of dst.  residual: flat problems only, and only their groups of two or more rows are
+    pooled (prcnn_level_pool_residual) -- the one-row groups were stored by destination (mlp_chain_group_multi with dst)."""
     n = len(problems)
     P, I = ctypes.c_void_p * n, ctypes.c_int * n
     src, ld, lst, off, cnt, count, cap, C, col = P(), I(), P(), P(), P(), P(), I(), I(), I()
@@ -1416,7 +1435,8 @@ def level_pool(problems, dst):
         src[q], ld[q], C[q], col[q], cap[q] = _p(s), s.stride(-2), s.shape[-1], int(c0), sp.G
         lst[q], count[q] = (_p(sp.slist), _p(sp.count_sparse)) if flat else (_p(sp.listn), _p(sp.count_dense))
         off[q], cnt[q] = (_p(sp.soff), _p(sp.scnt)) if flat else (None, None)
-    _cabi.check(_cabi.lib().prcnn_level_pool(n, src, ld, lst, off, cnt, count, cap, C, col, _p(dst), dst.stride(-2), _stream()), "prcnn_level_pool")
+    name = "prcnn_level_pool_residual" if residual else "prcnn_level_pool"
+    _cabi.check(getattr(_cabi.lib(), name)(n, src, ld, lst, off, cnt, count, cap, C, col, _p(dst), dst.stride(-2), _stream()), name)
 
 
 # what the wrappers of the passes over raw frames share (the native side of it is csrc/scene_common.h)
