@@ -389,6 +389,27 @@ size_t prcnn_roipool3d_work_bytes(int B, int N);
 int prcnn_roipool3d_ws(const float* xyz, const float* boxes3d, const float* feat, int B, int N, int M, int C, int S, float* pooled,
                        int32_t* empty, void* work, size_t work_bytes, prcnn_stream_t stream);
 
+/* The same two operators, also reporting the selection (pooled and empty are the bytes prcnn_roipool3d / _ws write):
+ *   idx (B,M,S) i32: the frame-local source point, in [0, N), of every pooled row; every row of an empty RoI holds -1;
+ *   distinct (B,M) i32: min(points in the box, S), 0 for an empty RoI.  idx[b,m,s] == idx[b,m,s % distinct] (roipool3d.cpp:171-177). */
+int prcnn_roipool3d_index(const float* xyz, const float* boxes3d, const float* feat, int B, int N, int M, int C, int S,
+                          float* pooled, int32_t* empty, int32_t* idx, int32_t* distinct, prcnn_stream_t stream);
+int prcnn_roipool3d_index_ws(const float* xyz, const float* boxes3d, const float* feat, int B, int N, int M, int C, int S, float* pooled,
+                             int32_t* empty, int32_t* idx, int32_t* distinct, void* work, size_t work_bytes, prcnn_stream_t stream);
+
+/* Gradient of the pooling with respect to the per-point features (the reference's roipool3d has no backward):
+ *   gfeat[b, p, c] = sum over (m, s) with idx[b, m, s] == p of gpooled[b, m, s, col0 + c]
+ * gpooled: (B, M, S) rows of stride ld_g >= col0 + C floats; idx, distinct: as prcnn_roipool3d_index wrote them (entries outside
+ * [0, N) and slots >= distinct of an RoI's first wrap period are ignored); gfeat: (B, N) rows of stride ld_out >= C, columns
+ * [0, C) written.  work: prcnn_roipool3d_grad_work_bytes(B, N, M, S) device bytes (0: outside the domain), 4-byte aligned.
+ * A gather: no float atomics, no memset; every gfeat element is written exactly once (a point no row refers to gets 0); a point's
+ * addends are added in float32 from zero in ascending (m, s); two calls give the same bytes; rows of empty RoIs are never read.
+ * Domain: 1 <= C <= 256, N <= 65536, S <= 512, M S < 2^31 -- PRCNN_EUNSUPPORTED beyond it, PRCNN_EINVAL for a bad shape, stride,
+ * null pointer or workspace; nothing is launched or written then. */
+size_t prcnn_roipool3d_grad_work_bytes(int B, int N, int M, int S);
+int prcnn_roipool3d_grad(const float* gpooled, int64_t ld_g, int col0, const int32_t* idx, const int32_t* distinct, int B, int N, int M,
+                         int S, int C, float* gfeat, int ld_out, void* work, size_t work_bytes, prcnn_stream_t stream);
+
 /* point-in-box flags on the device: flags (M,N) i32 (device twin of roipool3d.cpp:97-125) */
 int prcnn_pts_in_boxes3d(const float* pts, const float* boxes3d, int N, int M, int32_t* flags, prcnn_stream_t stream);
 

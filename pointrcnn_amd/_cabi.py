@@ -114,6 +114,10 @@ SIGNATURES = {
     "prcnn_roipool3d": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "prcnn_roipool3d_work_bytes": (_Z, [_I, _I]),
     "prcnn_roipool3d_ws": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "prcnn_roipool3d_index": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "prcnn_roipool3d_index_ws": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    "prcnn_roipool3d_grad_work_bytes": (_Z, [_I, _I, _I, _I]),
+    "prcnn_roipool3d_grad": (_I, [_P, _L, _I, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _Z, _P]),
     "prcnn_pts_in_boxes3d": (_I, [_P, _P, _I, _I, _P, _P]),
     "prcnn_boxes_overlap_bev": (_I, [_P, _I, _P, _I, _P, _P]),
     "prcnn_boxes_iou_bev": (_I, [_P, _I, _P, _I, _P, _P]),

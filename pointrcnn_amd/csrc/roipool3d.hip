@@ -289,12 +289,14 @@ __device__ __forceinline__ int rp_select_bins(const BoxConst& box, const RpBinsM
     return min(total, S);
 }
 
-template <bool BINS>
-__global__ __launch_bounds__(RP_THREADS) void roipool3d_kernel(const float* __restrict__ xyz,
-                                                               const float* __restrict__ boxes3d,
-                                                               const float* __restrict__ feat, int N, int M, int C,
-                                                               int S, float* __restrict__ pooled,
-                                                               int32_t* __restrict__ empty, const char* __restrict__ bins) {
+// The body of both pooling kernels.  IDX: also report the selection -- idx_out (B, M, S): the frame-local source point of every
+// pooled row (slot s copies slot s % total, so idx_out[s] == sel[s % total]; -1 in every row of an empty RoI), distinct_out
+// (B, M): total.  IDX is a compile-time flag: roipool3d_kernel below instantiates the body without it and is the kernel it was.
+template <bool BINS, bool IDX>
+__device__ __forceinline__ void rp_pool_body(const float* __restrict__ xyz, const float* __restrict__ boxes3d,
+                                             const float* __restrict__ feat, int N, int M, int C, int S, float* __restrict__ pooled,
+                                             int32_t* __restrict__ empty, const char* __restrict__ bins,
+                                             int32_t* __restrict__ idx_out, int32_t* __restrict__ distinct_out) {
     extern __shared__ int32_t lds[];          // linear: RP_WAVES lists of S indices + the merged list; bins: S indices + the bitmap
     __shared__ BoxConst sbox;
     __shared__ int wcnt[RP_WAVES];
@@ -312,6 +314,17 @@ __global__ __launch_bounds__(RP_THREADS) void roipool3d_kernel(const float* __re
     const int W = 3 + C;
     float* __restrict__ o = pooled + ((size_t)b * M + m) * S * W;
     if (tid == 0) empty[(size_t)b * M + m] = total == 0 ? 1 : 0;
+    if (IDX) {
+        int32_t* __restrict__ io = idx_out + ((size_t)b * M + m) * S;
+        if (tid == 0) distinct_out[(size_t)b * M + m] = total;
+        int r = total ? tid % total : 0;                       // tid % total, stepped without a division per slot
+        const int step = total ? RP_THREADS % total : 0;
+        for (int s2 = tid; s2 < S; s2 += RP_THREADS) {
+            io[s2] = total ? sel[r] : -1;
+            r += step;
+            if (r >= total) r -= total;
+        }
+    }
     if (total == 0) {
         for (size_t e = tid; e < (size_t)S * W; e += RP_THREADS) o[e] = 0.f;
         return;
@@ -353,6 +366,25 @@ __global__ __launch_bounds__(RP_THREADS) void roipool3d_kernel(const float* __re
             }
         }
     }
+}
+
+template <bool BINS>
+__global__ __launch_bounds__(RP_THREADS) void roipool3d_kernel(const float* __restrict__ xyz,
+                                                               const float* __restrict__ boxes3d,
+                                                               const float* __restrict__ feat, int N, int M, int C,
+                                                               int S, float* __restrict__ pooled,
+                                                               int32_t* __restrict__ empty, const char* __restrict__ bins) {
+    rp_pool_body<BINS, false>(xyz, boxes3d, feat, N, M, C, S, pooled, empty, bins, nullptr, nullptr);
+}
+
+template <bool BINS>
+__global__ __launch_bounds__(RP_THREADS) void roipool3d_index_kernel(const float* __restrict__ xyz,
+                                                                     const float* __restrict__ boxes3d,
+                                                                     const float* __restrict__ feat, int N, int M, int C,
+                                                                     int S, float* __restrict__ pooled,
+                                                                     int32_t* __restrict__ empty, const char* __restrict__ bins,
+                                                                     int32_t* __restrict__ idx_out, int32_t* __restrict__ distinct_out) {
+    rp_pool_body<BINS, true>(xyz, boxes3d, feat, N, M, C, S, pooled, empty, bins, idx_out, distinct_out);
 }
 
 // ---- fused RCNN input builder (lib/net/rcnn_net.py:127-154) -------------------------------
@@ -514,6 +546,225 @@ PRCNN_API int prcnn_roipool3d_ws(const float* xyz, const float* boxes3d, const f
 PRCNN_API int prcnn_roipool3d(const float* xyz, const float* boxes3d, const float* feat, int B, int N, int M, int C,
                               int S, float* pooled, int32_t* empty, prcnn_stream_t stream) {
     return prcnn_roipool3d_ws(xyz, boxes3d, feat, B, N, M, C, S, pooled, empty, nullptr, 0, stream);
+}
+
+PRCNN_API int prcnn_roipool3d_index_ws(const float* xyz, const float* boxes3d, const float* feat, int B, int N, int M, int C, int S,
+                                       float* pooled, int32_t* empty, int32_t* idx, int32_t* distinct, void* work, size_t work_bytes,
+                                       prcnn_stream_t stream) {
+    const char* op = "prcnn_roipool3d_index";
+    PRCNN_REQUIRE(B >= 0 && N > 0 && M >= 0 && C >= 0 && S > 0, "%s: bad shape B=%d N=%d M=%d C=%d S=%d", op, B, N, M, C, S);
+    if (B == 0 || M == 0) return PRCNN_OK;
+    PRCNN_REQUIRE(xyz && boxes3d && pooled && empty && idx && distinct && (C == 0 || feat), "%s: null pointer", op);
+    const bool bins = rp_use_bins(work, work_bytes, B, N);
+    const size_t lds_bytes = rp_lds_bytes(bins, N, S);
+    PRCNN_REQUIRE(lds_bytes <= 60 * 1024, "%s: sampled_pt_num %d too large for the LDS index lists", op, S);
+    hipStream_t s = (hipStream_t)stream;
+    if (bins) {
+        if (int rc = rp_bins_build(xyz, B, N, work, s)) return rc;
+        hipLaunchKernelGGL(roipool3d_index_kernel<true>, dim3(M, B), dim3(RP_THREADS), lds_bytes, s, xyz, boxes3d, feat, N, M, C, S, pooled,
+                           empty, (const char*)work, idx, distinct);
+    } else {
+        hipLaunchKernelGGL(roipool3d_index_kernel<false>, dim3(M, B), dim3(RP_THREADS), lds_bytes, s, xyz, boxes3d, feat, N, M, C, S, pooled,
+                           empty, (const char*)nullptr, idx, distinct);
+    }
+    PRCNN_LAUNCH_CHECK(op);
+    return PRCNN_OK;
+}
+
+PRCNN_API int prcnn_roipool3d_index(const float* xyz, const float* boxes3d, const float* feat, int B, int N, int M, int C, int S,
+                                    float* pooled, int32_t* empty, int32_t* idx, int32_t* distinct, prcnn_stream_t stream) {
+    return prcnn_roipool3d_index_ws(xyz, boxes3d, feat, B, N, M, C, S, pooled, empty, idx, distinct, nullptr, 0, stream);
+}
+
+// =====================================================================================================
+// Gradient of the pooling with respect to the per-point features, as a GATHER (no float atomics, no memset; the rule
+// interp_csr_gather_kernel set):   gfeat[b, p, c] = sum over (m, s) with idx[b, m, s] == p of gpooled[b, m, s, col0 + c].
+//
+// The wrap structure bounds the skew.  Inside one RoI the selected points are distinct, and slot s copies slot s % distinct, so
+// the point in slot j < distinct is referenced by exactly the slots j, j + distinct, j + 2 distinct, ...: ONE (m, j) reference
+// stands for all of them, and a point has at most M references however few points an RoI holds (distinct == 1: 512 slots, one
+// reference).
+//
+//  build:  per frame, the references (m, j < distinct[m]) bucketed by point -- a counting sort with the counters in LDS.  A
+//          workgroup owns RPG_CHUNK consecutive points of a frame and reads all of the frame's references (B M S ints at most:
+//          small next to the rows); references to lower points are only counted, which gives the chunk its base in the frame's
+//          entry list without a second launch.  The fill walks the RoIs in ascending m with a barrier between two RoIs: inside
+//          one RoI no two slots refer to the same point, so every bucket ends up in ascending m whatever the wave scheduling
+//          -- no sort in the gather, any M.  (The next RoI's indices are requested before the barrier.)
+//  gather: one wave per point, lanes across channels (16-byte pieces when rows, column offset and pointers allow it, single
+//          floats otherwise), references in bucket order == ascending m, the slots of each in ascending s, float32 additions
+//          from zero in that order.  Every gfeat element is written once; a point nobody refers to gets its zero from here.
+// Entries are m * S + j: the row of the first slot in the frame's (M S)-row block; j and m come back by one division.
+// =====================================================================================================
+#define RPG_THREADS 1024
+#define RPG_CHUNK 8192
+#define RPG_MAX_N 65536
+#define RPG_MAX_S 512
+#define RPG_MAX_C 256
+
+__global__ __launch_bounds__(RPG_THREADS) void roipool3d_grad_build_kernel(const int32_t* __restrict__ idx, const int32_t* __restrict__ distinct,
+                                                                           int N, int M, int S, int32_t* __restrict__ off_all,
+                                                                           int32_t* __restrict__ ent_all) {
+    __shared__ int cnt[RPG_CHUNK];
+    __shared__ int wsum[RPG_THREADS / 64];
+    __shared__ int wbelow[RPG_THREADS / 64];
+    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lo = blockIdx.x * RPG_CHUNK, hi = min(N, lo + RPG_CHUNK), span = hi - lo;
+    const int MS = M * S;
+    const int32_t* __restrict__ ib = idx + (size_t)b * MS;
+    const int32_t* __restrict__ db = distinct + (size_t)b * M;
+    int32_t* __restrict__ off = off_all + (size_t)b * (N + 1);
+    int32_t* __restrict__ ent = ent_all + (size_t)b * MS;
+    for (int i = tid; i < RPG_CHUNK; i += RPG_THREADS) cnt[i] = 0;
+    __syncthreads();
+    // count: this chunk's references per point, and the references to lower points
+    int below = 0;
+    for (int q = tid; q < MS; q += RPG_THREADS) {
+        const int m = q / S, j = q - m * S;
+        const int d = min(max(db[m], 0), S);
+        if (j < d) {
+            const int p = ib[q];
+            if (p >= 0 && p < lo) below++;
+            else if (p >= lo && p < hi) atomicAdd(&cnt[p - lo], 1);
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) below += __shfl_xor(below, o);
+    if (lane == 0) wbelow[wave] = below;
+    __syncthreads();
+    // exclusive scan over the chunk's counters: RPG_CHUNK / RPG_THREADS consecutive counters per thread
+    constexpr int per = RPG_CHUNK / RPG_THREADS;
+    const int j0 = tid * per;
+    int tsum = 0;
+#pragma unroll
+    for (int u = 0; u < per; u++) tsum += cnt[j0 + u];
+    int incl = tsum;
+    for (int o = 1; o < 64; o <<= 1) { int v = __shfl_up(incl, o); if (lane >= o) incl += v; }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    int run = incl - tsum;                                     // position in the frame's entry list
+    for (int wv = 0; wv < RPG_THREADS / 64; wv++) { run += wbelow[wv]; if (wv < wave) run += wsum[wv]; }
+#pragma unroll
+    for (int u = 0; u < per; u++) {
+        const int c = cnt[j0 + u];
+        if (j0 + u < span) off[lo + j0 + u] = run;
+        cnt[j0 + u] = run;
+        run += c;
+    }
+    if (hi == N && tid == RPG_THREADS - 1) off[N] = run;       // counters past the span are zero: run is the chunk's end
+    __syncthreads();
+    // fill: RoI by RoI (ascending m), slot j = tid (S <= RPG_THREADS: host-checked)
+    int d_next = 0, p_next = -1;
+    if (M > 0) { d_next = min(max(db[0], 0), S); if (tid < d_next) p_next = ib[tid]; }
+    for (int m = 0; m < M; m++) {
+        const int d = d_next, p = p_next;
+        if (m + 1 < M) {
+            d_next = min(max(db[m + 1], 0), S);
+            p_next = tid < d_next ? ib[(m + 1) * S + tid] : -1;
+        }
+        if (tid < d && p >= lo && p < hi) {
+            const int pos = atomicAdd(&cnt[p - lo], 1);
+            ent[pos] = m * S + tid;
+        }
+        __syncthreads();
+    }
+}
+
+__device__ __forceinline__ void rpg_load(float4& v, const float* p) { v = *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ void rpg_load(float& v, const float* p) { v = *p; }
+__device__ __forceinline__ void rpg_add(float4& a, const float4& v) {
+    a.x = __fadd_rn(a.x, v.x); a.y = __fadd_rn(a.y, v.y); a.z = __fadd_rn(a.z, v.z); a.w = __fadd_rn(a.w, v.w);
+}
+__device__ __forceinline__ void rpg_add(float& a, const float& v) { a = __fadd_rn(a, v); }
+__device__ __forceinline__ void rpg_zero(float4& a) { a = make_float4(0.f, 0.f, 0.f, 0.f); }
+__device__ __forceinline__ void rpg_zero(float& a) { a = 0.f; }
+__device__ __forceinline__ void rpg_store(float* p, const float4& a) { *reinterpret_cast<float4*>(p) = a; }
+__device__ __forceinline__ void rpg_store(float* p, const float& a) { *p = a; }
+
+// one wave per point; V = float4 (lanes = channel quads) or float (lanes = channels)
+template <typename V>
+__global__ __launch_bounds__(256) void roipool3d_grad_gather_kernel(const float* __restrict__ g, long ld_g, int col0,
+                                                                    const int32_t* __restrict__ off_all, const int32_t* __restrict__ ent_all,
+                                                                    const int32_t* __restrict__ distinct, long total, int N, int M, int S,
+                                                                    int C, float* __restrict__ gfeat, int ld_out) {
+    constexpr int W = sizeof(V) / 4;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long gj = (long)blockIdx.x * 4 + wave;               // b * N + p
+    if (gj >= total) return;
+    const int b = (int)(gj / N), p = (int)(gj - (long)b * N);
+    const int MS = M * S;
+    const int32_t* __restrict__ off = off_all + (size_t)b * (N + 1);
+    const int s0 = min(max(off[p], 0), MS), len = min(max(off[p + 1], s0), MS) - s0;
+    const int32_t* __restrict__ ent = ent_all + (size_t)b * MS + s0;
+    const int32_t* __restrict__ db = distinct + (size_t)b * M;
+    const float* __restrict__ gb = g + (size_t)b * MS * ld_g + col0;
+    float* __restrict__ o = gfeat + ((size_t)b * N + p) * ld_out;
+    for (int c = lane * W; c < C; c += 64 * W) {
+        V acc;
+        rpg_zero(acc);
+        for (int k0 = 0; k0 < len; k0 += 4) {                  // four references' first rows requested before the first is added
+            int e[4], d[4];
+            V v[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) e[u] = min(max(ent[min(k0 + u, len - 1)], 0), MS - 1);
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                d[u] = min(max(db[e[u] / S], 1), S);
+                rpg_load(v[u], gb + (size_t)e[u] * ld_g + c);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                if (k0 + u >= len) break;
+                rpg_add(acc, v[u]);
+                const int j = e[u] % S, dd = d[u];
+                const float* __restrict__ row = gb + (size_t)(e[u] - j) * ld_g + c;
+                for (int s = j + dd; s < S; s += 4 * dd) {     // the wrap copies of slot j, four rows in flight, added in ascending s
+                    V w[4];
+#pragma unroll
+                    for (int t = 0; t < 4; t++) rpg_load(w[t], row + (size_t)min(s + t * dd, S - 1) * ld_g);
+#pragma unroll
+                    for (int t = 0; t < 4; t++)
+                        if (s + t * dd < S) rpg_add(acc, w[t]);
+                }
+            }
+        }
+        rpg_store(o + c, acc);
+    }
+}
+
+PRCNN_API size_t prcnn_roipool3d_grad_work_bytes(int B, int N, int M, int S) {
+    if (B <= 0 || N <= 0 || M < 0 || S <= 0 || N > RPG_MAX_N || S > RPG_MAX_S || (long)M * S >= (1L << 31)) return 0;
+    return ((size_t)B * ((size_t)N + 1) + (size_t)B * (size_t)M * S) * sizeof(int32_t);
+}
+
+PRCNN_API int prcnn_roipool3d_grad(const float* gpooled, int64_t ld_g, int col0, const int32_t* idx, const int32_t* distinct, int B, int N, int M,
+                                   int S, int C, float* gfeat, int ld_out, void* work, size_t work_bytes, prcnn_stream_t stream) {
+    const char* op = "prcnn_roipool3d_grad";
+    PRCNN_REQUIRE(B >= 0 && N >= 0 && M >= 0 && S > 0 && C >= 1 && col0 >= 0, "%s: bad shape B=%d N=%d M=%d S=%d C=%d col0=%d", op, B, N, M, S,
+                  C, col0);
+    PRCNN_REQUIRE(ld_g >= (long)col0 + C && ld_out >= C, "%s: row strides smaller than the rows (ld_g=%ld col0=%d C=%d ld_out=%d)", op,
+                  (long)ld_g, col0, C, ld_out);
+    if (C > RPG_MAX_C || N > RPG_MAX_N || S > RPG_MAX_S || (long)M * S >= (1L << 31))
+        return prcnn_fail(PRCNN_EUNSUPPORTED, "%s: outside C <= %d, N <= %d, S <= %d, M S < 2^31 (C=%d N=%d S=%d M=%d)", op, RPG_MAX_C,
+                          RPG_MAX_N, RPG_MAX_S, C, N, S, M);
+    if (B == 0 || N == 0) return PRCNN_OK;
+    PRCNN_REQUIRE(gfeat && work && (M == 0 || (gpooled && idx && distinct)), "%s: null pointer", op);
+    PRCNN_REQUIRE(work_bytes >= prcnn_roipool3d_grad_work_bytes(B, N, M, S), "%s: workspace of %zu bytes, %zu needed", op, work_bytes,
+                  prcnn_roipool3d_grad_work_bytes(B, N, M, S));
+    PRCNN_REQUIRE(((uintptr_t)work & 3) == 0, "%s: workspace not 4-byte aligned", op);
+    int32_t* off = (int32_t*)work;
+    int32_t* ent = off + (size_t)B * ((size_t)N + 1);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(roipool3d_grad_build_kernel, dim3(prcnn_divup(N, RPG_CHUNK), B), dim3(RPG_THREADS), 0, s, idx, distinct, N, M, S, off, ent);
+    const long total = (long)B * N;
+    const bool v4 = C % 4 == 0 && col0 % 4 == 0 && ld_g % 4 == 0 && ld_out % 4 == 0 && ((uintptr_t)gpooled & 15) == 0 && ((uintptr_t)gfeat & 15) == 0;
+    if (v4)
+        hipLaunchKernelGGL(roipool3d_grad_gather_kernel<float4>, dim3(prcnn_divup(total, 4)), dim3(256), 0, s, gpooled, (long)ld_g, col0,
+                           (const int32_t*)off, (const int32_t*)ent, distinct, total, N, M, S, C, gfeat, ld_out);
+    else
+        hipLaunchKernelGGL(roipool3d_grad_gather_kernel<float>, dim3(prcnn_divup(total, 4)), dim3(256), 0, s, gpooled, (long)ld_g, col0,
+                           (const int32_t*)off, (const int32_t*)ent, distinct, total, N, M, S, C, gfeat, ld_out);
+    PRCNN_LAUNCH_CHECK(op);
+    return PRCNN_OK;
 }
 
 PRCNN_API int prcnn_pts_in_boxes3d(const float* pts, const float* boxes3d, int N, int M, int32_t* flags,

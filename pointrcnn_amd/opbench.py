@@ -563,6 +563,90 @@ def rcnn_loss_rows(dev, R=256, rounds=5):
                           "median_us": round(t[len(t) // 2] * 1e6, 1), "min_us": round(t[0] * 1e6, 1), "max_us": round(t[-1] * 1e6, 1)}), flush=True)
 
 
+def _joint_batch(dev, B=4, N=16384, G=10):
+    """the RCNN training tests' scene (uniform clouds, G car-sized ground-truth boxes on drawn points) with synthetic RPN labels"""
+    from . import train_functions as tf
+    pts = rpn.synthetic_clouds(B, N, seed0=300).to(dev)
+    g = torch.Generator().manual_seed(5)
+    pick = torch.randint(0, N, (B, G), generator=g).to(dev)
+    ctr = torch.gather(pts, 1, pick[..., None].expand(-1, -1, 3))
+    hwl = torch.tensor([1.56, 1.6, 3.9], device=dev)
+    ry = (torch.rand((B, G, 1), generator=g) * 6.283 - 3.1416).to(dev)
+    gt = torch.cat([ctr[..., 0:1], ctr[..., 1:2] + hwl[0] / 2, ctr[..., 2:3], hwl.expand(B, G, 3), ry], 2).contiguous()
+    cls, reg = tf.synthetic_rpn_labels(pts, gt, ops.pts_in_boxes3d)
+    return {"pts_input": pts, "gt_boxes3d": gt, "rpn_cls_label": cls, "rpn_reg_label": reg}
+
+
+def roipool_grad_rows(dev, B=4, N=16384, M=64, S=512, C=128, rounds=5):
+    """`roipool3d grad`: the pooling's gradient with respect to the per-point features at the RCNN step's shape, on RoIs a
+    ProposalTargetLayer samples from the training tests' scene (its own pooling call's idx / distinct).  The device route
+    (ops.roipool3d_grad: list build + gather, no atomics) against the composed torch route on the same idx (index_add_ into zeros:
+    float atomics), alternated in one process; per route the median, minimum and maximum over `rounds` windows of 20 calls.  gpooled is
+    the step's layout: (B*M, S, 133) rows, the C feature columns behind 5 others.  Floor: every gpooled feature column read once, every
+    gfeat element written once."""
+    from .proposal_target_layer import ProposalTargetLayer
+    from .rcnn import RCNNConfig
+    batch = _joint_batch(dev, B, N)
+    g = torch.Generator().manual_seed(3)
+    layer = ProposalTargetLayer(RCNNConfig, seed=21, pool_grad=True)
+    rois = (batch["gt_boxes3d"].repeat(1, 30, 1) + (torch.randn((B, 300, 7), generator=g) * 0.25).to(dev)).contiguous()      # jittered proposals
+    feat = torch.randn((B, N, C), generator=g).to(dev)
+    with torch.no_grad():
+        out = layer({"roi_boxes3d": rois, "gt_boxes3d": batch["gt_boxes3d"], "rpn_xyz": batch["pts_input"], "rpn_features": feat,
+                     "seg_mask": torch.zeros((B, N), device=dev), "pts_depth": torch.norm(batch["pts_input"], p=2, dim=2)})
+    idx, distinct = out["pool_idx"], out["pool_distinct"]
+    assert tuple(idx.shape) == (B, M, S)
+    gp = torch.randn((B * M, S, 5 + C), generator=g).to(dev)
+    flat = (idx.long() + (torch.arange(B, device=dev) * N).view(B, 1, 1)).reshape(-1)
+    live = (idx >= 0).reshape(-1)
+    flat_live, rows_live = flat[live].contiguous(), live.nonzero().squeeze(1)
+
+    def device():
+        return ops.roipool3d_grad(gp, idx, distinct, N, C, col0=5)
+
+    def composed():
+        return torch.zeros((B * N, C), device=dev).index_add_(0, flat_live, gp.view(-1, 5 + C)[rows_live, 5:]).view(B, N, C)
+    a, b = device(), composed()
+    err = (a - b).abs().max().item()
+    times = {"device": [], "composed": []}
+    for _ in range(rounds):
+        for name, fn in (("device", device), ("composed", composed)):
+            times[name].append(timeit(fn))
+    floor = 4 * (int(live.sum()) * C + B * N * C)
+    refs = torch.bincount(flat_live, minlength=B * N)
+    for name in ("device", "composed"):
+        t = sorted(times[name])
+        print(json.dumps({"op": "roipool3d grad (%s)" % name,
+                          "shape": "B%d N%d M%d S%d C%d, %d empty RoIs, distinct median %d, refs per point max %d"
+                                   % (B, N, M, S, C, int((distinct == 0).sum()), int(distinct.float().median()), int(refs.max())),
+                          "median_us": round(t[len(t) // 2] * 1e6, 1), "min_us": round(t[0] * 1e6, 1), "max_us": round(t[-1] * 1e6, 1),
+                          "traffic_floor_MB": round(floor / 1e6, 1), "floor_GBps_at_median": round(floor / t[len(t) // 2] / 1e9, 1),
+                          "max_abs_diff_between_routes": err}), flush=True)
+
+
+def joint_step_rows(dev, B=4, rounds=5, iters=5):
+    """`joint step`: train_functions.JointTrainer.step at bs4 on the training tests' scene, pool_grad off against on (two trainers on
+    copies of one model), alternated in one process; per setting the median, minimum and maximum over `rounds` windows of `iters`
+    steps.  bench.py has no workload for this step: these rows are its only timing."""
+    import copy
+    from . import point_rcnn, train_functions as tf
+    torch.manual_seed(11)
+    model = point_rcnn.PointRCNN(mode="TRAIN", rpn_fixed=False).to(dev)
+    batch = _joint_batch(dev, B)
+    trainers = {flag: tf.JointTrainer(copy.deepcopy(model), pool_grad=flag) for flag in (False, True)}
+    times = {False: [], True: []}
+    for flag in (False, True):
+        for _ in range(3):
+            trainers[flag].step(batch, next_batch=batch)
+    for _ in range(rounds):
+        for flag in (False, True):
+            times[flag].append(timeit(lambda: trainers[flag].step(batch, next_batch=batch), iters, 1))
+    for flag in (False, True):
+        t = sorted(times[flag])
+        print(json.dumps({"op": "joint step (pool_grad %s)" % ("on" if flag else "off"), "shape": "bs%d N16384, 64 RoIs per frame" % B,
+                          "median_ms": round(t[len(t) // 2] * 1e3, 3), "min_ms": round(t[0] * 1e3, 3), "max_ms": round(t[-1] * 1e3, 3)}), flush=True)
+
+
 def eval_stats_rows(dev, B=32, shapes=((100, 12), (512, 24)), N=16384, rounds=5):
     """`eval_stats`: the per-batch statistics of eval_one_epoch_joint (tools/eval_rcnn.py:539-573) at bs32 -- recall of the ground truth
     by the RoIs and the refined boxes at five thresholds, the segmentation IoU, the detection count.  Composed route: the reference's
@@ -745,6 +829,12 @@ def main():
         return
     if args.only == "eval_stats":
         eval_stats_rows(dev)
+        return
+    if args.only == "roipool_grad":
+        roipool_grad_rows(dev)
+        return
+    if args.only == "joint_step":
+        joint_step_rows(dev)
         return
     if args.only == "optimizer":
         optimizer_rows(dev)

@@ -605,18 +605,64 @@ def _roipool_work(B, N, M, dev):
     return torch.empty((nbytes,), dtype=torch.uint8, device=dev), nbytes
 
 
-def roipool3d(xyz, boxes3d_enlarged, pts_feature, sampled_pt_num):
+def roipool3d(xyz, boxes3d_enlarged, pts_feature, sampled_pt_num, want_index=False):
     """xyz (B,N,3), boxes (B,M,7) already enlarged, pts_feature (B,N,C) -> pooled (B,M,S,3+C), empty (B,M) i32
-    [roipool3d_cuda.forward, lib/utils/roipool3d/src/roipool3d.cpp:48-79]"""
+    [roipool3d_cuda.forward, lib/utils/roipool3d/src/roipool3d.cpp:48-79]
+    want_index: also -> idx (B,M,S) i32, the frame-local source point of every pooled row (-1 in the rows of an empty RoI), and
+    distinct (B,M) i32 = min(points in the box, S) (prcnn_roipool3d_index; pooled and empty are the same bytes)"""
     _chk(xyz, "xyz", ndim=3); _chk(boxes3d_enlarged, "boxes3d", ndim=3); _chk(pts_feature, "pts_feature", ndim=3)
     B, N, _ = xyz.shape
     M, C = boxes3d_enlarged.shape[1], pts_feature.shape[2]
     pooled = torch.empty((B, M, sampled_pt_num, 3 + C), dtype=_F32, device=xyz.device)
     empty = torch.empty((B, M), dtype=_INT, device=xyz.device)
     work, nbytes = _roipool_work(B, N, M, xyz.device)
+    if want_index:
+        idx = torch.empty((B, M, sampled_pt_num), dtype=_INT, device=xyz.device)
+        distinct = torch.empty((B, M), dtype=_INT, device=xyz.device)
+        _cabi.check(_cabi.lib().prcnn_roipool3d_index_ws(_p(xyz), _p(boxes3d_enlarged), _p(pts_feature), B, N, M, C, sampled_pt_num,
+                                                         _p(pooled), _p(empty), _p(idx), _p(distinct), _p(work), nbytes, _stream()),
+                    "prcnn_roipool3d_index")
+        return pooled, empty, idx, distinct
     _cabi.check(_cabi.lib().prcnn_roipool3d_ws(_p(xyz), _p(boxes3d_enlarged), _p(pts_feature), B, N, M, C, sampled_pt_num,
                                                _p(pooled), _p(empty), _p(work), nbytes, _stream()), "prcnn_roipool3d")
     return pooled, empty
+
+
+def roipool3d_grad(gpooled, idx, distinct, N, C=None, col0=0, out=None):
+    """The pooling's gradient with respect to the per-point features (prcnn_roipool3d_grad; the reference has none):
+    gfeat[b, p, c] = sum over (m, s) with idx[b, m, s] == p of gpooled[b, m, s, col0 + c], float32, ascending (m, s), no atomics.
+    gpooled: (B, M, S, W) or (B * M, S, W) fp32 rows of unit last stride and one row stride (a column slice of a wider tensor is
+    taken as it is); idx (B,M,S) / distinct (B,M) i32 from roipool3d(..., want_index=True); C: columns summed (default W - col0).
+    out: (B, N, >= C) rows to write the C columns into (default: a fresh (B, N, C) tensor) -> gfeat"""
+    _chk(idx, "idx", _INT, 3); _chk(distinct, "distinct", _INT, 2)
+    B, M, S = idx.shape
+    if tuple(distinct.shape) != (B, M):
+        raise ValueError("roipool3d_grad: distinct must be (B, M) = %s, got %s" % ((B, M), tuple(distinct.shape)))
+    if not (isinstance(gpooled, torch.Tensor) and gpooled.is_cuda and gpooled.dtype == _F32):
+        raise RuntimeError("roipool3d_grad: gpooled must be a fp32 device tensor")
+    g = gpooled.view(B, M, S, gpooled.shape[-1]) if gpooled.dim() == 3 and gpooled.shape[0] == B * M and gpooled.shape[1] == S else gpooled
+    if g.dim() != 4 or tuple(g.shape[:3]) != (B, M, S):
+        raise ValueError("roipool3d_grad: gpooled must be (B, M, S, W) or (B * M, S, W) with idx (B, M, S) = %s, got %s"
+                         % ((B, M, S), tuple(gpooled.shape)))
+    W = g.shape[3]
+    C = W - col0 if C is None else int(C)
+    ld_g = g.stride(2) if S > 1 else (g.stride(1) if M > 1 else max(g.stride(0), W))
+    if B * M * S > 0 and (g.stride(3) != 1 or (M > 1 and g.stride(1) != S * ld_g) or (B > 1 and g.stride(0) != M * S * ld_g)):
+        raise RuntimeError("roipool3d_grad: gpooled rows must have unit last stride and one row stride")
+    if col0 < 0 or C < 1 or col0 + C > W:
+        raise ValueError("roipool3d_grad: columns [%d, %d) outside the %d of gpooled" % (col0, col0 + C, W))
+    dev = idx.device
+    if out is None:
+        out = torch.empty((B, N, C), dtype=_F32, device=dev)
+    elif not (out.is_cuda and out.dtype == _F32 and out.dim() == 3 and out.shape[0] == B and out.shape[1] == N and out.shape[2] >= C
+              and out.is_contiguous()):
+        raise ValueError("roipool3d_grad: out must be a contiguous (B, N, >= C) fp32 device tensor")
+    L = _cabi.lib()
+    nbytes = L.prcnn_roipool3d_grad_work_bytes(B, N, M, S)
+    work = torch.empty((max(nbytes, 4),), dtype=torch.uint8, device=dev)
+    _cabi.check(L.prcnn_roipool3d_grad(_p(g), ld_g, col0, _p(idx), _p(distinct), B, N, M, S, C, _p(out), out.shape[2], _p(work), nbytes,
+                                       _stream()), "prcnn_roipool3d_grad")
+    return out
 
 
 def roipool3d_canonical(xyz, pool_boxes3d, rois, extras, feat_cl, sampled_pt_num, out_feat=None, want_distinct=False):

@@ -11,20 +11,55 @@ import torch.nn as nn
 from . import ops
 from .proposal_layer import CLS_MEAN_SIZE, ProposalConfig, ProposalLayer, _anchor3
 from .rcnn import RCNNConfig, RCNNNet
-from .rpn import RPN, RPNConfig
+from .rpn import RPN, RPNConfig, pt_utils
 
 
 class PointRCNN(nn.Module):
     def __init__(self, num_classes=2, use_xyz=True, mode="TEST", rpn_cfg=RPNConfig, rcnn_cfg=RCNNConfig,
-                 proposal_cfg=ProposalConfig, rpn_score_thresh=0.3):
+                 proposal_cfg=ProposalConfig, rpn_score_thresh=0.3, rpn_fixed=True, pool_grad=False):
+        """rpn_fixed: cfg.RPN.FIXED.  False (`--train_mode rcnn --set RPN.FIXED False`): in training the RPN runs in train mode with
+        gradient and its outputs keep their graph, for a joint loss (train_functions.JointTrainer); evaluation is unchanged.
+        pool_grad: RCNNNet's opt-in RoI-pooling backward (beyond the reference)."""
         super().__init__()
         self.rpn = RPN(use_xyz=use_xyz, cfg=rpn_cfg)
         self.rpn.proposal_layer = ProposalLayer(mode=mode, cfg=proposal_cfg)      # lib/net/rpn.py:48
-        self.rcnn_net = RCNNNet(num_classes=num_classes, input_channels=128, use_xyz=use_xyz, cfg=rcnn_cfg)
+        self.rcnn_net = RCNNNet(num_classes=num_classes, input_channels=128, use_xyz=use_xyz, cfg=rcnn_cfg, pool_grad=pool_grad)
         self.rpn_score_thresh = rpn_score_thresh                                  # cfg.RPN.SCORE_THRESH
         self.rcnn_cfg = rcnn_cfg
+        self.rpn_fixed = bool(rpn_fixed)
+
+    def _forward_joint(self, input_data):
+        """point_rcnn.py:26-63 with cfg.RPN.FIXED False, training: the RPN in train mode under enable_grad (hand-written training
+        stacks), rpn_cls / rpn_reg / backbone_features with their graph; the proposal block without gradient, as the reference has it"""
+        output = {}
+        with torch.enable_grad():                                                 # point_rcnn.py:36-37 (set_grad_enabled(not FIXED))
+            # RPN.forward, with the RCNN stage's view of the features taken BEFORE the heads: autograd runs nodes in reverse creation
+            # order, so in backward both heads deliver their gradient to backbone_features first and the pooling's gradient (pool_grad)
+            # is added last -- the RPN-loss part of that sum is then the same bits with pool_grad on and off
+            rpn = self.rpn
+            backbone_xyz, backbone_features = rpn.backbone_net(input_data["pts_input"])
+            rpn_features = backbone_features.permute((0, 2, 1))
+            rpn_output = {"rpn_cls": pt_utils.fused_sequential(rpn.rpn_cls_layer, backbone_features).transpose(1, 2).contiguous(),
+                          "rpn_reg": pt_utils.fused_sequential(rpn.rpn_reg_layer, backbone_features).transpose(1, 2).contiguous(),
+                          "backbone_xyz": backbone_xyz, "backbone_features": backbone_features}
+        output.update(rpn_output)
+        with torch.no_grad():                                                     # point_rcnn.py:40-52
+            rpn_cls, rpn_reg = rpn_output["rpn_cls"], rpn_output["rpn_reg"]
+            rpn_scores_raw = rpn_cls[:, :, 0]
+            rpn_scores_norm = torch.sigmoid(rpn_scores_raw)
+            seg_mask = (rpn_scores_norm > self.rpn_score_thresh).float()
+            pts_depth = torch.norm(backbone_xyz, p=2, dim=2)
+            rois, roi_scores_raw = self.rpn.proposal_layer(rpn_scores_raw, rpn_reg, backbone_xyz)
+            output["rois"], output["roi_scores_raw"], output["seg_result"] = rois, roi_scores_raw, seg_mask
+        rcnn_input_info = {"rpn_xyz": backbone_xyz, "rpn_features": rpn_features,
+                           "seg_mask": seg_mask, "roi_boxes3d": rois, "pts_depth": pts_depth,
+                           "gt_boxes3d": input_data["gt_boxes3d"]}
+        output.update(self.rcnn_net(rcnn_input_info))
+        return output
 
     def forward(self, input_data):
+        if self.training and not self.rpn_fixed:
+            return self._forward_joint(input_data)
         output = {}
         with torch.no_grad():                                                     # point_rcnn.py:30-52 (RPN.FIXED)
             if self.training:

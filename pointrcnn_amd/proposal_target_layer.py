@@ -51,8 +51,37 @@ def _alpha(boxes):
     return -torch.sign(beta) * math.pi / 2 + beta + boxes[:, :, 6]
 
 
+class RoIPoolFeatures(torch.autograd.Function):
+    """The pooled feature columns as a function of the per-point features.  forward hands out columns the pooling call has already
+    written (no second pooling); backward is ops.roipool3d_grad on the selection that call reported.  This goes beyond the
+    reference: its roipool3d has no backward.  xyz, boxes and the scalar channels (seg mask, depth) carry no gradient, by definition
+    here: the selection is piecewise constant in them, and the mask and depth columns are inputs of the stage, not features.
+
+    apply(feat (B,N,C), pooled_feat (B*M,S,C) or (B,M,S,C), idx (B,M,S) i32, distinct (B,M) i32, xyz, boxes, *extras) -> pooled_feat"""
+
+    @staticmethod
+    def forward(ctx, feat, pooled_feat, idx, distinct, xyz=None, boxes=None, *extras):
+        ctx.save_for_backward(idx, distinct)
+        ctx.feat_shape = tuple(feat.shape)
+        ctx.n_rest = 2 + len(extras)
+        return pooled_feat.detach()                      # the same storage, a node of its own
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_pooled):
+        idx, distinct = ctx.saved_tensors
+        B, N, C = ctx.feat_shape
+        g = grad_pooled.reshape(-1, idx.shape[2], C) if grad_pooled.dim() == 4 else grad_pooled
+        # the gradient of a torch.cat arrives as a column slice of the wider rows: read in place (ld_g = the wide row) when its rows
+        # are uniformly strided, copied otherwise
+        if g.dtype != torch.float32 or g.stride(2) != 1 or g.stride(0) != g.shape[1] * g.stride(1):
+            g = g.float().contiguous()
+        gfeat = ops.roipool3d_grad(g, idx, distinct, N, C)
+        return (gfeat, None, None, None) + (None,) * ctx.n_rest
+
+
 class ProposalTargetLayer(nn.Module):
-    def __init__(self, cfg=ProposalTargetConfig, seed=None):
+    def __init__(self, cfg=ProposalTargetConfig, seed=None, pool_grad=False):
         """seed None (default): every call keys the sampler's counter-based random table with a fresh draw from torch's global
         (host) generator -- as the reference's sampler, which draws from the numpy / torch global RNGs, it follows
         torch.manual_seed, differs between DDP ranks seeded differently and resumes with the generator state; an int: a
@@ -60,6 +89,9 @@ class ProposalTargetLayer(nn.Module):
         state-dict keys.)"""
         super().__init__()
         self.cfg, self.seed = cfg, None if seed is None else int(seed)
+        # pool_grad: the pooling call also reports its selection, returned as "pool_idx" (B,R,S) / "pool_distinct" (B,R) next to the
+        # usual entries (every other output is the same bytes), for RCNNNet to route the pooled feature columns through RoIPoolFeatures
+        self.pool_grad = bool(pool_grad)
 
     def forward(self, input_dict):
         cfg = self.cfg
@@ -71,8 +103,14 @@ class ProposalTargetLayer(nn.Module):
         if cfg.USE_DEPTH:
             extra.append((input_dict["pts_depth"] / 70.0 - 0.5).unsqueeze(dim=2))
         pts_feature = torch.cat(extra + [rpn_features], dim=2).contiguous()
-        pooled, pooled_empty_flag = ops.roipool3d(rpn_xyz.contiguous(), enlarge_box3d(batch_rois, cfg.POOL_EXTRA_WIDTH).contiguous(),
-                                                  pts_feature, cfg.NUM_POINTS)
+        pool_sel = None
+        if self.pool_grad:
+            pooled, pooled_empty_flag, pool_idx, pool_distinct = ops.roipool3d(
+                rpn_xyz.contiguous(), enlarge_box3d(batch_rois, cfg.POOL_EXTRA_WIDTH).contiguous(), pts_feature, cfg.NUM_POINTS, want_index=True)
+            pool_sel = {"pool_idx": pool_idx, "pool_distinct": pool_distinct}
+        else:
+            pooled, pooled_empty_flag = ops.roipool3d(rpn_xyz.contiguous(), enlarge_box3d(batch_rois, cfg.POOL_EXTRA_WIDTH).contiguous(),
+                                                      pts_feature, cfg.NUM_POINTS)
         sampled_pts, sampled_features = pooled[:, :, :, 0:3], pooled[:, :, :, 3:]
         if cfg.AUG_DATA:
             sampled_pts, batch_rois, batch_gt_of_rois = self.data_augmentation(sampled_pts, batch_rois, batch_gt_of_rois)
@@ -93,10 +131,13 @@ class ProposalTargetLayer(nn.Module):
         invalid_mask = (batch_roi_iou > cfg.CLS_BG_THRESH) & (batch_roi_iou < cfg.CLS_FG_THRESH)
         batch_cls_label[valid_mask == 0] = -1
         batch_cls_label[invalid_mask > 0] = -1
-        return {"sampled_pts": sampled_pts.view(-1, cfg.NUM_POINTS, 3),
-                "pts_feature": sampled_features.reshape(-1, cfg.NUM_POINTS, sampled_features.shape[3]),
-                "cls_label": batch_cls_label.view(-1), "reg_valid_mask": reg_valid_mask.view(-1),
-                "gt_of_rois": batch_gt_of_rois.reshape(-1, 7), "gt_iou": batch_roi_iou.view(-1), "roi_boxes3d": batch_rois.reshape(-1, 7)}
+        ret = {"sampled_pts": sampled_pts.view(-1, cfg.NUM_POINTS, 3),
+               "pts_feature": sampled_features.reshape(-1, cfg.NUM_POINTS, sampled_features.shape[3]),
+               "cls_label": batch_cls_label.view(-1), "reg_valid_mask": reg_valid_mask.view(-1),
+               "gt_of_rois": batch_gt_of_rois.reshape(-1, 7), "gt_iou": batch_roi_iou.view(-1), "roi_boxes3d": batch_rois.reshape(-1, 7)}
+        if pool_sel is not None:
+            ret.update(pool_sel)
+        return ret
 
     def sample_rois_for_rcnn(self, roi_boxes3d, gt_boxes3d, seed=None):
         """(B,M,7), (B,G,7) -> batch_rois (B,R,7), batch_gt_of_rois (B,R,7), batch_roi_iou (B,R); `self.last` keeps the sampler's

@@ -112,9 +112,13 @@ def nms_gpu(boxes_bev, scores, thresh):
 
 
 class RCNNNet(nn.Module):
-    def __init__(self, num_classes=2, input_channels=128, use_xyz=True, cfg=RCNNConfig):
+    def __init__(self, num_classes=2, input_channels=128, use_xyz=True, cfg=RCNNConfig, pool_grad=False):
+        """pool_grad (opt-in, beyond the reference, whose RoI pooling has no backward): in training with online RoI sampling, the pooled
+        RPN feature columns of pts_input depend on rpn_features through RoIPoolFeatures (proposal_target_layer.py), so the RCNN loss
+        reaches the backbone.  The forward pass computes the same bytes either way."""
         super().__init__()
         self.cfg = cfg
+        self.pool_grad = bool(pool_grad)
         self.SA_modules = nn.ModuleList()
         channel_in = input_channels
         self.rcnn_input_channel = 3 + int(cfg.USE_INTENSITY) + int(cfg.USE_MASK) + int(cfg.USE_DEPTH)
@@ -246,6 +250,27 @@ class RCNNNet(nn.Module):
                 raise ValueError("RCNNNet: %s has %d rows, pts_input %d" % (k, v.shape[0], rows))
         return pts_input, target_dict
 
+    def _pool_grad_input(self, input_data):
+        """the training entry with pool_grad: the target layer runs without gradient as ever (same sampler, same draws, same bytes)
+        and also reports its pooling call's selection; the RPN feature columns of pts_input -- those behind the xyz and scalar
+        channels -- then go through RoIPoolFeatures, whose backward scatters their gradient onto rpn_features"""
+        from .proposal_target_layer import RoIPoolFeatures
+        layer = self.proposal_target_layer
+        had = layer.pool_grad
+        layer.pool_grad = True
+        try:
+            with torch.no_grad():
+                target_dict = layer(input_data)
+        finally:
+            layer.pool_grad = had
+        pts_feature, feat = target_dict["pts_feature"], input_data["rpn_features"]
+        n_extra = pts_feature.shape[2] - feat.shape[2]
+        cols = pts_feature[..., n_extra:]
+        if torch.is_grad_enabled() and feat.requires_grad:
+            cols = RoIPoolFeatures.apply(feat, cols, target_dict["pool_idx"], target_dict["pool_distinct"], input_data["rpn_xyz"],
+                                         target_dict["roi_boxes3d"], input_data["seg_mask"], input_data["pts_depth"])
+        return torch.cat((target_dict["sampled_pts"], pts_feature[..., :n_extra], cols), dim=2), target_dict
+
     def forward(self, input_data):
         target_dict = None
         offline = not self.cfg.ROI_SAMPLE_JIT
@@ -255,9 +280,12 @@ class RCNNNet(nn.Module):
         elif self.training:
             # rcnn_net.py:120-126: RoI sampling, noise augmentation, pooling, canonical transform, labels (device sampler:
             # proposal_target_layer.py) -- no gradient; the network below trains on its (B * 64, 512, 3 + C') rows
-            with torch.no_grad():
-                target_dict = self.proposal_target_layer(input_data)
-            pts_input = torch.cat((target_dict["sampled_pts"], target_dict["pts_feature"]), dim=2)
+            if self.pool_grad:
+                pts_input, target_dict = self._pool_grad_input(input_data)
+            else:
+                with torch.no_grad():
+                    target_dict = self.proposal_target_layer(input_data)
+                pts_input = torch.cat((target_dict["sampled_pts"], target_dict["pts_feature"]), dim=2)
             target_dict["pts_input"] = pts_input
             empty = None
         elif self._fused_ok(input_data):
