@@ -893,6 +893,27 @@ int prcnn_train_stack_bwd_split(const prcnn_train_src_t* src, const prcnn_train_
 int prcnn_train_stack_bwd_wsplit(const prcnn_train_src_t* src, const prcnn_train_layer_t* layers, int nl, int pool_ns, const float* a_dump,
                                  int ld_dump, const float* gout, int ld_gout, const uint8_t* arg, float* gin, int ld_gin,
                                  void* const* wsplit_t, void* work, size_t work_bytes, prcnn_stream_t stream);
+/* The split-bf16 x 6 arithmetic for the REST of a stack as well (opt-in; the five entry points above keep their launches and can
+ * reach none of the kernels named here).  The tables are those of _fwd_split / _bwd_split, sized with prcnn_wsplit_bytes, which
+ * counts whole 32-wide chunks of the reduction width: the images are zero-padded that far.  Per layer, on top of the layers the
+ * two older entry points already take (those keep train_fwd_s_kernel / train_dgrad_s_kernel):
+ *   forward, plain rows                 K >= 32, K % 4 == 0, 16-byte aligned rows and prologue tables; any K % 32
+ *   forward, layer 0 of a mode-1 (padded or padding-free) or mode-2 source     K >= 32; any C / C2 / C1 and alignment.  a_dump
+ *                                       receives exactly the bytes prcnn_train_stack_fwd writes
+ *   dgrad                               Nout >= 32; fewer than 2^31 rows
+ * (train_fwd_sa_kernel / train_dgrad_sa_kernel; a staged element past the width is +0 by selection and no load reaches past a
+ * row's end).  K < 32 / Nout < 32 and everything else run the fp32 kernel of the twin.  ONE launch per call
+ * (train_pack_split_all_kernel) writes every split image the call uses -- a grouped layer 0's with the k rotation of its fp32
+ * image, its transposed one without the three xyz columns --; wpack / wpack_t are written as in the twin.
+ * prcnn_train_stack_bwd_split_all: wgrad_split != 0 runs the wide layers' wgrad as prcnn_train_stack_bwd_wsplit does.
+ * Non-finite operands: as for the two older entry points (no recomputation; a row with a non-finite staged value is non-finite in
+ * its own row only). */
+int prcnn_train_stack_fwd_split_all(const prcnn_train_src_t* src, const prcnn_train_layer_t* layers, int nl, int pool_ns, float* a_dump,
+                                    int ld_dump, float* out, int ld_out, int col_off, uint8_t* arg, void* const* wsplit, void* work,
+                                    size_t work_bytes, prcnn_stream_t stream);
+int prcnn_train_stack_bwd_split_all(const prcnn_train_src_t* src, const prcnn_train_layer_t* layers, int nl, int pool_ns, const float* a_dump,
+                                    int ld_dump, const float* gout, int ld_gout, const uint8_t* arg, float* gin, int ld_gin,
+                                    void* const* wsplit_t, void* work, size_t work_bytes, prcnn_stream_t stream, int wgrad_split);
 /* Padding-free rows for a grouped stack (exact: ball_query pads a group with copies of its first hit; copies are identical rows).
  * prcnn_train_group_rows builds the distinct-row list deterministically (count -> exclusive scan -> fill, group order);
  * prcnn_flat_rows_grad scatters the first layer's row gradients back: dfeat[ridx[r], 0:C] += G[r, 0:C] for the live rows. */

@@ -165,6 +165,10 @@ SIGNATURES = {
                                          ctypes.POINTER(_P), _P, _Z, _P]),
     "prcnn_train_stack_bwd_wsplit": (_I, [ctypes.POINTER(TrainSrc), ctypes.POINTER(TrainLayer), _I, _I, _P, _I, _P, _I, _P, _P, _I,
                                           ctypes.POINTER(_P), _P, _Z, _P]),
+    "prcnn_train_stack_fwd_split_all": (_I, [ctypes.POINTER(TrainSrc), ctypes.POINTER(TrainLayer), _I, _I, _P, _I, _P, _I, _I, _P,
+                                             ctypes.POINTER(_P), _P, _Z, _P]),
+    "prcnn_train_stack_bwd_split_all": (_I, [ctypes.POINTER(TrainSrc), ctypes.POINTER(TrainLayer), _I, _I, _P, _I, _P, _I, _P, _P, _I,
+                                             ctypes.POINTER(_P), _P, _Z, _P, _I]),
     "prcnn_ref_trig": (_I, [_P, _P, _I, _I, _P, _P]),
     "prcnn_boxes_iou3d": (_I, [_P, _I, _P, _I, _P, _P]),
     "prcnn_proposal_target_sample": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, _I, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -433,7 +433,8 @@ PRCNN_API int prcnn_pack_weight(const float* w, int Nout, int K, int k_rot, floa
 
 PRCNN_API size_t prcnn_wsplit_bytes(int Nout, int K) {
     if (Nout <= 0 || K <= 0) return 0;
-    return (size_t)((Nout + 31) / 32) * ((K + 15) / 16) * 3 * 1024;
+    // whole 32-wide chunks of k (two k-steps each): the training images of a ragged K are zero-padded that far; K % 32 == 0: (K + 15) / 16
+    return (size_t)((Nout + 31) / 32) * (((K + 31) / 32) * 2) * 3 * 1024;
 }
 
 PRCNN_API int prcnn_pack_weight_split(const float* w, int Nout, int K, int chain, void* wsplit, prcnn_stream_t stream) {

@@ -23,8 +23,11 @@
 //                                   (no LDS, no barrier); row ranges are split over workgroups, partial tiles reduced in fixed order.
 //   opt-in    train_fwd_s_kernel, train_dgrad_s_kernel: the forward of plain-row layers and dgrad on the split-bf16 x 6 arithmetic of
 //                                   the inference layers (prcnn_train_stack_fwd_split / _bwd_split; see the block above those kernels).
+//             train_fwd_sa_kernel, train_dgrad_sa_kernel: the same for the gathered first layers and the ragged widths, with
+//                                   train_pack_split_all_kernel (prcnn_train_stack_fwd_split_all / _bwd_split_all).
 // Nothing here folds BatchNorm or removes padded rows: the arithmetic is the reference's, row for row.
 #pragma once
+#include "train_split_index.h"
 
 struct TrainFwd {
     MlpParams P;                  // rows, K, KB, NB, wpack, Nout, out (= y), ld_out, and the MODE_* source fields
@@ -833,6 +836,203 @@ __global__ void train_pack_split_t_kernel(const float* __restrict__ w, int Nout,
     for (int p = 0; p < 3; p++)
         img[(blk * 3 + p) * 64 + lane] = make_uint4(bf16_pair(b[p][0], b[p][1]), bf16_pair(b[p][2], b[p][3]),
                                                     bf16_pair(b[p][4], b[p][5]), bf16_pair(b[p][6], b[p][7]));
+}
+
+// =====================================================================================================
+// Split-bf16 x 6 for the REST of the stacks (OPT-IN, prcnn_train_stack_fwd_split_all / _bwd_split_all only; the kernels above keep
+// the layers the two older entry points give them): gathered first layers and ragged reduction widths.
+//   forward  train_fwd_sa_kernel<MODE, WNB>: train_s_tile over ceil(K / 32) chunks.  MODE_GROUP / MODE_INTERP stage their rows with
+//            TrainGatherStage (make_meta / fetch / finish of mlp.hip, the fp32 kernel's own staging: the dumped first-layer rows are
+//            its bytes), MODE_PLAIN with TrainFwdRagStage (K % 4 == 0, any K % 32).
+//   dgrad    train_dgrad_sa_kernel<WNB, POOL>: the reduction over N runs ceil(N / 32) chunks (N % 4 == 0).
+// A staged element past the width is +0 by SELECTION (never a product: +-inf beside the rows stays out), and no load reaches past
+// a row's last element: the gathered fetchers check every element, the plain and dgrad stagers clamp the address to the row's last
+// 16-byte piece (min(k, K - 4), as train_fwd_kernel's FASTP form) and select zero.  The weight images are zero-padded to
+// 32 ceil(K / 32) by train_pack_split_all_kernel, ONE launch per call for every image the call needs.
+// =====================================================================================================
+template <int MODE>
+struct TrainGatherStage {
+    const MlpParams* P;                                   // (the kernel's copy: rows = the live rows)
+    float* a_dump;                                        // NULL: not this workgroup's to write (blockIdx.y != 0) or not asked for
+    int ld_dump, c4;
+    long drow;                                            // row0 + r0
+    RowMeta<MODE> meta[4];
+    Raw<MODE> ra[4];
+    bool live[4];
+    __device__ __forceinline__ void load(int c) {
+        const int k = c * MLP_BK + c4 * 4;
+#pragma unroll
+        for (int u = 0; u < 4; u++) fetch<MODE>(*P, meta[u], k, ra[u]);
+    }
+    __device__ __forceinline__ float4 value(int u, int c) const {
+        const int k = c * MLP_BK + c4 * 4;
+        const float4 v = finish<MODE>(*P, meta[u], k, ra[u]);
+        if (a_dump && live[u] && k < ld_dump) *reinterpret_cast<float4*>(a_dump + (drow + 32 * u) * (long)ld_dump + k) = v;
+        return v;
+    }
+};
+// plain rows, K % 4 == 0, any K % 32: TrainFwdStage with the clamped address and the selected zero
+struct TrainFwdRagStage {
+    const float* arow[4];                                 // row start (no column offset)
+    const float *ps_p, *pb_p;                             // NULL: raw rows
+    int K, c4;
+    float4 ra[4], ps, pb;
+    __device__ __forceinline__ void load(int c) {
+        const int kc = min(c * MLP_BK + c4 * 4, K - 4);
+        if (ps_p) { ps = ld4(ps_p + kc); pb = ld4(pb_p + kc); }
+#pragma unroll
+        for (int u = 0; u < 4; u++) ra[u] = ld4(arow[u] + kc);
+    }
+    __device__ __forceinline__ float4 value(int u, int c) const {
+        float4 v = ra[u];
+        if (ps_p) {
+            v.x = fmaxf(v.x * ps.x + pb.x, 0.f); v.y = fmaxf(v.y * ps.y + pb.y, 0.f);
+            v.z = fmaxf(v.z * ps.z + pb.z, 0.f); v.w = fmaxf(v.w * ps.w + pb.w, 0.f);
+        }
+        return (c * MLP_BK + c4 * 4 < K) ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+};
+// T.P.wsplit: the split image of W (chain = 0) zero-padded to 32 ceil(K / 32), a grouped layer 0's with train_pack_kernel's rotation
+template <int MODE, int WNB>
+__global__ __launch_bounds__(MLP_THREADS, 2) void train_fwd_sa_kernel(const TrainFwd T) {
+    MlpParams P = T.P;
+    P.rows = effective_rows(T.P);
+    const long row0 = (long)blockIdx.x * MLP_BM;
+    const int nb0 = blockIdx.y * 2 * WNB;
+    if (row0 >= P.rows) return;                           // (device-side row count: tiles past the live rows exit at once)
+    __shared__ __attribute__((aligned(16))) unsigned char Ls[2 * 3 * SPL_PLANE];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c4 = tid & 7, r0 = tid >> 3;
+    const int KS = ((P.K + 31) >> 5) * 2;
+    f32x16 acc[2][WNB];
+    if constexpr (MODE == MODE_PLAIN) {
+        TrainFwdRagStage st;
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            long grow = row0 + r0 + 32 * u;
+            if (grow >= P.rows) grow = P.rows - 1;        // clamped: results of dead rows are never stored or counted
+            st.arow[u] = P.in + grow * P.ld_in;
+        }
+        st.ps_p = T.pro_scale; st.pb_p = T.pro_scale ? T.pro_shift : nullptr;
+        st.K = P.K; st.c4 = c4;
+        train_s_tile<WNB>(st, reinterpret_cast<const uint4*>(P.wsplit), KS, P.NB, nb0, tid, Ls, acc);
+    } else {
+        TrainGatherStage<MODE> st;
+        st.P = &P; st.c4 = c4; st.drow = row0 + r0;
+        st.a_dump = blockIdx.y == 0 ? T.a_dump : nullptr; st.ld_dump = T.ld_dump;
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            long grow = row0 + r0 + 32 * u;
+            st.live[u] = grow < P.rows;
+            if (!st.live[u]) grow = P.rows - 1;
+            make_meta<MODE>(P, grow, st.meta[u]);
+        }
+        train_s_tile<WNB>(st, reinterpret_cast<const uint4*>(P.wsplit), KS, P.NB, nb0, tid, Ls, acc);
+    }
+    const int wm = wave >> 1, wn = wave & 1;
+    train_fwd_epilogue<WNB>(T, P, acc, row0, nb0, wm, wn, lane, (nb0 + wn * WNB) < P.NB);
+}
+
+// dgrad over a ragged N: TrainDgradStage with every address (G, y, the six constant vectors, the arg words) clamped to the row's
+// last 16-byte piece and the staged dy selected to zero past N
+template <int POOL>
+struct TrainDgradRagStage {
+    const TrainBwd* T;
+    int grow[4], ggrp[4];
+    int gslot[4], c4;
+    float rm[4];
+    float4 rg[4], ry[4], sc, sh, mu, is, c1, c2;
+    uchar4 rarg[4];
+    __device__ __forceinline__ void load(int c) {
+        const TrainBwd& B = *T;
+        const int k = min(c * MLP_BK + c4 * 4, B.N - 4);  // (N is a multiple of 4)
+        sc = ld4(B.cst + k); sh = ld4(B.cst + B.ld_c + k); mu = ld4(B.cst + 2 * B.ld_c + k); is = ld4(B.cst + 3 * B.ld_c + k);
+        c1 = ld4(B.cst + 4 * B.ld_c + k); c2 = ld4(B.cst + 5 * B.ld_c + k);
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            rg[u] = ld4(B.G + ggrp[u] * (long)B.ldG + k);
+            if (POOL != 0) rarg[u] = *reinterpret_cast<const uchar4*>(B.arg + ggrp[u] * (long)B.N + k);
+            ry[u] = ld4(B.y + grow[u] * (long)B.ld_y + k);
+        }
+    }
+    __device__ __forceinline__ float4 value(int u, int c) const {
+        float4 g = rg[u];
+        if (POOL != 0) {
+            const int sl = gslot[u];
+            g.x = rarg[u].x == sl ? g.x : 0.f; g.y = rarg[u].y == sl ? g.y : 0.f;
+            g.z = rarg[u].z == sl ? g.z : 0.f; g.w = rarg[u].w == sl ? g.w : 0.f;
+        }
+        const float4 d = bwd_dy4(g, ry[u], sc, sh, mu, is, c1, c2, rm[u]);
+        return (c * MLP_BK + c4 * 4 < T->N) ? d : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+};
+// S.wsplit: the split image of W^T zero-padded in N to 32 ceil(N / 32)
+template <int WNB, int POOL>
+__global__ __launch_bounds__(MLP_THREADS, 2) void train_dgrad_sa_kernel(const TrainDgradS S) {
+    const TrainDgrad& D = S.D;
+    const TrainBwd& T = D.B;
+    const long row0 = (long)blockIdx.x * MLP_BM;
+    const int nb0 = blockIdx.y * 2 * WNB;
+    const long live = bwd_live_rows(T);
+    if (row0 >= live) return;                             // (device-side row count)
+    __shared__ __attribute__((aligned(16))) unsigned char Ls[2 * 3 * SPL_PLANE];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r0 = tid >> 3;
+    TrainDgradRagStage<POOL> st;
+    st.T = &T; st.c4 = tid & 7;
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        long gl = row0 + r0 + 32 * u;
+        if (gl >= live) gl = live - 1;
+        const int g = (int)gl;
+        st.grow[u] = g;
+        st.rm[u] = T.mult ? T.mult[g] : 1.f;
+        if (POOL == 2) { st.ggrp[u] = T.row_grp[g]; st.gslot[u] = g - T.seg_off[st.ggrp[u]]; }
+        else if (POOL == 1) { st.ggrp[u] = g / T.pool_ns; st.gslot[u] = g - st.ggrp[u] * T.pool_ns; }
+        else { st.ggrp[u] = g; st.gslot[u] = 0; }
+    }
+    f32x16 acc[2][WNB];
+    train_s_tile<WNB>(st, S.wsplit, ((T.N + 31) >> 5) * 2, D.NB, nb0, tid, Ls, acc);
+    const int wm = wave >> 1, wn = wave & 1;
+    train_dgrad_epilogue<WNB>(D, acc, row0, nb0, wm, wn, lane, live, (nb0 + wn * WNB) < D.NB);
+}
+
+// Every split image of one call in one launch: a table of <= 8 descriptors by value, one thread per (image, column block, k-step,
+// lane) as in pack_weight_split_kernel / train_pack_split_t_kernel, whose chain = 0 layout this writes.  The element an image
+// position reads (or none: zero padding) is train_split_src (train_split_index.h), shared with the host check of that arithmetic.
+struct TrainPackDesc {
+    const float* w;               // (Nout x K), torch layout
+    uint4* img;
+    long first;                   // the launch's first thread of this image
+    TrainSplitImage I;
+};
+struct TrainPackAll { int n; long total; TrainPackDesc d[8]; };
+__global__ __launch_bounds__(256) void train_pack_split_all_kernel(const TrainPackAll A) {
+    const long e0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e0 >= A.total) return;
+    int i = 0;
+#pragma unroll
+    for (int t = 1; t < 8; t++)
+        if (t < A.n && e0 >= A.d[t].first) i = t;
+    const TrainPackDesc& d = A.d[i];
+    const long e = e0 - d.first;
+    const int lane = (int)(e & 63);
+    const long blk = e >> 6;
+    const int ks = (int)(blk % d.I.KS), nb = (int)(blk / d.I.KS);
+    const int row = nb * 32 + (lane & 31), hh = lane >> 5;
+    uint32_t b[3][8];
+#pragma unroll
+    for (int x = 0; x < 8; x++) {
+        const long src = train_split_src(d.I, row, ks * 16 + 8 * hh + x);
+        const float v = src >= 0 ? d.w[src] : 0.f;
+        split3(v, b[0][x], b[1][x], b[2][x]);
+    }
+#pragma unroll
+    for (int p = 0; p < 3; p++)
+        d.img[(blk * 3 + p) * 64 + lane] = make_uint4(bf16_pair(b[p][0], b[p][1]), bf16_pair(b[p][2], b[p][3]),
+                                                      bf16_pair(b[p][4], b[p][5]), bf16_pair(b[p][6], b[p][7]));
 }
 
 // dW[n, k] = sum_r dy[r, n] * a[r, k].  Both operands go from global memory straight into MFMA operand registers: per step a wave
@@ -1695,12 +1895,13 @@ static WgradPlan wgrad_plan(long rows, int N, int K) {
 // What the host decided for one layer (as MlpLaunch, mlp_host.h): filled by the train_plan_* functions, which launch nothing, and
 // read by train_launch_fwd / _wgrad / _dgrad, the only places that name a GEMM instance.  A forward call fills the shape and the
 // forward part, a backward call the shape, wgrad and dgrad.
-enum TrainKernel { TK_GENERIC, TK_FAST, TK_SPLIT, TK_DIRECT, TK_LDS };
+enum TrainKernel { TK_GENERIC, TK_FAST, TK_SPLIT, TK_DIRECT, TK_LDS, TK_SPLIT_ALL };
 struct TrainLayerPlan {
     int K, N, kin_t;             // input / output channels; the input channels that take a gradient (a grouped layer 0: not its 3 dxyz)
     bool group0, no_bn;          // layer 0 of a grouped source; Conv (+ bias in `beta`) -> ReLU, no normalisation
     WgradPlan wg;
-    // forward: TK_SPLIT train_fwd_s_kernel<WNB>, TK_FAST train_fwd_kernel<MODE_PLAIN, WNB, true>, TK_GENERIC train_fwd_kernel<mode, WNB>
+    // forward: TK_SPLIT train_fwd_s_kernel<WNB>, TK_FAST train_fwd_kernel<MODE_PLAIN, WNB, true>, TK_GENERIC train_fwd_kernel<mode, WNB>,
+    // TK_SPLIT_ALL train_fwd_sa_kernel<mode, WNB>
     int fwd, mode;
     bool fwd_wide;               // WNB = 2
     dim3 fwd_grid, pack_grid, pack_s_grid;
@@ -1709,8 +1910,8 @@ struct TrainLayerPlan {
     int wgrad, pool;
     bool mult, pro;
     dim3 wg_grid;
-    // dgrad: train_dgrad_s_kernel / train_dgrad_kernel<WNB, pool>
-    bool dgrad, dgrad_split, dgrad_wide;
+    // dgrad: train_dgrad_s_kernel / train_dgrad_kernel<WNB, pool>; dgrad_rag: train_dgrad_sa_kernel<WNB, pool> (N % 32 != 0)
+    bool dgrad, dgrad_split, dgrad_wide, dgrad_rag;
     int Kin, KB, NB;             // k-blocks over N, n-blocks over Kin
     dim3 dgrad_grid, pack_t_grid;
 };
@@ -1762,6 +1963,16 @@ static bool train_fwd_split_ok(int mode, int K, const float* in, int ld_in, cons
     return mode == MODE_PLAIN && K % 32 == 0 && K >= 32 && ld_in % 4 == 0 && aligned16(in) && aligned16(pro_scale) && aligned16(pro_shift);
 }
 static bool train_dgrad_split_ok(int N, long rows) { return N % 32 == 0 && N >= 32 && rows < (1L << 31); }
+// ... and with prcnn_train_stack_fwd_split_all / _bwd_split_all in addition (train_fwd_sa_kernel / train_dgrad_sa_kernel):
+//   forward  plain rows with K >= 32, K % 4 == 0 and the alignment above, any K % 32; layer 0 of a grouped or interpolated source
+//            with K >= 32, whatever its C and alignment (fetch<MODE> serves them)
+//   dgrad    N >= 32 (N % 4 == 0 holds for every layer); fewer than 2^31 rows
+// K < 32 / N < 32 keep the fp32 kernel: padding them to 32 would more than double the pipe work of latency-bound launches
+static bool train_fwd_split_all_ok(int mode, int K, const float* in, int ld_in, const float* pro_scale, const float* pro_shift) {
+    if (mode != MODE_PLAIN) return K >= 32;
+    return K >= 32 && K % 4 == 0 && ld_in % 4 == 0 && aligned16(in) && aligned16(pro_scale) && aligned16(pro_shift);
+}
+static bool train_dgrad_split_all_ok(int N, long rows) { return N >= 32 && rows < (1L << 31); }
 
 static int train_check_layers(const prcnn_train_layer_t* L, int nl) {
     PRCNN_REQUIRE(L && nl > 0 && nl <= 8, "prcnn_train_stack: 1..8 layers");
@@ -1793,8 +2004,24 @@ static dim3 train_tile_grid(long rows, int NB, bool& wide) {
     return dim3((unsigned)tiles, prcnn_divup(NB, wide ? 4 : 2));
 }
 
-// first: layer 0, whose prologue (if any) is the caller's; pack_t: the transposed weights are packed too; ws: the split image offered
-static void train_plan_fwd(TrainLayerPlan& p, long rows, int mode, const TrainInput& in, bool vec_a, bool first, bool pack_t, const void* ws) {
+// The forms of the split-all kernels that spill at WNB = 2 take the narrow grid instead (resources in DESIGN 5.5.2): the forward of
+// an interpolated layer 0 (three raw vectors per row in flight: 256 VGPRs + 18 spilled) and the two pooled ragged dgrads (256 + 2).
+// Their wide instantiations do not exist.
+#define TRAIN_SA_NARROW(mode) ((mode) == MODE_INTERP)
+#define TRAIN_SA_DGRAD_NARROW(pool) ((pool) != 0)
+static void train_pack_all_add(TrainPackAll& A, const float* w, void* img, const TrainSplitImage& I) {
+    TrainPackDesc& d = A.d[A.n++];
+    d.w = w; d.img = reinterpret_cast<uint4*>(img); d.first = A.total; d.I = I;
+    A.total += train_split_threads(I);
+}
+static void train_pack_all_launch(const TrainPackAll& A, hipStream_t s) {
+    if (A.n) hipLaunchKernelGGL(train_pack_split_all_kernel, dim3(prcnn_divup(A.total, 256)), dim3(256), 0, s, A);
+}
+
+// first: layer 0, whose prologue (if any) is the caller's; pack_t: the transposed weights are packed too; ws: the split image offered;
+// all: the widened set of prcnn_train_stack_fwd_split_all
+static void train_plan_fwd(TrainLayerPlan& p, long rows, int mode, const TrainInput& in, bool vec_a, bool first, bool pack_t, const void* ws,
+                           bool all) {
     const int K = p.K, N = p.N, NB = prcnn_divup(N, 32);
     p.mode = mode;
     p.pack_grid = dim3(prcnn_divup((long)NB * prcnn_divup(K, 8) * 256 + (pack_t ? (long)prcnn_divup(p.kin_t, 32) * prcnn_divup(N, 8) * 256 : 0), 256));
@@ -1803,16 +2030,22 @@ static void train_plan_fwd(TrainLayerPlan& p, long rows, int mode, const TrainIn
     const bool fast = mode == MODE_PLAIN && vec_a && K % 4 == 0 && K >= 4 && in.lda % 4 == 0 && aligned16(in.a) && (!in.pro_scale || !first) &&
                       !sw_present(SW_TRAIN_FWD_GENERIC);
     p.fwd = (ws && train_fwd_split_ok(mode, K, in.a, in.lda, in.pro_scale, in.pro_shift)) ? TK_SPLIT : fast ? TK_FAST : TK_GENERIC;
+    if (all && ws && p.fwd != TK_SPLIT && train_fwd_split_all_ok(mode, K, in.a, in.lda, in.pro_scale, in.pro_shift)) {
+        p.fwd = TK_SPLIT_ALL;
+        if (TRAIN_SA_NARROW(mode) && p.fwd_wide) { p.fwd_wide = false; p.fwd_grid = dim3(p.fwd_grid.x, prcnn_divup(NB, 2)); }
+    }
 }
 
 // X(family, mode, kernel<.. W ..>): every forward instance, wide (W = 2) and narrow (W = 1)
 #define TRAIN_FWD_TABLE(X)                                                                                                    \
     X(TK_SPLIT, MODE_PLAIN, train_fwd_s_kernel<W>) X(TK_FAST, MODE_PLAIN, train_fwd_kernel<MODE_PLAIN, W, true>)              \
     X(TK_GENERIC, MODE_PLAIN, train_fwd_kernel<MODE_PLAIN, W>) X(TK_GENERIC, MODE_GROUP, train_fwd_kernel<MODE_GROUP, W>)    \
-    X(TK_GENERIC, MODE_INTERP, train_fwd_kernel<MODE_INTERP, W>)
+    X(TK_GENERIC, MODE_INTERP, train_fwd_kernel<MODE_INTERP, W>)                                                              \
+    X(TK_SPLIT_ALL, MODE_PLAIN, train_fwd_sa_kernel<MODE_PLAIN, W>) X(TK_SPLIT_ALL, MODE_GROUP, train_fwd_sa_kernel<MODE_GROUP, W>)
 static int train_launch_fwd(const TrainLayerPlan& p, const TrainFwd& T, hipStream_t s) {
 #define GO(WNB, ...) { constexpr int W = WNB; hipLaunchKernelGGL((__VA_ARGS__), p.fwd_grid, dim3(MLP_THREADS), 0, s, T); }
 #define X(F, M, ...) if (p.fwd == F && p.mode == M && p.fwd_wide) GO(2, __VA_ARGS__) else if (p.fwd == F && p.mode == M) GO(1, __VA_ARGS__) else
+    if (p.fwd == TK_SPLIT_ALL && p.mode == MODE_INTERP && !p.fwd_wide) GO(1, train_fwd_sa_kernel<MODE_INTERP, W>) else       // (narrow only)
     TRAIN_FWD_TABLE(X)
         return prcnn_fail(PRCNN_EINVAL, "prcnn_train_stack_fwd: no forward instance for family %d mode %d", p.fwd, p.mode);
 #undef X
@@ -1823,7 +2056,7 @@ static int train_launch_fwd(const TrainLayerPlan& p, const TrainFwd& T, hipStrea
 // wsplit: NULL (prcnn_train_stack_fwd: every layer on the fp32 pipe, the launches of every release so far) or nl split-image
 // pointers (prcnn_train_stack_fwd_split); an eligible layer with a non-NULL entry runs train_fwd_s_kernel
 static int train_stack_fwd_run(const prcnn_train_src_t* src, const prcnn_train_layer_t* L, int nl, int pool_ns, float* a_dump, int ld_dump,
-                               float* out, int ld_out, int col_off, uint8_t* arg, void* const* wsplit, void* work, size_t work_bytes,
+                               float* out, int ld_out, int col_off, uint8_t* arg, void* const* wsplit, bool all, void* work, size_t work_bytes,
                                prcnn_stream_t stream) {
     TrainFwd T0 = {};
     int rc = train_fill_src(src, T0.P);
@@ -1849,11 +2082,21 @@ static int train_stack_fwd_run(const prcnn_train_src_t* src, const prcnn_train_l
     train_plan_shapes(S, src, L, nl);
     for (int l = 0; l < nl; l++)
         train_plan_fwd(S.l[l], rows, l ? MODE_PLAIN : src->mode, l ? train_input(L, l) : in0, l ? true : T0.P.vec_a != 0, l == 0,
-                       L[l].wpack_t && S.l[l].kin_t > 0, wsplit ? wsplit[l] : nullptr);
+                       L[l].wpack_t && S.l[l].kin_t > 0, wsplit ? wsplit[l] : nullptr, all);
     TrainWork W;
     rc = train_take_work("prcnn_train_stack_fwd", rows, S, false, work, work_bytes, W);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
+    if (all) {                                             // every split image of the call in one launch
+        TrainPackAll A = {};
+        for (int l = 0; l < nl; l++) {
+            const TrainLayerPlan& p = S.l[l];
+            if (p.fwd != TK_SPLIT && p.fwd != TK_SPLIT_ALL) continue;
+            PRCNN_REQUIRE(aligned16(wsplit[l]), "prcnn_train_stack_fwd_split_all: layer %d: split image not 16-byte aligned", l);
+            train_pack_all_add(A, L[l].W, wsplit[l], train_split_image(p.N, p.K, p.N, p.group0 ? 3 : 0, 0));
+        }
+        train_pack_all_launch(A, s);
+    }
     for (int l = 0; l < nl; l++) {
         const TrainLayerPlan& p = S.l[l];
         const int K = p.K, N = p.N, rot = p.group0 ? 3 : 0;
@@ -1869,7 +2112,9 @@ static int train_stack_fwd_run(const prcnn_train_src_t* src, const prcnn_train_l
         P.wpack = L[l].wpack; P.Nout = N; P.out = L[l].y; P.ld_out = N; P.col_off = 0;
         P.KB = (K + 7) / 8; P.NB = (N + 31) / 32;
         T.part = p.no_bn ? nullptr : W.part; T.ld_part = N;
-        if (p.fwd == TK_SPLIT) {
+        if (all && (p.fwd == TK_SPLIT || p.fwd == TK_SPLIT_ALL)) {
+            P.wsplit = wsplit[l];
+        } else if (p.fwd == TK_SPLIT) {
             void* ws = wsplit[l];
             PRCNN_REQUIRE(aligned16(ws), "prcnn_train_stack_fwd_split: layer %d: split image not 16-byte aligned", l);
             hipLaunchKernelGGL(pack_weight_split_kernel, p.pack_s_grid, dim3(256), 0, s, L[l].W, N, K, K / 16, P.NB, 0, reinterpret_cast<uint4*>(ws));
@@ -1898,13 +2143,19 @@ static int train_stack_fwd_run(const prcnn_train_src_t* src, const prcnn_train_l
 PRCNN_API int prcnn_train_stack_fwd(const prcnn_train_src_t* src, const prcnn_train_layer_t* L, int nl, int pool_ns, float* a_dump,
                                     int ld_dump, float* out, int ld_out, int col_off, uint8_t* arg, void* work, size_t work_bytes,
                                     prcnn_stream_t stream) {
-    return train_stack_fwd_run(src, L, nl, pool_ns, a_dump, ld_dump, out, ld_out, col_off, arg, nullptr, work, work_bytes, stream);
+    return train_stack_fwd_run(src, L, nl, pool_ns, a_dump, ld_dump, out, ld_out, col_off, arg, nullptr, false, work, work_bytes, stream);
 }
 PRCNN_API int prcnn_train_stack_fwd_split(const prcnn_train_src_t* src, const prcnn_train_layer_t* L, int nl, int pool_ns, float* a_dump,
                                           int ld_dump, float* out, int ld_out, int col_off, uint8_t* arg, void* const* wsplit, void* work,
                                           size_t work_bytes, prcnn_stream_t stream) {
     PRCNN_REQUIRE(wsplit, "prcnn_train_stack_fwd_split: null split-image table");
-    return train_stack_fwd_run(src, L, nl, pool_ns, a_dump, ld_dump, out, ld_out, col_off, arg, wsplit, work, work_bytes, stream);
+    return train_stack_fwd_run(src, L, nl, pool_ns, a_dump, ld_dump, out, ld_out, col_off, arg, wsplit, false, work, work_bytes, stream);
+}
+PRCNN_API int prcnn_train_stack_fwd_split_all(const prcnn_train_src_t* src, const prcnn_train_layer_t* L, int nl, int pool_ns, float* a_dump,
+                                              int ld_dump, float* out, int ld_out, int col_off, uint8_t* arg, void* const* wsplit, void* work,
+                                              size_t work_bytes, prcnn_stream_t stream) {
+    PRCNN_REQUIRE(wsplit, "prcnn_train_stack_fwd_split_all: null split-image table");
+    return train_stack_fwd_run(src, L, nl, pool_ns, a_dump, ld_dump, out, ld_out, col_off, arg, wsplit, true, work, work_bytes, stream);
 }
 
 // pool_ns: the layer's (TrainBwd::pool_ns); a / lda: its input rows; split: prcnn_train_stack_bwd_wsplit.  The 128 x 128 tile is
@@ -1916,12 +2167,14 @@ static void train_plan_wgrad(TrainLayerPlan& p, int pool_ns, bool flat, const fl
     const bool tile128 = p.wg.KQ == 2 && p.wg.NQ == 2 && p.wg.WK == 2 && p.wg.WN == 2;
     p.wgrad = (tile128 && lda % 4 == 0 && aligned16(a) && !sw_present(SW_WGRAD_DIRECT)) ? (split ? TK_SPLIT : TK_LDS) : TK_DIRECT;
 }
-// Kin: the input channels that take the gradient; wst: the split image of W^T offered
-static void train_plan_dgrad(TrainLayerPlan& p, long rows, int Kin, const void* wst) {
+// Kin: the input channels that take the gradient; wst: the split image of W^T offered; all: prcnn_train_stack_bwd_split_all
+static void train_plan_dgrad(TrainLayerPlan& p, long rows, int Kin, const void* wst, bool all) {
     p.dgrad = true;
     p.Kin = Kin; p.KB = (p.N + 7) / 8; p.NB = (Kin + 31) / 32;
     p.dgrad_grid = train_tile_grid(rows, p.NB, p.dgrad_wide);
     p.dgrad_split = wst && train_dgrad_split_ok(p.N, rows);
+    p.dgrad_rag = all && wst && !p.dgrad_split && train_dgrad_split_all_ok(p.N, rows);
+    if (p.dgrad_rag && TRAIN_SA_DGRAD_NARROW(p.pool) && p.dgrad_wide) { p.dgrad_wide = false; p.dgrad_grid = dim3(p.dgrad_grid.x, prcnn_divup(p.NB, 2)); }
     p.pack_t_grid = dim3(prcnn_divup((long)p.NB * (p.N / 16) * 64, 256));
 }
 
@@ -1949,6 +2202,11 @@ static int train_launch_dgrad(const TrainLayerPlan& p, const TrainDgradS& DS, hi
 #define GO(arg, ...) hipLaunchKernelGGL((__VA_ARGS__), p.dgrad_grid, dim3(MLP_THREADS), 0, s, arg)
 #define FORM(SPLIT, arg, kernel, POOL) if (p.dgrad_split == SPLIT && p.pool == POOL && p.dgrad_wide) GO(arg, kernel<2, POOL>); else \
                                        if (p.dgrad_split == SPLIT && p.pool == POOL) GO(arg, kernel<1, POOL>); else
+    if (p.dgrad_rag && p.pool == 0 && p.dgrad_wide) GO(DS, train_dgrad_sa_kernel<2, 0>); else
+#define RAG(POOL) if (p.dgrad_rag && p.pool == POOL && !p.dgrad_wide) GO(DS, train_dgrad_sa_kernel<1, POOL>); else
+    RAG(0) RAG(1) RAG(2)                                   // (the pooled forms: narrow only)
+#undef RAG
+    if (p.dgrad_rag) return prcnn_fail(PRCNN_EINVAL, "prcnn_train_stack_bwd_split_all: no ragged dgrad instance for pool %d wide %d", p.pool, (int)p.dgrad_wide); else
     FORM(true, DS, train_dgrad_s_kernel, 0) FORM(true, DS, train_dgrad_s_kernel, 1) FORM(true, DS, train_dgrad_s_kernel, 2)
     FORM(false, DS.D, train_dgrad_kernel, 0) FORM(false, DS.D, train_dgrad_kernel, 1) FORM(false, DS.D, train_dgrad_kernel, 2)
         return prcnn_fail(PRCNN_EINVAL, "prcnn_train_stack_bwd: no dgrad instance for split %d pool %d", (int)p.dgrad_split, p.pool);
@@ -1962,7 +2220,7 @@ static int train_launch_dgrad(const TrainLayerPlan& p, const TrainDgradS& DS, hi
 // reaches train_wgrad_lds_kernel runs train_wgrad_s_kernel in its place
 static int train_stack_bwd_run(const prcnn_train_src_t* src, const prcnn_train_layer_t* L, int nl, int pool_ns, const float* a_dump,
                                int ld_dump, const float* gout, int ld_gout, const uint8_t* arg, float* gin, int ld_gin, void* const* wsplit_t,
-                               bool wgrad_split, void* work, size_t work_bytes, prcnn_stream_t stream) {
+                               bool wgrad_split, bool all, void* work, size_t work_bytes, prcnn_stream_t stream) {
     PRCNN_REQUIRE(src && gout, "prcnn_train_stack_bwd: null pointer");
     int rc = train_check_layers(L, nl);
     if (rc) return rc;
@@ -1984,12 +2242,22 @@ static int train_stack_bwd_run(const prcnn_train_src_t* src, const prcnn_train_l
         const TrainInput in = l ? train_input(L, l) : in0;
         train_plan_wgrad(S.l[l], l == nl - 1 ? ns : 0, flat, in.a, in.lda, in.pro_scale != nullptr, wgrad_split);
         S.l[l].dgrad = false;
-        if (l > 0 || gin) train_plan_dgrad(S.l[l], rows, l ? S.l[l].K : kin0, wsplit_t ? wsplit_t[l] : nullptr);
+        if (l > 0 || gin) train_plan_dgrad(S.l[l], rows, l ? S.l[l].K : kin0, wsplit_t ? wsplit_t[l] : nullptr, all);
     }
     TrainWork W;
     rc = train_take_work("prcnn_train_stack_bwd", rows, S, true, work, work_bytes, W);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
+    if (all) {                                             // every split image of W^T the call needs in one launch
+        TrainPackAll A = {};
+        for (int l = 0; l < nl; l++) {
+            const TrainLayerPlan& p = S.l[l];
+            if (!p.dgrad || !(p.dgrad_split || p.dgrad_rag)) continue;
+            PRCNN_REQUIRE(aligned16(wsplit_t[l]), "prcnn_train_stack_bwd_split_all: layer %d: split image not 16-byte aligned", l);
+            train_pack_all_add(A, L[l].W, wsplit_t[l], train_split_image(p.N, p.K, p.Kin, p.K - p.Kin, 1));
+        }
+        train_pack_all_launch(A, s);
+    }
     const float* G = gout;
     int ldG = ld_gout;
     for (int l = nl - 1; l >= 0; l--) {
@@ -2029,7 +2297,9 @@ static int train_stack_bwd_run(const prcnn_train_src_t* src, const prcnn_train_l
         D.B = T; D.wpack = L[l].wpack_t;
         D.Kin = p.Kin; D.KB = p.KB; D.NB = p.NB;
         D.out = l == 0 ? gin : W.G[l & 1]; D.ld_out = l == 0 ? ld_gin : K;
-        if (p.dgrad_split) {
+        if (all && (p.dgrad_split || p.dgrad_rag)) {
+            DS.wsplit = reinterpret_cast<const uint4*>(wsplit_t[l]);
+        } else if (p.dgrad_split) {
             void* wst = wsplit_t[l];
             PRCNN_REQUIRE(aligned16(wst), "prcnn_train_stack_bwd_split: layer %d: split image not 16-byte aligned", l);
             hipLaunchKernelGGL(train_pack_split_t_kernel, p.pack_t_grid, dim3(256), 0, s, L[l].W, N, K, D.Kin, K - D.Kin, N / 16, D.NB,
@@ -2046,19 +2316,25 @@ static int train_stack_bwd_run(const prcnn_train_src_t* src, const prcnn_train_l
 PRCNN_API int prcnn_train_stack_bwd(const prcnn_train_src_t* src, const prcnn_train_layer_t* L, int nl, int pool_ns, const float* a_dump,
                                     int ld_dump, const float* gout, int ld_gout, const uint8_t* arg, float* gin, int ld_gin, void* work,
                                     size_t work_bytes, prcnn_stream_t stream) {
-    return train_stack_bwd_run(src, L, nl, pool_ns, a_dump, ld_dump, gout, ld_gout, arg, gin, ld_gin, nullptr, false, work, work_bytes, stream);
+    return train_stack_bwd_run(src, L, nl, pool_ns, a_dump, ld_dump, gout, ld_gout, arg, gin, ld_gin, nullptr, false, false, work, work_bytes, stream);
 }
 PRCNN_API int prcnn_train_stack_bwd_split(const prcnn_train_src_t* src, const prcnn_train_layer_t* L, int nl, int pool_ns, const float* a_dump,
                                           int ld_dump, const float* gout, int ld_gout, const uint8_t* arg, float* gin, int ld_gin,
                                           void* const* wsplit_t, void* work, size_t work_bytes, prcnn_stream_t stream) {
     PRCNN_REQUIRE(wsplit_t, "prcnn_train_stack_bwd_split: null split-image table");
-    return train_stack_bwd_run(src, L, nl, pool_ns, a_dump, ld_dump, gout, ld_gout, arg, gin, ld_gin, wsplit_t, false, work, work_bytes, stream);
+    return train_stack_bwd_run(src, L, nl, pool_ns, a_dump, ld_dump, gout, ld_gout, arg, gin, ld_gin, wsplit_t, false, false, work, work_bytes, stream);
 }
 PRCNN_API int prcnn_train_stack_bwd_wsplit(const prcnn_train_src_t* src, const prcnn_train_layer_t* L, int nl, int pool_ns, const float* a_dump,
                                            int ld_dump, const float* gout, int ld_gout, const uint8_t* arg, float* gin, int ld_gin,
                                            void* const* wsplit_t, void* work, size_t work_bytes, prcnn_stream_t stream) {
     PRCNN_REQUIRE(wsplit_t, "prcnn_train_stack_bwd_wsplit: null split-image table");
-    return train_stack_bwd_run(src, L, nl, pool_ns, a_dump, ld_dump, gout, ld_gout, arg, gin, ld_gin, wsplit_t, true, work, work_bytes, stream);
+    return train_stack_bwd_run(src, L, nl, pool_ns, a_dump, ld_dump, gout, ld_gout, arg, gin, ld_gin, wsplit_t, true, false, work, work_bytes, stream);
+}
+PRCNN_API int prcnn_train_stack_bwd_split_all(const prcnn_train_src_t* src, const prcnn_train_layer_t* L, int nl, int pool_ns, const float* a_dump,
+                                              int ld_dump, const float* gout, int ld_gout, const uint8_t* arg, float* gin, int ld_gin,
+                                              void* const* wsplit_t, void* work, size_t work_bytes, prcnn_stream_t stream, int wgrad_split) {
+    PRCNN_REQUIRE(wsplit_t, "prcnn_train_stack_bwd_split_all: null split-image table");
+    return train_stack_bwd_run(src, L, nl, pool_ns, a_dump, ld_dump, gout, ld_gout, arg, gin, ld_gin, wsplit_t, wgrad_split != 0, true, work, work_bytes, stream);
 }
 
 PRCNN_API int prcnn_group_rows_grad(const float* G, int ldG, const int32_t* idx, int B, int M, int ns, int C, int N, float* dfeat,

@@ -224,12 +224,15 @@ def rpn_loss_kind_rows(dev, B=16, N=16384, rounds=5):
 
 
 def train_split_rows(dev, B=16, rounds=5):
-    """`train stack fwd+bwd`: one SharedMLPTrain forward + backward at two RPN training shapes -- an SA2-like padding-free stack
-    (4096 -> 1024 centres, radius 2.5, nsample 32, [96 + 3, 64, 96, 128]) and an FP-like plain stack (B x 16 384 rows, [256, 128, 128]) -- with
-    train_mlp.TRAIN_SPLIT 0 (fp32 MFMA throughout) against 6 (split-bf16 forward / dgrad on the eligible layers) against 6 with
-    train_mlp.TRAIN_SPLIT_WGRAD 6 as well (the wide layers' wgrad on train_wgrad_s_kernel), alternated in one process; per setting
-    the median, minimum and maximum over `rounds` windows of 20 calls.  `split_launches`: the per-call weight split launches the
-    setting adds; `split_wgrads`: the layers whose wgrad runs the split kernel."""
+    """`train stack fwd+bwd`: one SharedMLPTrain forward + backward at four RPN training shapes -- an SA2-like padding-free stack
+    (4096 -> 1024 centres, radius 2.5, nsample 32, [96 + 3, 64, 96, 128]), an SA4-like padding-free first layer (256 -> 64 centres,
+    nsample 32, [512 + 3, 256]), an FP-like plain stack (B x 16 384 rows, [256, 128, 128]) and an FP-like stack with its interpolated
+    first layer (4096 known -> 16 384 points, [128 + 128, 128, 128]) -- with train_mlp.TRAIN_SPLIT 0 (fp32 MFMA throughout) against 6
+    (split-bf16 forward / dgrad on the plain-row layers) against train_mlp.TRAIN_SPLIT_ALL 6 (the gathered first layers and the
+    ragged widths as well, one split-image launch per call), each also with train_mlp.TRAIN_SPLIT_WGRAD 6 (the wide layers' wgrad
+    on train_wgrad_s_kernel), alternated in one process; per setting the median, minimum and maximum over `rounds` windows of 20
+    calls.  `split_launches`: the weight split launches per forward + backward the setting adds; `split_wgrads`: the layers whose
+    wgrad runs the split kernel."""
     from . import train_mlp
     g = torch.Generator().manual_seed(5)
     xyz = rpn.synthetic_clouds(B, 16384, device=dev)
@@ -237,10 +240,18 @@ def train_split_rows(dev, B=16, rounds=5):
     nx2 = ops.gather_rows(xyz1, ops.furthest_point_sample(xyz1, 1024))
     idx = ops.ball_query(2.5, 32, xyz1, nx2)          # (radius 1.0 finds the centre alone among these uniform FPS samples)
     gr = train_mlp.GroupRows(idx, nx2, 4096)
+    xyz3 = ops.gather_rows(nx2, ops.furthest_point_sample(nx2, 256))
+    nx4 = ops.gather_rows(xyz3, ops.furthest_point_sample(xyz3, 64))
+    gr4 = train_mlp.GroupRows(ops.ball_query(20.0, 32, xyz3, nx4), nx4, 256)
+    _, idx3, w3 = ops.three_nn(xyz, xyz1, want_weight=True)
     stacks = (("SA2-like padding-free", train_mlp.Source("group", xyz=xyz1.reshape(1, -1, 3), rows=gr), 32,
-               torch.randn(B, 4096, 96, generator=g).to(dev), [99, 64, 96, 128], B * 1024),
-              ("FP-like plain", train_mlp.Source("plain"), 0, torch.randn(B * 16384, 256, generator=g).to(dev), [256, 128, 128], B * 16384))
-    for name, src, ns, x0, chans, groups in stacks:
+               torch.randn(B, 4096, 96, generator=g).to(dev), None, [99, 64, 96, 128], B * 1024, gr),
+              ("SA4-like padding-free first layer", train_mlp.Source("group", xyz=xyz3.reshape(1, -1, 3), rows=gr4), 32,
+               torch.randn(B, 256, 512, generator=g).to(dev), None, [515, 256], B * 64, gr4),
+              ("FP-like plain", train_mlp.Source("plain"), 0, torch.randn(B * 16384, 256, generator=g).to(dev), None, [256, 128, 128], B * 16384, None),
+              ("FP-like interpolated", train_mlp.Source("interp", idx3=idx3, w3=w3), 0, torch.randn(B, 4096, 128, generator=g).to(dev),
+               torch.randn(B, 16384, 128, generator=g).to(dev), [256, 128, 128], B * 16384, None))
+    for name, src, ns, x0, x1, chans, groups, rows_of in stacks:
         x0.requires_grad_(True)
         bns = [torch.nn.BatchNorm1d(n).to(dev).train() for n in chans[1:]]
         params = []
@@ -250,27 +261,29 @@ def train_split_rows(dev, B=16, rounds=5):
 
         def step():
             x0.grad = None
-            train_mlp.SharedMLPTrain.apply(src, bns, ns, x0, None, *params).backward(gout)
-        settings = ((0, 0, "fp32 MFMA"), (6, 0, "split-bf16 x 6"), (6, 6, "split-bf16 x 6 + split wgrad"))
-        times = {st[:2]: [] for st in settings}
-        keep = train_mlp.TRAIN_SPLIT, train_mlp.TRAIN_SPLIT_WGRAD
+            train_mlp.SharedMLPTrain.apply(src, bns, ns, x0, x1, *params).backward(gout)
+        settings = ((0, 0, 0, "fp32 MFMA"), (6, 0, 0, "split-bf16 x 6"), (6, 6, 0, "split-bf16 x 6 + split wgrad"),
+                    (0, 0, 6, "split-bf16 x 6 all"), (0, 6, 6, "split-bf16 x 6 all + split wgrad"))
+        times = {st[:3]: [] for st in settings}
+        keep = train_mlp.TRAIN_SPLIT, train_mlp.TRAIN_SPLIT_WGRAD, train_mlp.TRAIN_SPLIT_ALL
         try:
             for _ in range(rounds):
-                for terms, wterms, _ in settings:
-                    train_mlp.TRAIN_SPLIT, train_mlp.TRAIN_SPLIT_WGRAD = terms, wterms
-                    times[(terms, wterms)].append(timeit(step))
+                for terms, wterms, aterms, _ in settings:
+                    train_mlp.TRAIN_SPLIT, train_mlp.TRAIN_SPLIT_WGRAD, train_mlp.TRAIN_SPLIT_ALL = terms, wterms, aterms
+                    times[(terms, wterms, aterms)].append(timeit(step))
         finally:
-            train_mlp.TRAIN_SPLIT, train_mlp.TRAIN_SPLIT_WGRAD = keep
-        rows = int(gr.rows_dev.item()) if ns else groups
+            train_mlp.TRAIN_SPLIT, train_mlp.TRAIN_SPLIT_WGRAD, train_mlp.TRAIN_SPLIT_ALL = keep
+        rows = int(rows_of.rows_dev.item()) if rows_of is not None else groups
         fwd_split = sum(1 for l, k in enumerate(chans[:-1]) if k % 32 == 0 and (l > 0 or src.mode == "plain"))
         bwd_split = sum(1 for n in chans[1:] if n % 32 == 0)
         wide = sum(1 for k, n in zip(chans[:-1], chans[1:]) if k > 64 and n > 64)
-        for terms, wterms, label in settings:
-            t = sorted(times[(terms, wterms)])
+        for terms, wterms, aterms, label in settings:
+            t = sorted(times[(terms, wterms, aterms)])
             print(json.dumps({"op": "train stack fwd+bwd (%s)" % label,
                               "shape": "%s: B%d, %d rows, %s" % (name, B, rows, chans), "median_us": round(t[len(t) // 2] * 1e6, 1),
                               "min_us": round(t[0] * 1e6, 1), "max_us": round(t[-1] * 1e6, 1),
-                              "split_launches": (fwd_split + bwd_split) if terms else 0, "split_wgrads": wide if wterms else 0}), flush=True)
+                              "split_launches": 2 if aterms else (fwd_split + bwd_split) if terms else 0,
+                              "split_wgrads": wide if wterms else 0}), flush=True)
 
 
 def train_wgrad_rows(dev, rounds=5):
@@ -818,7 +831,7 @@ def eval_loop_rows(dev, B=16, nbatches=3, rounds=5):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
-    ap.add_argument("--only", default=None, help="run one row family only: eval_stats | optimizer | rpn_loss_kinds | train_split | train_wgrad | head_tail | result_writer | eval_loop")
+    ap.add_argument("--only", default=None, help="run one row family only: eval_stats | optimizer | rpn_loss_kinds | train_split (= train_stack) | train_wgrad | head_tail | result_writer | eval_loop")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     if args.only == "result_writer":
@@ -843,7 +856,7 @@ def main():
     if args.only == "rpn_loss_kinds":
         rpn_loss_kind_rows(dev)
         return
-    if args.only == "train_split":
+    if args.only in ("train_split", "train_stack"):
         train_split_rows(dev)
         return
     if args.only == "train_wgrad":

@@ -40,6 +40,15 @@ _TRAIN_SPLIT_WGRAD_ENV = os.environ.get("PRCNN_TRAIN_SPLIT_WGRAD", "")
 if _TRAIN_SPLIT_WGRAD_ENV not in ("", "0", "1", "6"):
     raise RuntimeError("PRCNN_TRAIN_SPLIT_WGRAD=%r: 1 or 6 = six split-bf16 terms, 0 / unset = fp32 MFMA" % _TRAIN_SPLIT_WGRAD_ENV)
 TRAIN_SPLIT_WGRAD = 6 if _TRAIN_SPLIT_WGRAD_ENV in ("1", "6") else 0
+# The split arithmetic for the rest of the stacks (implies TRAIN_SPLIT's forward / dgrad split, whatever TRAIN_SPLIT holds; composes
+# with TRAIN_SPLIT_WGRAD as TRAIN_SPLIT does; read once like them): 0 (default) = off; 6 (PRCNN_TRAIN_SPLIT_ALL=1 or 6) = also the
+# gathered first layers (group / interp, K >= 32) and the ragged widths (plain K >= 32 with K % 4 == 0, dgrad N >= 32) run split-bf16
+# x 6 (csrc/mlp_train.h: train_fwd_sa_kernel / train_dgrad_sa_kernel, through prcnn_train_stack_fwd_split_all / _bwd_split_all, one
+# split-image launch per call); K < 32 / N < 32 stay on fp32 MFMA
+_TRAIN_SPLIT_ALL_ENV = os.environ.get("PRCNN_TRAIN_SPLIT_ALL", "")
+if _TRAIN_SPLIT_ALL_ENV not in ("", "0", "1", "6"):
+    raise RuntimeError("PRCNN_TRAIN_SPLIT_ALL=%r: 1 or 6 = six split-bf16 terms, 0 / unset = off" % _TRAIN_SPLIT_ALL_ENV)
+TRAIN_SPLIT_ALL = 6 if _TRAIN_SPLIT_ALL_ENV in ("1", "6") else 0
 # bench.py's accounting: when a list, every stack forward appends (rows (int) or live-row counter (device tensor), [(K, N) per layer],
 # first layer takes an input gradient) -- nothing is read back here
 FLOP_LOG = None
@@ -239,16 +248,23 @@ class _Stack:
             self.grad_views.append((dW, dg if gamma is not None else None, db if beta is not None else None))
 
         self.wsplit = self.wsplit_t = None
-        if TRAIN_SPLIT:
-            self._split_images(kins, wt_need, plain, dev)
+        self.split_all = bool(TRAIN_SPLIT_ALL)
+        if TRAIN_SPLIT or TRAIN_SPLIT_ALL:
+            self._split_images(kins, wt_need, plain, dev, self.split_all)
 
-    def _split_images(self, kins, wt_need, plain, dev):
+    def _split_images(self, kins, wt_need, plain, dev, split_all=False):
         """scratch for the split weight images of the layers the split kernels can take (the library decides again, on the
         pointers it sees: include/prcnn_pointops.h), one allocation; NULL entries keep a layer on the fp32 pipe"""
         L = _cabi.lib()
         nl, nout, ks = self.nl, self.nout, self.ks
-        fsz = [L.prcnn_wsplit_bytes(nout[l], ks[l]) if (ks[l] % 32 == 0 and (l > 0 or plain)) else 0 for l in range(nl)]
-        tsz = [L.prcnn_wsplit_bytes(kins[l], nout[l]) if (nout[l] % 32 == 0 and wt_need[l] and kins[l] > 0) else 0 for l in range(nl)]
+        if split_all:          # the widened set: every K >= 32 forward (gathered first layers included), every N >= 32 dgrad
+            f_ok = [ks[l] >= 32 and (ks[l] % 4 == 0 or (l == 0 and not plain)) for l in range(nl)]
+            t_ok = [nout[l] >= 32 for l in range(nl)]
+        else:
+            f_ok = [ks[l] % 32 == 0 and (l > 0 or plain) for l in range(nl)]
+            t_ok = [nout[l] % 32 == 0 for l in range(nl)]
+        fsz = [L.prcnn_wsplit_bytes(nout[l], ks[l]) if f_ok[l] else 0 for l in range(nl)]
+        tsz = [L.prcnn_wsplit_bytes(kins[l], nout[l]) if (t_ok[l] and wt_need[l] and kins[l] > 0) else 0 for l in range(nl)]
         self.sbuf = torch.empty((sum(fsz) + sum(tsz) + 16,), dtype=torch.uint8, device=dev)
         self.wsplit, self.wsplit_t = (ctypes.c_void_p * nl)(), (ctypes.c_void_p * nl)()
         o = (self.sbuf.data_ptr() + 15) // 16 * 16
@@ -299,7 +315,10 @@ class SharedMLPTrain(torch.autograd.Function):
             out = torch.empty((groups, N), dtype=_F32, device=dev)
             arg = torch.empty((groups, N), dtype=torch.uint8, device=dev) if (ns > 1 or flat is not None) else None
             work, nbytes = st.work(K0, False, dev)
-            if st.wsplit is not None:
+            if st.split_all:
+                _cabi.check(L.prcnn_train_stack_fwd_split_all(ctypes.byref(S), st.layers, nl, ns, _p(a_dump), ld_dump, _p(out), N, 0, _p(arg),
+                                                              st.wsplit, _aligned_ptr(work), nbytes, _stream()), "prcnn_train_stack_fwd_split_all")
+            elif st.wsplit is not None:
                 _cabi.check(L.prcnn_train_stack_fwd_split(ctypes.byref(S), st.layers, nl, ns, _p(a_dump), ld_dump, _p(out), N, 0, _p(arg),
                                                           st.wsplit, _aligned_ptr(work), nbytes, _stream()), "prcnn_train_stack_fwd_split")
             else:
@@ -330,7 +349,11 @@ class SharedMLPTrain(torch.autograd.Function):
             ld_gin = _up(ctx.kin0, 4)
             gin = torch.empty((rows, ld_gin), dtype=_F32, device=dev)
         work, nbytes = st.work(ctx.K0, True, dev)
-        if TRAIN_SPLIT_WGRAD:
+        if st.split_all:
+            _cabi.check(L.prcnn_train_stack_bwd_split_all(ctypes.byref(ctx.S), st.layers, st.nl, ctx.ns, _p(ctx.a_dump), ctx.ld_dump, _p(G),
+                                                          G.stride(0), _p(ctx.arg), _p(gin), ld_gin, st.wsplit_t, _aligned_ptr(work), nbytes,
+                                                          _stream(), 1 if TRAIN_SPLIT_WGRAD else 0), "prcnn_train_stack_bwd_split_all")
+        elif TRAIN_SPLIT_WGRAD:
             # (a table of NULLs: every dgrad on the fp32 pipe)
             table = st.wsplit_t if st.wsplit_t is not None else (ctypes.c_void_p * st.nl)()
             _cabi.check(L.prcnn_train_stack_bwd_wsplit(ctypes.byref(ctx.S), st.layers, st.nl, ctx.ns, _p(ctx.a_dump), ctx.ld_dump, _p(G),
