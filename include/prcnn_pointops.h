@@ -79,6 +79,9 @@ int prcnn_abi_version(void);   /* 12: + prcnn_switches_reload, prcnn_switch_get 
                                  * (the same for RPN.LOSS_CLS = DiceLoss and BinaryCrossEntropy);
                                  * still 12 (additive): + prcnn_rcnn_loss_workspace_bytes, prcnn_rcnn_loss_forward, prcnn_rcnn_loss_finalize,
                                  * prcnn_rcnn_loss_backward (the RCNN training loss and its gradient in device passes);
+                                 * still 12 (additive): + prcnn_scene_prepare_large, prcnn_scene_large_workspace_bytes,
+                                 * prcnn_train_scene_prepare_large, prcnn_train_scene_large_workspace_bytes (both input builders up to
+                                 * 65536 points per frame: the shuffle sorted through HBM);
                                  * 11: + prcnn_train_scene_workspace_bytes, prcnn_train_scene_prepare (the RPN training batch on the device);
                                  * 10: + prcnn_corner_iou3d, prcnn_gt_aug_sample (GT-augmentation sampling loop on the device);
                                  * 9: + prcnn_fps_mode, prcnn_ball_query_arith, prcnn_three_nn_arith (comparison mode: the squared distance as nvcc contracts the
@@ -679,13 +682,24 @@ int prcnn_level_pool_residual(int nprob, const float* const* src, const int* ld_
  * Every point at rect depth >= 40 m is kept, the rest drawn without replacement, the result shuffled; short frames are
  * topped up with a draw without replacement from themselves.  The draw uses a counter-based generator keyed by
  * (seed, frame, raw index) -- see scene.hip -- so results are reproducible and independent of launch geometry
- * (the reference uses numpy's unseeded global stream).  npoints <= 16384.
+ * (the reference uses numpy's unseeded global stream).  npoints <= 16384 (prcnn_scene_prepare_large: <= 65536).
  * ====================================================================================================== */
 size_t prcnn_scene_workspace_bytes(int64_t total_points, int B);
 int prcnn_scene_prepare(const float* raw, const int64_t* offsets, int B, int64_t total_points, int max_points_per_frame,
                         const float* calib, const int32_t* img_hw, const double* scope, int npoints, uint32_t seed,
                         float* out_xyz, float* out_intensity, int32_t* out_src, int32_t* nvalid, int32_t* status,
                         void* workspace, size_t workspace_bytes, prcnn_stream_t stream);
+/* The same builder for npoints 1..65536; arguments, outputs and random streams as prcnn_scene_prepare.  npoints <= 16384 runs the
+ * launches of prcnn_scene_prepare (same bytes, same workspace need).  16384 < npoints <= 65536: the draw writes every frame's
+ * selection to a key array in the workspace, the shuffle sorts it through HBM in 16384-key chunks (3 plain launches for up to
+ * 32768 points, 6 above), a last launch writes the rows -- all on `stream`, in launch order, with no host synchronisation; the
+ * workspace (8-byte aligned) grows by B key arrays of npoints rounded up to a power of two, 8 bytes a key, plus 4 bytes per frame.
+ * PRCNN_EINVAL for npoints outside 1..65536 (nothing launched) and for a workspace below prcnn_scene_large_workspace_bytes. */
+size_t prcnn_scene_large_workspace_bytes(int64_t total_points, int B, int npoints);
+int prcnn_scene_prepare_large(const float* raw, const int64_t* offsets, int B, int64_t total_points, int max_points_per_frame,
+                              const float* calib, const int32_t* img_hw, const double* scope, int npoints, uint32_t seed,
+                              float* out_xyz, float* out_intensity, int32_t* out_src, int32_t* nvalid, int32_t* status,
+                              void* workspace, size_t workspace_bytes, prcnn_stream_t stream);
 
 /* ======================================================================================================
  * RPN training batch (train_scene.hip).  KittiRCNNDataset.get_rpn_sample in TRAIN mode (kitti_rcnn_dataset.py:246-362, RPN.FIXED
@@ -719,6 +733,18 @@ int prcnn_train_scene_prepare(const float* raw, const int64_t* offsets, int B, i
                               const double* aug_cfg, float* out_xyz, float* out_input, float* out_features, int32_t* out_src,
                               int32_t* nvalid, int32_t* status, float* out_gt_boxes3d, int32_t* out_num_gt, double* aug,
                               void* workspace, size_t workspace_bytes, prcnn_stream_t stream);
+/* The same pass for npoints 1..65536, as prcnn_scene_prepare_large is to prcnn_scene_prepare: the one-workgroup form up to 16384
+ * (same bytes, same workspace need), select -> HBM sort -> rows above it. */
+size_t prcnn_train_scene_large_workspace_bytes(int64_t total_points, int B, int K, int db_max_points, int npoints);
+int prcnn_train_scene_prepare_large(const float* raw, const int64_t* offsets, int B, int64_t total_points, int max_points_per_frame,
+                                    const float* calib, const int32_t* img_hw, const double* scope, int npoints, uint32_t seed,
+                                    const float* gt_boxes3d, const float* gt_alpha, const int32_t* num_gt, int G,
+                                    const int32_t* acc_count, const int32_t* acc_db_id, const float* acc_boxes3d, const float* acc_alpha,
+                                    const double* acc_y_shift, const int32_t* acc_status, int K, const float* db_points,
+                                    const float* db_intensity, const int64_t* db_offsets, int D, int db_max_points,
+                                    const double* aug_cfg, float* out_xyz, float* out_input, float* out_features, int32_t* out_src,
+                                    int32_t* nvalid, int32_t* status, float* out_gt_boxes3d, int32_t* out_num_gt, double* aug,
+                                    void* workspace, size_t workspace_bytes, prcnn_stream_t stream);
 
 /* ======================================================================================================
  * GT-augmentation database builder (gt_database.hip).  tools/generate_gt_database.py:50-84 for a batch of frames: the rect-camera

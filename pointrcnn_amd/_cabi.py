@@ -148,6 +148,11 @@ SIGNATURES = {
     "prcnn_train_scene_workspace_bytes": (_Z, [_L, _I, _I, _I]),
     "prcnn_train_scene_prepare": (_I, [_P, _P, _I, _L, _I, _P, _P, _P, _I, ctypes.c_uint32, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I,
                                        _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "prcnn_scene_large_workspace_bytes": (_Z, [_L, _I, _I]),
+    "prcnn_scene_prepare_large": (_I, [_P, _P, _I, _L, _I, _P, _P, _P, _I, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "prcnn_train_scene_large_workspace_bytes": (_Z, [_L, _I, _I, _I, _I]),
+    "prcnn_train_scene_prepare_large": (_I, [_P, _P, _I, _L, _I, _P, _P, _P, _I, ctypes.c_uint32, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I,
+                                             _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "prcnn_gt_database_workspace_bytes": (_Z, [_L, _I, _I]),
     "prcnn_gt_database_count": (_I, [_P, _P, _I, _L, _I, _P, _P, _P, _I, _P, _P, _Z, _P]),
     "prcnn_gt_database_fill": (_I, [_P, _P, _I, _L, _I, _P, _P, _P, _I, _P, _L, _P, _P, _P, _P, _Z, _P]),

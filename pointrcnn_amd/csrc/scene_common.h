@@ -2,10 +2,13 @@
 // train_scene.hip (RPN training batch), gt_database.hip (GT-augmentation database: the rect transform and the frame checks).
 // A new pass takes its prelude from here:
 //   device  SceneFrames (head of the kernel params), scene_rect / scene_project (lidar -> rect -> image, get_valid_flag),
-//           scene_append (a block's valid points -> the frame's candidate list), SceneLds + scene_select_sort (the npoints draw:
-//           radix select, ties, LDS bitonic shuffle), scene_empty_frame (the rows of a frame without candidates);
-//   host    scene_check_frames, scene_fill_frames (scope, NP, the counters | list workspace), scene_reset_counters,
-//           scene_launch_sample -- each takes the entry point's name (`who`) for its messages.
+//           scene_append (a block's valid points -> the frame's candidate list), SceneLds + scene_draw + scene_gather (the npoints
+//           draw: radix select, ties, the selection as shuffle keys), scene_select_sort (draw + LDS bitonic shuffle, npoints <= 16384),
+//           scene_select_large (draw -> the frame's HBM key array, npoints > 16384), scene_large_identity (row j's identity after
+//           the HBM sort), scene_empty_frame (the rows of a frame without candidates);
+//   host    scene_check_frames, scene_fill_frames (scope, NP, the counters | list workspace), scene_fill_large (the key arrays and
+//           per-frame totals behind it), scene_reset_counters, scene_launch_sample, scene_large_shuffle (the HBM sort, scene.hip)
+//           -- each takes the entry point's name (`who`) for its messages.
 // The arithmetic contract and the random streams are stated in scene.hip's header comment.
 #pragma once
 #include "lds_sort.h"
@@ -14,6 +17,8 @@
 constexpr int SCENE_THREADS = 1024;
 constexpr int SCENE_MAX_TIES = 1024;
 constexpr unsigned SCENE_FAR = 1u << 30;
+constexpr int SCENE_SMALL_MAX = 16384;       // npoints up to here: draw and shuffle in one workgroup's LDS
+constexpr int SCENE_LARGE_MAX = 65536;       // npoints up to here: the shuffle sorts SCENE_SMALL_MAX-key chunks through HBM
 
 // head of the kernel params of a pass that draws npoints of every frame: SceneParams and TrainSceneParams derive from it
 struct SceneFrames {
@@ -31,6 +36,8 @@ struct SceneFrames {
     int32_t* out_src;           // (B, npoints) identity of every output point
     int32_t* nvalid;            // (B)
     int32_t* status;            // (B) 0 ok, 1 outside the reference's domain (it raises), 2 no valid point
+    u64* large_keys;            // npoints > SCENE_SMALL_MAX only: (B, NP) shuffle keys, sorted through HBM between select and rows
+    int32_t* large_total;       // (B) keys a frame selected (0: the frame wrote its empty rows in the select launch)
 };
 
 struct RectPoint { float x, y, z; bool valid; };
@@ -111,12 +118,14 @@ __device__ __forceinline__ void scene_pick_bin(int c, int want, int* wsum, int* 
     __syncthreads();
 }
 
-// block-wide (SCENE_THREADS threads): the draw and the shuffle of one frame.  L holds the frame's n > 0 candidates (f of them far)
-// as (class | 30-bit key, identity); afterwards keys[lds_phys(0 .. total-1)] hold (shuffle key << 32 | identity) in output order.
-// -> (total, status)
-struct SceneSel { int total, status; };
-__device__ __forceinline__ SceneSel scene_select_sort(const uint2* __restrict__ L, int n, int f, int np, int NP, unsigned seed, unsigned b,
-                                                      u64* keys, SceneLds& S) {
+// block-wide (SCENE_THREADS threads): the draw of one frame.  L holds the frame's n > 0 candidates (f of them far) as
+// (class | 30-bit key, identity).  -> what scene_gather needs to tell the selected candidates; the tie list is left in S.
+struct SceneDraw {
+    int status, need, m;        // need of the m listed candidates with key == T belong to the draw
+    unsigned T;
+    bool keep_far, keep_all;
+};
+__device__ __forceinline__ SceneDraw scene_draw(const uint2* __restrict__ L, int n, int f, int np, SceneLds& S) {
     const int tid = threadIdx.x;
     if (tid == 0) { S.nties = 0; S.nsel = 0; }           // ordered before their first use by the barriers below
     // what to draw: k candidates with the smallest keys; far points are outside the draw (always kept) when more valid
@@ -172,33 +181,45 @@ __device__ __forceinline__ SceneSel scene_select_sort(const uint2* __restrict__ 
         }
     }
     __syncthreads();
-    const int m = min(S.nties, SCENE_MAX_TIES);
-    // ---- gather the selection into LDS as (shuffle key << 32 | raw index)
+    SceneDraw D;
+    D.status = st; D.need = need; D.m = min(S.nties, SCENE_MAX_TIES); D.T = T; D.keep_far = keep_far; D.keep_all = keep_all;
+    return D;
+}
+
+// block-wide, after scene_draw: hands every selected candidate to put(slot, shuffle key << 32 | identity), the slots 0 .. total-1
+// in the order the atomics append (the sort that follows removes it).  -> total (== npoints unless D.status == 1)
+template <class Put>
+__device__ __forceinline__ int scene_gather(const uint2* __restrict__ L, int n, const SceneDraw& D, unsigned seed, unsigned b, SceneLds& S, Put put) {
+    const int tid = threadIdx.x;
     for (int e0 = 0; e0 < n; e0 += SCENE_THREADS) {
         const int e = e0 + tid;
         if (e < n) {
             const uint2 it = L[e];
             const bool isfar = (it.x & SCENE_FAR) != 0u;
             const unsigned key = it.x & (SCENE_FAR - 1u);
-            const bool cand = !(keep_far && isfar);
-            bool drawn = cand && key < T;
-            if (cand && need > 0 && key == T) {
+            const bool cand = !(D.keep_far && isfar);
+            bool drawn = cand && key < D.T;
+            if (cand && D.need > 0 && key == D.T) {
                 int rank = 0;
-                for (int q = 0; q < m; q++) rank += S.ties[q] < it.y ? 1 : 0;
-                drawn = rank < need;
+                for (int q = 0; q < D.m; q++) rank += S.ties[q] < it.y ? 1 : 0;
+                drawn = rank < D.need;
             }
-            if (keep_all || (keep_far && isfar)) {
-                const int p = atomicAdd(&S.nsel, 1);
-                keys[lds_phys(p)] = ((u64)scene_rand(seed, 1u, b, it.y) << 32) | it.y;
-            }
-            if (drawn) {
-                const int p = atomicAdd(&S.nsel, 1);
-                keys[lds_phys(p)] = ((u64)scene_rand(seed, keep_all ? 2u : 1u, b, it.y) << 32) | it.y;
-            }
+            if (D.keep_all || (D.keep_far && isfar)) put(atomicAdd(&S.nsel, 1), ((u64)scene_rand(seed, 1u, b, it.y) << 32) | it.y);
+            if (drawn) put(atomicAdd(&S.nsel, 1), ((u64)scene_rand(seed, D.keep_all ? 2u : 1u, b, it.y) << 32) | it.y);
         }
     }
     __syncthreads();
-    const int total = S.nsel;                              // == npoints unless st == 1
+    return S.nsel;
+}
+
+// block-wide (SCENE_THREADS threads): the draw and the shuffle of one frame with npoints <= SCENE_SMALL_MAX; afterwards
+// keys[lds_phys(0 .. total-1)] hold (shuffle key << 32 | identity) in output order.  -> (total, status)
+struct SceneSel { int total, status; };
+__device__ __forceinline__ SceneSel scene_select_sort(const uint2* __restrict__ L, int n, int f, int np, int NP, unsigned seed, unsigned b,
+                                                      u64* keys, SceneLds& S) {
+    const int tid = threadIdx.x;
+    const SceneDraw D = scene_draw(L, n, f, np, S);
+    const int total = scene_gather(L, n, D, seed, b, S, [keys](int p, u64 v) { keys[lds_phys(p)] = v; });
     u64 v[16];
     if (tid * 16 < NP) {
 #pragma unroll
@@ -210,7 +231,7 @@ __device__ __forceinline__ SceneSel scene_select_sort(const uint2* __restrict__ 
     __syncthreads();
     block_sort16(v, keys, NP, tid);
     SceneSel r;
-    r.total = total; r.status = st;
+    r.total = total; r.status = D.status;
     return r;
 }
 
@@ -223,6 +244,31 @@ __device__ __forceinline__ void scene_empty_frame(const SceneFrames& F, int b, f
         if (in4) { in4[j * 4] = 0.f; in4[j * 4 + 1] = 0.f; in4[j * 4 + 2] = 0.f; in4[j * 4 + 3] = 0.f; }
     }
     if (threadIdx.x == 0) F.status[b] = 2;
+}
+
+// block-wide, npoints > SCENE_SMALL_MAX: the draw of frame b (L: its candidate list) into the frame's NP-entry key array, unsorted,
+// the tail [total, NP) filled with ~0; nvalid, status and the frame's total are written here.  A frame without candidates writes
+// its empty rows and total 0: the sort and row launches skip it.  feat / in4 as scene_empty_frame.
+__device__ __forceinline__ void scene_select_large(const SceneFrames& F, int b, const uint2* __restrict__ L, float* feat, float* in4, SceneLds& S) {
+    const int tid = threadIdx.x;
+    const int n = F.counters[b * 2], f = F.counters[b * 2 + 1];
+    if (tid == 0) F.nvalid[b] = n;
+    if (n == 0) {
+        scene_empty_frame(F, b, feat, in4);
+        if (tid == 0) F.large_total[b] = 0;
+        return;
+    }
+    u64* keys = F.large_keys + (size_t)b * F.NP;
+    const SceneDraw D = scene_draw(L, n, f, F.npoints, S);
+    const int total = scene_gather(L, n, D, F.seed, (unsigned)b, S, [keys](int p, u64 v) { keys[p] = v; });
+    for (int j = total + tid; j < F.NP; j += SCENE_THREADS) keys[j] = ~0ULL;
+    if (tid == 0) { F.large_total[b] = total; F.status[b] = D.status; }
+}
+
+// identity of output row j < npoints of frame b once the key array is sorted (a short selection -- status 1 -- repeats cyclically);
+// only entries below total are read, so the padding identity 0xFFFFFFFF never becomes an address.  total > 0.
+__device__ __forceinline__ unsigned scene_large_identity(const SceneFrames& F, int b, int j, int total) {
+    return (unsigned)F.large_keys[(size_t)b * F.NP + (j < total ? j : j % total)];
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
@@ -243,6 +289,7 @@ static int scene_check_frames(const char* who, const float* raw, const int64_t* 
 // the workspace of a drawing pass is  counters (B, 2) | candidate list, the list on the next 64-byte boundary
 static size_t scene_counters_bytes(int B) { return (size_t)B * 2 * sizeof(int32_t); }
 static size_t scene_list_offset(int B) { return ((scene_counters_bytes(B) + 63) / 64) * 64; }
+static int scene_pow2(int npoints) { int NP = 16; while (NP < npoints) NP <<= 1; return NP; }      // what the shuffle sorts
 
 static void scene_fill_frames(SceneFrames& F, const float* raw, const int64_t* offsets, int B, const float* calib, const int32_t* img_hw,
                               const double* scope, int npoints, uint32_t seed, void* workspace, float* out_xyz, int32_t* out_src,
@@ -251,12 +298,26 @@ static void scene_fill_frames(SceneFrames& F, const float* raw, const int64_t* o
     F.use_scope = scope != nullptr;
     for (int q = 0; q < 6; q++) F.scope[q] = scope ? scope[q] : 0.0;
     F.B = B; F.npoints = npoints; F.seed = seed;
-    F.NP = 16;
-    while (F.NP < npoints) F.NP <<= 1;
+    F.NP = scene_pow2(npoints);
     F.counters = static_cast<int32_t*>(workspace);
     F.list = reinterpret_cast<uint2*>(static_cast<char*>(workspace) + scene_list_offset(B));
     F.out_xyz = out_xyz; F.out_src = out_src; F.nvalid = nvalid; F.status = status;
 }
+
+// Behind a pass's small-form workspace (small_bytes of it), for npoints > SCENE_SMALL_MAX:  key arrays (B, NP) u64 on the next
+// 256-byte boundary | totals (B) i32
+static size_t scene_large_offset(size_t small_bytes) { return ((small_bytes + 255) / 256) * 256; }
+static size_t scene_large_bytes(size_t small_bytes, int B, int npoints) {
+    if (npoints <= SCENE_SMALL_MAX) return small_bytes;
+    return scene_large_offset(small_bytes) + (size_t)B * scene_pow2(npoints) * sizeof(u64) + (size_t)B * sizeof(int32_t);
+}
+static void scene_fill_large(SceneFrames& F, void* workspace, size_t small_bytes) {
+    char* base = static_cast<char*>(workspace) + scene_large_offset(small_bytes);
+    F.large_keys = reinterpret_cast<u64*>(base);
+    F.large_total = reinterpret_cast<int32_t*>(base + (size_t)F.B * F.NP * sizeof(u64));
+}
+// the exact ascending sort of every frame's NP keys through HBM, in plain launches on s (scene.hip)
+int scene_large_shuffle(const char* who, const SceneFrames& F, hipStream_t s);
 
 static int scene_reset_counters(const char* who, const SceneFrames& F, hipStream_t s) {
     if (prcnn_fill_words(F.counters, 0u, (size_t)F.B * 2, s) != hipSuccess) return prcnn_fail(PRCNN_EHIP, "%s: memset failed", who);

@@ -25,8 +25,11 @@
 //                          scene_append: removed points never enter the candidate list.
 //   tscene_paste_kernel  : one workgroup per (accepted object, frame): appends the object's points to the same list with their
 //                          far bit and draw key (one atomic per object).
-//   tscene_sample_kernel : one workgroup per frame: scene_select_sort; the row writer reads the raw scan (scene_rect) or the
-//                          database (applying y_shift) and applies step 5 as it writes.
+//   tscene_sample_kernel : npoints <= 16384.  One workgroup per frame: scene_select_sort; the row writer reads the raw scan
+//                          (scene_rect) or the database (applying y_shift) and applies step 5 as it writes.
+//   16384 < npoints <= 65536 (prcnn_train_scene_prepare_large) replaces the sample launch as scene.hip does:
+//   tscene_select_large_kernel (the draw into the frame's HBM key array), scene_large_shuffle (scene.hip's three sort kernels),
+//   tscene_rows_kernel (one thread per output row, the same row writer).
 // The frame head of the params, the projection, the append, the draw and the host prelude are scene_common.h's.
 // No (N + P) cloud is materialised and nothing synchronises with the host between the launches.  The selected set and the output
 // order depend on (seed, frame, identity) only, never on the order in which the atomics append.
@@ -202,77 +205,115 @@ __global__ __launch_bounds__(TS_PASTE_THREADS) void tscene_paste_kernel(TrainSce
     if (tid == 0 && nfar > 0) atomicAdd(P.counters + b * 2 + 1, nfar);
 }
 
+// where the pasted identities of a frame live: filled by one thread (ts_paste_fill), read by the row writer after a barrier
+struct TsPaste {
+    unsigned base[TS_MAX_ACCEPT + 1];         // identity (minus n_raw) of every accepted object's first point
+    int64_t first[TS_MAX_ACCEPT];             // its first database row
+    double shift[TS_MAX_ACCEPT];
+};
+__device__ __forceinline__ void ts_paste_fill(const TrainSceneParams& P, int b, int na, TsPaste& T) {
+    unsigned run = 0;
+    for (int a = 0; a < na; ++a) {
+        int64_t first;
+        const int m = ts_object_points(P, b, a, first);
+        T.base[a] = run; T.first[a] = first; T.shift[a] = P.acc_shift[(size_t)b * P.K + a];
+        run += (unsigned)m;
+    }
+    T.base[na] = run;
+}
+
+// the frame's augmentation as tscene_box_kernel reported it
+struct TsAug {
+    bool rot, scl, flip;
+    double rc, rs;
+    float fs;
+};
+__device__ __forceinline__ TsAug ts_load_aug(const TrainSceneParams& P, int b) {
+    const double* A = P.aug + (size_t)b * 8;
+    TsAug g;
+    g.rot = A[3] == A[3]; g.scl = A[6] == A[6]; g.flip = A[7] != 0.0;
+    g.rc = A[4]; g.rs = A[5]; g.fs = (float)A[6];
+    return g;
+}
+
+// output row j of frame b is the candidate with identity i: a raw point (i < n_raw) or a pasted one, augmented as it is written
+__device__ __forceinline__ void ts_write_row(const TrainSceneParams& P, int b, int j, unsigned i, int na, const TsPaste& T, const TsAug& g) {
+    const int np = P.npoints;
+    const int64_t o = P.off[b];
+    const unsigned n_raw = (unsigned)(P.off[b + 1] - o);
+    float* oxyz = P.out_xyz + (size_t)b * np * 3;
+    float* oin = P.out_input ? P.out_input + (size_t)b * np * 4 : nullptr;
+    float x, y, z, w;
+    if (i < n_raw) {
+        const float4 p = P.raw[o + i];
+        scene_rect(p, P.calib + b * 24, x, y, z);
+        w = p.w;
+    } else {
+        const unsigned jj = i - n_raw;
+        int a = 0;
+        while (a + 1 < na && jj >= T.base[a + 1]) ++a;
+        const int64_t q = T.first[a] + (jj - T.base[a]);
+        x = P.db_pts[q * 3];
+        y = (float)((double)P.db_pts[q * 3 + 1] - T.shift[a]);    // new_gt_points[:, 1] -= move_height (:470)
+        z = P.db_pts[q * 3 + 2];
+        w = P.db_int[q];
+    }
+    if (g.rot) {
+        const double dx = (double)x, dz = (double)z;
+        x = (float)(dx * g.rc + dz * (-g.rs));
+        z = (float)(dx * g.rs + dz * g.rc);
+    }
+    if (g.scl) { x = x * g.fs; y = y * g.fs; z = z * g.fs; }
+    if (g.flip) x = -x;
+    const float feat = w - 0.5f;
+    oxyz[j * 3 + 0] = x; oxyz[j * 3 + 1] = y; oxyz[j * 3 + 2] = z;
+    if (oin) { oin[j * 4 + 0] = x; oin[j * 4 + 1] = y; oin[j * 4 + 2] = z; oin[j * 4 + 3] = feat; }
+    P.out_feat[(size_t)b * np + j] = feat;
+    P.out_src[(size_t)b * np + j] = (int32_t)i;
+}
+
 __global__ __launch_bounds__(SCENE_THREADS) void tscene_sample_kernel(TrainSceneParams P) {
     extern __shared__ u64 keys[];
     __shared__ SceneLds lds;
-    __shared__ unsigned pbase[TS_MAX_ACCEPT + 1];               // identity (minus n_raw) of every accepted object's first point
-    __shared__ int64_t pfirst[TS_MAX_ACCEPT];                   // its first database row
-    __shared__ double pshift[TS_MAX_ACCEPT];
+    __shared__ TsPaste paste;
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int64_t o = P.off[b];
-    const unsigned n_raw = (unsigned)(P.off[b + 1] - o);
-    const uint2* __restrict__ L = ts_list(P, b);
     const int n = P.counters[b * 2], f = P.counters[b * 2 + 1];
     const int np = P.npoints;
-    float* oxyz = P.out_xyz + (size_t)b * np * 3;
-    float* oin = P.out_input ? P.out_input + (size_t)b * np * 4 : nullptr;
-    float* ofeat = P.out_feat + (size_t)b * np;
-    int32_t* osrc = P.out_src + (size_t)b * np;
     const int na = ts_accepted(P, b);
     if (tid == 0) {
         P.nvalid[b] = n;
-        unsigned run = 0;
-        for (int a = 0; a < na; ++a) {
-            int64_t first;
-            const int m = ts_object_points(P, b, a, first);
-            pbase[a] = run; pfirst[a] = first; pshift[a] = P.acc_shift[(size_t)b * P.K + a];
-            run += (unsigned)m;
-        }
-        pbase[na] = run;
+        ts_paste_fill(P, b, na, paste);                         // ordered before the row writer by scene_select_sort's barriers
     }
     if (n == 0) {
         scene_empty_frame(P, b, P.out_feat, P.out_input);
         return;
     }
-    const SceneSel ss = scene_select_sort(L, n, f, np, P.NP, P.seed, (unsigned)b, keys, lds);
+    const SceneSel ss = scene_select_sort(ts_list(P, b), n, f, np, P.NP, P.seed, (unsigned)b, keys, lds);
     const int total = ss.total;                                 // == npoints unless the status is 1
     // ---- rows in shuffled order (a short selection -- status 1 -- repeats cyclically), augmented as they are written
-    const double* A = P.aug + (size_t)b * 8;
-    const bool rot = A[3] == A[3], scl = A[6] == A[6], flip = A[7] != 0.0;
-    const double rc = A[4], rs = A[5];
-    const float fs = (float)A[6];
-    const float* c = P.calib + b * 24;
-    for (int j = tid; j < np; j += SCENE_THREADS) {
-        const unsigned i = (unsigned)keys[lds_phys(j < total ? j : j % total)];
-        float x, y, z, w;
-        if (i < n_raw) {
-            const float4 p = P.raw[o + i];
-            scene_rect(p, c, x, y, z);
-            w = p.w;
-        } else {
-            const unsigned jj = i - n_raw;
-            int a = 0;
-            while (a + 1 < na && jj >= pbase[a + 1]) ++a;
-            const int64_t q = pfirst[a] + (jj - pbase[a]);
-            x = P.db_pts[q * 3];
-            y = (float)((double)P.db_pts[q * 3 + 1] - pshift[a]);    // new_gt_points[:, 1] -= move_height (:470)
-            z = P.db_pts[q * 3 + 2];
-            w = P.db_int[q];
-        }
-        if (rot) {
-            const double dx = (double)x, dz = (double)z;
-            x = (float)(dx * rc + dz * (-rs));
-            z = (float)(dx * rs + dz * rc);
-        }
-        if (scl) { x = x * fs; y = y * fs; z = z * fs; }
-        if (flip) x = -x;
-        const float feat = w - 0.5f;
-        oxyz[j * 3 + 0] = x; oxyz[j * 3 + 1] = y; oxyz[j * 3 + 2] = z;
-        if (oin) { oin[j * 4 + 0] = x; oin[j * 4 + 1] = y; oin[j * 4 + 2] = z; oin[j * 4 + 3] = feat; }
-        ofeat[j] = feat;
-        osrc[j] = (int32_t)i;
-    }
+    const TsAug g = ts_load_aug(P, b);
+    for (int j = tid; j < np; j += SCENE_THREADS) ts_write_row(P, b, j, (unsigned)keys[lds_phys(j < total ? j : j % total)], na, paste, g);
     if (tid == 0) P.status[b] = ss.status;
+}
+
+// ---- 16384 < npoints <= 65536: select -> scene_large_shuffle -> rows (scene.hip's header) ------------------------------------------
+__global__ __launch_bounds__(SCENE_THREADS) void tscene_select_large_kernel(TrainSceneParams P) {
+    __shared__ SceneLds lds;
+    const int b = blockIdx.x;
+    scene_select_large(P, b, ts_list(P, b), P.out_feat, P.out_input, lds);
+}
+
+// grid (ceil(npoints / SCENE_THREADS), B): one thread per output row
+__global__ __launch_bounds__(SCENE_THREADS) void tscene_rows_kernel(TrainSceneParams P) {
+    __shared__ TsPaste paste;
+    const int b = blockIdx.y, j = blockIdx.x * SCENE_THREADS + threadIdx.x;
+    const int total = P.large_total[b];
+    if (total == 0) return;                                     // block-uniform: the whole frame was written by the select launch
+    const int na = ts_accepted(P, b);
+    if (threadIdx.x == 0) ts_paste_fill(P, b, na, paste);
+    __syncthreads();
+    if (j >= P.npoints) return;
+    ts_write_row(P, b, j, scene_large_identity(P, b, j, total), na, paste, ts_load_aug(P, b));
 }
 
 PRCNN_API size_t prcnn_train_scene_workspace_bytes(int64_t total_points, int B, int K, int db_max_points) {
@@ -281,8 +322,9 @@ PRCNN_API size_t prcnn_train_scene_workspace_bytes(int64_t total_points, int B, 
     return entries * sizeof(uint2) + scene_list_offset(B) + 64;
 }
 
-PRCNN_API int prcnn_train_scene_prepare(const float* raw, const int64_t* offsets, int B, int64_t total_points, int max_points_per_frame,
-                                        const float* calib, const int32_t* img_hw, const double* scope, int npoints, uint32_t seed,
+// both exports; max_npoints = the export's domain
+static int train_scene_prepare_any(const char* who, int max_npoints, const float* raw, const int64_t* offsets, int B, int64_t total_points,
+                                   int max_points_per_frame, const float* calib, const int32_t* img_hw, const double* scope, int npoints, uint32_t seed,
                                         const float* gt_boxes3d, const float* gt_alpha, const int32_t* num_gt, int G,
                                         const int32_t* acc_count, const int32_t* acc_db_id, const float* acc_boxes3d, const float* acc_alpha,
                                         const double* acc_y_shift, const int32_t* acc_status, int K, const float* db_points,
@@ -290,28 +332,33 @@ PRCNN_API int prcnn_train_scene_prepare(const float* raw, const int64_t* offsets
                                         const double* aug_cfg, float* out_xyz, float* out_input, float* out_features, int32_t* out_src,
                                         int32_t* nvalid, int32_t* status, float* out_gt_boxes3d, int32_t* out_num_gt, double* aug,
                                         void* workspace, size_t workspace_bytes, prcnn_stream_t stream) {
-    const char* who = "prcnn_train_scene_prepare";
-    PRCNN_REQUIRE(npoints > 0 && npoints <= 16384, "prcnn_train_scene_prepare: npoints=%d (1..16384: the shuffle is one LDS-resident sort per frame)", npoints);
-    PRCNN_REQUIRE(G >= 0 && K >= 0 && K <= TS_MAX_ACCEPT, "prcnn_train_scene_prepare: G=%d K=%d (K: 0..%d accepted objects per frame)", G, K, TS_MAX_ACCEPT);
-    PRCNN_REQUIRE(G + K <= TS_MAX_BOXES, "prcnn_train_scene_prepare: G + K = %d > %d (what prcnn_rpn_labels takes per frame)", G + K, TS_MAX_BOXES);
-    PRCNN_REQUIRE(D >= 0 && db_max_points >= 0, "prcnn_train_scene_prepare: bad database shape D=%d max=%d", D, db_max_points);
-    PRCNN_REQUIRE(aug_cfg, "prcnn_train_scene_prepare: null aug_cfg");
+    if (max_npoints == SCENE_SMALL_MAX)
+        PRCNN_REQUIRE(npoints > 0 && npoints <= 16384, "%s: npoints=%d (1..16384: the shuffle is one LDS-resident sort per frame)", who, npoints);
+    else
+        PRCNN_REQUIRE(npoints > 0 && npoints <= SCENE_LARGE_MAX, "%s: npoints=%d (1..65536: the shuffle sorts at most four 16384-key chunks per frame)", who, npoints);
+    const bool large = npoints > SCENE_SMALL_MAX;
+    PRCNN_REQUIRE(G >= 0 && K >= 0 && K <= TS_MAX_ACCEPT, "%s: G=%d K=%d (K: 0..%d accepted objects per frame)", who, G, K, TS_MAX_ACCEPT);
+    PRCNN_REQUIRE(G + K <= TS_MAX_BOXES, "%s: G + K = %d > %d (what prcnn_rpn_labels takes per frame)", who, G + K, TS_MAX_BOXES);
+    PRCNN_REQUIRE(D >= 0 && db_max_points >= 0, "%s: bad database shape D=%d max=%d", who, D, db_max_points);
+    PRCNN_REQUIRE(aug_cfg, "%s: null aug_cfg", who);
     const bool paste = acc_count != nullptr && K > 0;
     const int Kp = paste ? K : 0;
     int rc = scene_check_frames(who, raw, offsets, B, total_points, max_points_per_frame, calib, (long)Kp * db_max_points, SCENE_THREADS);
     if (rc != PRCNN_OK || B == 0) return rc;
     PRCNN_REQUIRE(img_hw && out_xyz && out_features && out_src && nvalid && status && out_num_gt && aug,
-                  "prcnn_train_scene_prepare: null pointer");
-    PRCNN_REQUIRE(G + K == 0 || out_gt_boxes3d, "prcnn_train_scene_prepare: null out_gt_boxes3d");
-    PRCNN_REQUIRE(G == 0 || (gt_boxes3d && gt_alpha), "prcnn_train_scene_prepare: null gt_boxes3d / gt_alpha");
+                  "%s: null pointer", who);
+    PRCNN_REQUIRE(G + K == 0 || out_gt_boxes3d, "%s: null out_gt_boxes3d", who);
+    PRCNN_REQUIRE(G == 0 || (gt_boxes3d && gt_alpha), "%s: null gt_boxes3d / gt_alpha", who);
     PRCNN_REQUIRE(!paste || (acc_db_id && acc_boxes3d && acc_alpha && acc_y_shift && acc_status && db_offsets &&
                              (db_max_points == 0 || (db_points && db_intensity))),
-                  "prcnn_train_scene_prepare: the accepted objects need db_id, boxes3d, alpha, y_shift, status and the database");
-    PRCNN_REQUIRE(workspace && workspace_bytes >= prcnn_train_scene_workspace_bytes(total_points, B, Kp, db_max_points),
-                  "prcnn_train_scene_prepare: workspace too small");
+                  "%s: the accepted objects need db_id, boxes3d, alpha, y_shift, status and the database", who);
+    const size_t small_bytes = prcnn_train_scene_workspace_bytes(total_points, B, Kp, db_max_points);
+    PRCNN_REQUIRE(workspace && workspace_bytes >= scene_large_bytes(small_bytes, B, npoints), "%s: workspace too small", who);
+    PRCNN_REQUIRE(!large || ((uintptr_t)workspace % 8) == 0, "%s: workspace must be 8-byte aligned", who);
     hipStream_t s = (hipStream_t)stream;
     TrainSceneParams P = {};
     scene_fill_frames(P, raw, offsets, B, calib, img_hw, scope, npoints, seed, workspace, out_xyz, out_src, nvalid, status);
+    if (large) scene_fill_large(P, workspace, small_bytes);
     P.gt = gt_boxes3d; P.gt_alpha = gt_alpha; P.num_gt = num_gt; P.G = G;
     P.acc_count = paste ? acc_count : nullptr; P.acc_id = acc_db_id; P.acc_boxes = acc_boxes3d; P.acc_alpha = acc_alpha;
     P.acc_shift = acc_y_shift; P.acc_status = acc_status; P.K = K;
@@ -331,5 +378,35 @@ PRCNN_API int prcnn_train_scene_prepare(const float* raw, const int64_t* offsets
         hipLaunchKernelGGL(tscene_paste_kernel, dim3(K, B), dim3(TS_PASTE_THREADS), 0, s, P);
         PRCNN_LAUNCH_CHECK("prcnn_train_scene_prepare(paste)");
     }
-    return scene_launch_sample<tscene_sample_kernel>(who, P, s);
+    if (!large) return scene_launch_sample<tscene_sample_kernel>(who, P, s);
+    hipLaunchKernelGGL(tscene_select_large_kernel, dim3(B), dim3(SCENE_THREADS), 0, s, P);
+    PRCNN_LAUNCH_CHECK("prcnn_train_scene_prepare_large(select)");
+    if ((rc = scene_large_shuffle(who, P, s)) != PRCNN_OK) return rc;
+    hipLaunchKernelGGL(tscene_rows_kernel, dim3(prcnn_divup(npoints, SCENE_THREADS), B), dim3(SCENE_THREADS), 0, s, P);
+    PRCNN_LAUNCH_CHECK("prcnn_train_scene_prepare_large(rows)");
+    return PRCNN_OK;
+}
+
+// the argument list both exports share (include/prcnn_pointops.h states it in full)
+#define TS_ARGS_DECL                                                                                                                                  \
+    const float* raw, const int64_t* offsets, int B, int64_t total_points, int max_points_per_frame, const float* calib, const int32_t* img_hw,       \
+        const double* scope, int npoints, uint32_t seed, const float* gt_boxes3d, const float* gt_alpha, const int32_t* num_gt, int G,                \
+        const int32_t* acc_count, const int32_t* acc_db_id, const float* acc_boxes3d, const float* acc_alpha, const double* acc_y_shift,              \
+        const int32_t* acc_status, int K, const float* db_points, const float* db_intensity, const int64_t* db_offsets, int D,                        \
+        int db_max_points, const double* aug_cfg, float* out_xyz, float* out_input, float* out_features, int32_t* out_src, int32_t* nvalid,           \
+        int32_t* status, float* out_gt_boxes3d, int32_t* out_num_gt, double* aug, void* workspace, size_t workspace_bytes, prcnn_stream_t stream
+#define TS_ARGS                                                                                                                              \
+    raw, offsets, B, total_points, max_points_per_frame, calib, img_hw, scope, npoints, seed, gt_boxes3d, gt_alpha, num_gt, G, acc_count,     \
+        acc_db_id, acc_boxes3d, acc_alpha, acc_y_shift, acc_status, K, db_points, db_intensity, db_offsets, D, db_max_points, aug_cfg, out_xyz, \
+        out_input, out_features, out_src, nvalid, status, out_gt_boxes3d, out_num_gt, aug, workspace, workspace_bytes, stream
+
+PRCNN_API int prcnn_train_scene_prepare(TS_ARGS_DECL) { return train_scene_prepare_any("prcnn_train_scene_prepare", SCENE_SMALL_MAX, TS_ARGS); }
+
+PRCNN_API size_t prcnn_train_scene_large_workspace_bytes(int64_t total_points, int B, int K, int db_max_points, int npoints) {
+    if (total_points < 0 || B < 0 || K < 0 || db_max_points < 0 || npoints < 0) return 0;
+    return scene_large_bytes(prcnn_train_scene_workspace_bytes(total_points, B, K, db_max_points), B, npoints);
+}
+
+PRCNN_API int prcnn_train_scene_prepare_large(TS_ARGS_DECL) {
+    return train_scene_prepare_any("prcnn_train_scene_prepare_large", SCENE_LARGE_MAX, TS_ARGS);
 }

@@ -109,7 +109,8 @@ def pack_scans(scans, calibs, img_shapes, pin=True):
 
 class ScenePreparer:
     """Batch version of get_rpn_sample's inference branch.  ``npoints`` / ``random_select`` as in KittiRCNNDataset
-    (kitti_rcnn_dataset.py:13); area_scope = cfg.PC_AREA_SCOPE or None for cfg.PC_REDUCE_BY_RANGE = False."""
+    (kitti_rcnn_dataset.py:13); area_scope = cfg.PC_AREA_SCOPE or None for cfg.PC_REDUCE_BY_RANGE = False.  npoints up to 65536:
+    above 16384 ops.scene_prepare takes the large export (the shuffle sorted through HBM) on its own."""
 
     def __init__(self, npoints=16384, area_scope=PC_AREA_SCOPE, device="cuda"):
         self.npoints = npoints
@@ -489,12 +490,18 @@ class TrainScenePreparer:
     road planes and the packed GT database in, the dictionary collate_batch would return out, on the device.  Settings carry their
     cfg names: GT_AUG_ENABLED (with gt_database), GT_EXTRA_NUM, GT_AUG_RAND_NUM, GT_AUG_APPLY_PROB (GT_AUG_HARD_RATIO belongs to the
     database), AUG_DATA, AUG_METHOD_LIST, AUG_METHOD_PROB, AUG_ROT_RANGE, RPN.USE_INTENSITY as use_intensity; area_scope =
-    cfg.PC_AREA_SCOPE or None for cfg.PC_REDUCE_BY_RANGE false; max_accept bounds the accepted objects per frame (K <= 64)."""
+    cfg.PC_AREA_SCOPE or None for cfg.PC_REDUCE_BY_RANGE false; max_accept bounds the accepted objects per frame (K <= 64).
+    large_clouds: False (the default) calls prcnn_train_scene_prepare, which refuses npoints > 16384; True calls
+    prcnn_train_scene_prepare_large, which takes 1..65536 and writes the same bytes up to 16384.  ScenePreparer switches on npoints by
+    itself; this class does not, because its refusal of 16385 points is asserted behaviour (tests/test_gpu_train_scene.py) that a
+    default must not change: a dense training batch is asked for by name."""
 
     def __init__(self, npoints=16384, area_scope=PC_AREA_SCOPE, gt_database=None, GT_AUG_ENABLED=True, GT_EXTRA_NUM=15,
                  GT_AUG_RAND_NUM=True, GT_AUG_APPLY_PROB=1.0, AUG_DATA=True, AUG_METHOD_LIST=("rotation", "scaling", "flip"),
-                 AUG_METHOD_PROB=(1.0, 1.0, 0.5), AUG_ROT_RANGE=18, use_intensity=False, max_accept=16, try_times=100, device="cuda"):
+                 AUG_METHOD_PROB=(1.0, 1.0, 0.5), AUG_ROT_RANGE=18, use_intensity=False, max_accept=16, try_times=100, device="cuda",
+                 large_clouds=False):
         self.npoints = npoints
+        self.large_clouds = bool(large_clouds)
         self.scope = None if area_scope is None else [float(v) for ax in area_scope for v in ax]
         self.db = gt_database if GT_AUG_ENABLED else None
         if GT_AUG_ENABLED and gt_database is None:
@@ -543,7 +550,7 @@ class TrainScenePreparer:
                                  self.try_times, self.max_accept, seed)
         out = ops.train_scene_prepare(t["raw"], t["offsets"], packed["max_points"], t["calib"], t["img_hw"], self.scope, self.npoints, seed,
                                       t["gt_boxes3d"], t["gt_alpha"], t["num_gt"], acc, self.db, self.methods, self.prob, self.rot_range,
-                                      self.use_intensity)
+                                      self.use_intensity, large=self.large_clouds)
         out["rpn_cls_label"], out["rpn_reg_label"] = ops.rpn_labels(out["pts_rect"], out["gt_boxes3d"], out["num_gt"])
         if acc is not None:
             out.update(gt_aug_status=acc["status"], count=acc["count"], db_id=acc["db_id"], stats=acc["stats"])

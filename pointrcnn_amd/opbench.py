@@ -114,6 +114,42 @@ def _train_scene_device(prep, t, max_points, seed):
     return ops.rpn_labels(out["pts_rect"], out["gt_boxes3d"], out["num_gt"])
 
 
+def scene_large_rows(dev, B=8, n_raw=400000, npoints=65536, D=2000):
+    """Both input builders at BASELINE config 5 (65 536 points per frame, bs8) on 400 000-point synthetic scans with fov_frac 0.2:
+    the large form (select, HBM sort, rows) and, alternately in the same process on the same scans, the one-workgroup form at
+    16 384 points -- the cost of the HBM sort against the LDS sort.  Every row: median of five windows of 20 launches, min and max."""
+    from . import kitti_input
+    r = np.random.default_rng(7)
+    box = lambda n: (r.random((n, 7)) * [60., .8, 60., .3, .3, 1., 6.28] + [-30., 1.2, 5., 1.4, 1.5, 3.4, -3.14]).astype(np.float32)   # noqa: E731
+    dbb, npd = box(D), r.integers(5, 400, D)
+    gdb = kitti_input.GTDatabase.from_arrays(dbb, np.zeros(D, np.float32), [r.random((int(n), 3)).astype(np.float32) + dbb[i, :3] for i, n in enumerate(npd)],
+                                             [r.random(int(n)).astype(np.float32) for n in npd], device=dev)
+    calib = kitti_input.Calibration.from_text(kitti_input.KITTI_CALIB_TXT)
+    scans = [kitti_input.synthetic_scan(n_raw + 97 * b, seed=900 + b, fov_frac=0.2) for b in range(B)]
+    labels = [box(12) for _ in range(B)]
+    preps = {n: kitti_input.TrainScenePreparer(npoints=n, gt_database=gdb, device=dev, large_clouds=n > ops.SCENE_SMALL_MAX) for n in (npoints, 16384)}
+    packed = preps[npoints].pack(scans, [calib] * B, [(375, 1242)] * B, labels, [np.zeros(12, np.float32)] * B, labels, [[0.0, -1.0, 0.0, 1.65]] * B)
+    t = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in packed.items()}
+    scope = preps[npoints].scope
+    acc = gdb.sample(t["all_gt_boxes3d"], t["num_all_gt"], t["planes"], seed=5)
+    st = ops.scene_prepare(t["raw"], t["offsets"], packed["max_points"], t["calib"], t["img_hw"], scope, npoints, 5)
+    calls = {}
+    for n in (npoints, 16384):
+        calls["scene_prepare", n] = lambda n=n: ops.scene_prepare(t["raw"], t["offsets"], packed["max_points"], t["calib"], t["img_hw"], scope, n, 5)
+        calls["train_scene_prepare", n] = lambda n=n: ops.train_scene_prepare(
+            t["raw"], t["offsets"], packed["max_points"], t["calib"], t["img_hw"], scope, n, 5, t["gt_boxes3d"], t["gt_alpha"], t["num_gt"], acc, gdb,
+            large=n > ops.SCENE_SMALL_MAX)
+    times = {k: [] for k in calls}
+    for _ in range(5):                                           # the forms alternate, window by window
+        for k, fn in calls.items():
+            times[k].append(timeit(fn))
+    for (name, n), ts in times.items():
+        print(json.dumps({"op": name, "shape": "B%d ~%dk raw (fov_frac 0.2, %d..%d valid) npoints %d%s" % (
+            B, n_raw // 1000, int(st[3].min()), int(st[3].max()), n, " K%d D%d (builder only: no sampler, no labels)" % (acc["db_id"].shape[1], D)
+            if name.startswith("train") else ""), "form": "large (select, HBM sort, rows)" if n > ops.SCENE_SMALL_MAX else "one workgroup per frame",
+            "median_us": round(float(np.median(ts)) * 1e6, 1), "min_us": round(min(ts) * 1e6, 1), "max_us": round(max(ts) * 1e6, 1)}), flush=True)
+
+
 def gt_database_row(dev, B=8, n_raw=120000, nbox=8):
     """The GT-database builder (kitti_input.GTDatabase.from_kitti's device pass) at one KITTI-sized batch: count, scan, the host read
     of the total, fill.  Next to its time the traffic floor: the raw scans read twice (once per pass) plus the outputs written."""
@@ -831,9 +867,15 @@ def eval_loop_rows(dev, B=16, nbatches=3, rounds=5):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
-    ap.add_argument("--only", default=None, help="run one row family only: eval_stats | optimizer | rpn_loss_kinds | train_split (= train_stack) | train_wgrad | head_tail | result_writer | eval_loop")
+    ap.add_argument("--only", default=None, help="run one row family only: scene_large | train_scene | eval_stats | optimizer | rpn_loss_kinds | train_split (= train_stack) | train_wgrad | head_tail | result_writer | eval_loop")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
+    if args.only == "scene_large":
+        scene_large_rows(dev)
+        return
+    if args.only == "train_scene":
+        train_scene_rows(dev)
+        return
     if args.only == "result_writer":
         result_writer_rows(dev)
         return
@@ -979,6 +1021,9 @@ def main():
 
     # ---- the RPN training batch from raw scans (kitti_input.TrainScenePreparer) next to the separate passes
     train_scene_rows(dev, B=4 if args.quick else 16)
+    # ---- both input builders at 65 536 points per frame (BASELINE config 5) next to the 16 384-point call on the same scans
+    if not args.quick:
+        scene_large_rows(dev)
 
     # ---- the GT-augmentation database from raw scans and labels (kitti_input.GTDatabase.from_kitti)
     gt_database_row(dev)

@@ -1516,19 +1516,38 @@ def _sample_outputs(B, npoints, dev):
 # ---------------------------------------------------------------------------------------------------------
 # RPN input builder (csrc/scene.hip)
 # ---------------------------------------------------------------------------------------------------------
-def scene_prepare(raw, offsets, max_points_per_frame, calib, img_hw, scope, npoints, seed):
+SCENE_SMALL_MAX = 16384       # npoints up to here: the one-workgroup form of the draw (csrc/scene_common.h)
+SCENE_LARGE_MAX = 65536       # npoints up to here: the large exports (the shuffle sorted through HBM)
+
+
+def _large_npoints(name, npoints):
+    """the domain of the large exports, held before any allocation or launch"""
+    if not 1 <= int(npoints) <= SCENE_LARGE_MAX:
+        raise _cabi.PointOpsError("%s: npoints=%d (1..%d)" % (name, int(npoints), SCENE_LARGE_MAX))
+
+
+def scene_prepare(raw, offsets, max_points_per_frame, calib, img_hw, scope, npoints, seed, large=None, workspace=None):
     """raw (total,4) f32 scans back to back, offsets (B+1) i64, calib (B,24) f32 [M 4x3 | P2 3x4], img_hw (B,2) i32 -- all on
-    the device; scope: 6 host floats [x0 x1 y0 y1 z0 z1] or None.
+    the device; scope: 6 host floats [x0 x1 y0 y1 z0 z1] or None.  large: True = prcnn_scene_prepare_large (npoints 1..65536),
+    False = prcnn_scene_prepare (1..16384), None = the large export when npoints > 16384.
     -> pts_rect (B,npoints,3), intensity - 0.5 (B,npoints), src index (B,npoints) i32, nvalid (B) i32, status (B) i32
     [lib/datasets/kitti_rcnn_dataset.py:246-310 for a whole batch; see prcnn_scene_prepare]"""
+    if large is None:
+        large = int(npoints) > SCENE_SMALL_MAX
+    if large:
+        _large_npoints("scene_prepare", npoints)
     B, total, dev = _frames(raw, offsets, calib, img_hw)
     L = _cabi.lib()
-    ws = torch.empty((int(L.prcnn_scene_workspace_bytes(total, B)),), dtype=torch.uint8, device=dev)
+    if large:
+        need, fn, name = int(L.prcnn_scene_large_workspace_bytes(total, B, int(npoints))), L.prcnn_scene_prepare_large, "prcnn_scene_prepare_large"
+    else:
+        need, fn, name = int(L.prcnn_scene_workspace_bytes(total, B)), L.prcnn_scene_prepare, "prcnn_scene_prepare"
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev) if workspace is None else workspace
     xyz, src, nvalid, status = _sample_outputs(B, npoints, dev)
     inten = torch.empty((B, npoints), dtype=_F32, device=dev)
-    _cabi.check(L.prcnn_scene_prepare(_p(raw), _p(offsets), B, total, int(max_points_per_frame), _p(calib), _p(img_hw), _scope(scope),
-                                      int(npoints), int(seed) & 0xFFFFFFFF, _p(xyz), _p(inten), _p(src), _p(nvalid), _p(status), _p(ws),
-                                      ws.numel(), _stream()), "prcnn_scene_prepare")
+    _cabi.check(fn(_p(raw), _p(offsets), B, total, int(max_points_per_frame), _p(calib), _p(img_hw), _scope(scope),
+                   int(npoints), int(seed) & 0xFFFFFFFF, _p(xyz), _p(inten), _p(src), _p(nvalid), _p(status), _p(ws),
+                   ws.numel(), _stream()), name)
     return xyz, inten, src, nvalid, status
 
 
@@ -1540,14 +1559,17 @@ AUG_METHODS = ("rotation", "scaling", "flip")
 
 def train_scene_prepare(raw, offsets, max_points_per_frame, calib, img_hw, scope, npoints, seed, gt_boxes3d, gt_alpha, num_gt=None,
                         accepted=None, db=None, aug_methods=AUG_METHODS, aug_prob=(1.0, 1.0, 0.5), aug_rot_range=18,
-                        use_intensity=False, workspace=None):
+                        use_intensity=False, workspace=None, large=False):
     """get_rpn_sample's TRAIN path between the GT-augmentation sampling loop and the label generation, for a whole batch
     (prcnn_train_scene_prepare).  raw .. seed as scene_prepare; gt_boxes3d (B,G,7), gt_alpha (B,G), num_gt (B) i32 or None: the
     training labels; accepted = gt_aug_sample's dict or None (GT_AUG_ENABLED false), db = the packed database (an object with
     points (P,3), intensity (P,), offsets (D+1,) i64, size, max_points: kitti_input.GTDatabase); aug_methods = the names of
     cfg.AUG_METHOD_LIST that run (() = cfg.AUG_DATA false), aug_prob = cfg.AUG_METHOD_PROB, aug_rot_range = cfg.AUG_ROT_RANGE.
     -> dict pts_rect (B,npoints,3), pts_input (the same tensor, or (B,npoints,4) when use_intensity), pts_features (B,npoints,1),
-    gt_boxes3d (B,G+K,7), num_gt (B), src, nvalid, status, aug (B,8) f64 -- see include/prcnn_pointops.h"""
+    gt_boxes3d (B,G+K,7), num_gt (B), src, nvalid, status, aug (B,8) f64 -- see include/prcnn_pointops.h.
+    large: True = prcnn_train_scene_prepare_large (npoints 1..65536); the default keeps prcnn_train_scene_prepare (1..16384)."""
+    if large:
+        _large_npoints("train_scene_prepare", npoints)
     B, total, dev = _frames(raw, offsets, calib, img_hw)
     _chk(gt_boxes3d, "gt_boxes3d", ndim=3); _chk(gt_alpha, "gt_alpha", ndim=2)
     G = gt_boxes3d.shape[1]
@@ -1576,7 +1598,11 @@ def train_scene_prepare(raw, offsets, max_points_per_frame, calib, img_hw, scope
         if dbt[2].dtype != torch.int64 or dbt[2].shape[0] != D + 1 or dbt[1].shape[0] != dbt[0].shape[0]:
             raise ValueError("train_scene_prepare: db.offsets must be (D+1,) int64, db.intensity one value per point")
     L = _cabi.lib()
-    need = int(L.prcnn_train_scene_workspace_bytes(total, B, K, db_max))
+    if large:
+        need, fn, name = int(L.prcnn_train_scene_large_workspace_bytes(total, B, K, db_max, int(npoints))), L.prcnn_train_scene_prepare_large, \
+            "prcnn_train_scene_prepare_large"
+    else:
+        need, fn, name = int(L.prcnn_train_scene_workspace_bytes(total, B, K, db_max)), L.prcnn_train_scene_prepare, "prcnn_train_scene_prepare"
     ws = torch.empty((need,), dtype=torch.uint8, device=dev) if workspace is None else workspace
     xyz, src, nvalid, status = _sample_outputs(B, npoints, dev)
     pin = torch.empty((B, npoints, 4), dtype=_F32, device=dev) if use_intensity else None
@@ -1587,11 +1613,11 @@ def train_scene_prepare(raw, offsets, max_points_per_frame, calib, img_hw, scope
     hi = math.pi / aug_rot_range
     cfg = (ctypes.c_double * 10)(*([1.0 if m in aug_methods else 0.0 for m in AUG_METHODS] + [float(p) for p in aug_prob] +
                                    [-hi, hi, 0.95, 1.05]))
-    _cabi.check(L.prcnn_train_scene_prepare(
+    _cabi.check(fn(
         _p(raw), _p(offsets), B, total, int(max_points_per_frame), _p(calib), _p(img_hw), _scope(scope), int(npoints),
         int(seed) & 0xFFFFFFFF, _p(gt_boxes3d), _p(gt_alpha), _p(num_gt), G, _p(acc[0]), _p(acc[1]), _p(acc[2]), _p(acc[3]), _p(acc[4]), _p(acc[5]), K,
         _p(dbt[0]), _p(dbt[1]), _p(dbt[2]), D, db_max, cfg, _p(xyz), _p(pin), _p(feat), _p(src), _p(nvalid), _p(status), _p(out_gt),
-        _p(out_ng), _p(aug), _p(ws), ws.numel(), _stream()), "prcnn_train_scene_prepare")
+        _p(out_ng), _p(aug), _p(ws), ws.numel(), _stream()), name)
     return {"pts_rect": xyz, "pts_input": pin if use_intensity else xyz, "pts_features": feat.unsqueeze(-1), "gt_boxes3d": out_gt,
             "num_gt": out_ng, "src": src, "nvalid": nvalid, "status": status, "aug": aug}
 
